@@ -67,6 +67,9 @@ def parse():
                         'quirks Q3 / Q5 then see the LOCAL batch of bs/N images')
     p.add_argument('--device_prior', action='store_true', help='opt-in: the sampler prior from the device generator (Philox) instead of the CPU default generator (sde.py:26-28); a different random stream')
     p.add_argument('--no_roi_window', action='store_true', help='compute the full stride-4 FPN maps instead of the pixels the RoIAligns read (same results; A/B aid)')
+    p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                   help='after the timed steps, write what the last timed step returned (the predict outputs and its metric rows) as DIR/<name>.npy '
+                        '(see dump_outputs)')
     return p.parse_args()
 
 
@@ -168,19 +171,20 @@ def main():
             f.result()
         barrier()
 
-    def run_steps(k, pipelined=True):
-        rows, nfev = [], []
+    def run_steps(k, pipelined=True, keep_last=False):
+        """keep_last: also return the output dict of the last step with its metric rows (None otherwise); no earlier step's outputs are held"""
+        rows, nfev, last = [], [], None
         if pipe is not None and pipelined:
             def post(out, batch, engine, i=0):
                 return None
             futs = []
             for i in range(k):
                 first = (rank * k + i) * lbs
-                futs.append(pipe.submit(batches[i % 2], lambda out, batch, engine, first=first: (
+                futs.append(pipe.submit(batches[i % 2], lambda out, batch, engine, first=first, keep=keep_last and i == k - 1: (
                     E.metric_rows(out, batch, gt_joint, gt_vert, first, assets),
-                    (engine.last_info['hand_ode']['nfev'], engine.last_info['obj_ode']['nfev']))))
+                    (engine.last_info['hand_ode']['nfev'], engine.last_info['obj_ode']['nfev']), out if keep else None)))
             for f in futs:
-                r, n = f.result()
+                r, n, last = f.result()
                 rows.append(r)
                 nfev.append(n)
         else:
@@ -191,7 +195,10 @@ def main():
                 out = model(batches[i % 2], mode='predict')
                 rows.append(E.metric_rows(out, batches[i % 2], gt_joint, gt_vert, (rank * k + i) * lbs, assets))
                 nfev.append((eng.last_info['hand_ode']['nfev'], eng.last_info['obj_ode']['nfev']))
-        return E.gather_rows(torch.cat(rows, 0)), nfev     # the ONE collective of the evaluation
+            last = out if keep_last else None
+        if last is not None:
+            last = dict(last, metric_rows=rows[-1])
+        return E.gather_rows(torch.cat(rows, 0)), nfev, last     # the ONE collective of the evaluation
 
     # ---- timed region: K steps, no instrumentation -----------------------------------------------------------------
     def thread_cpu():
@@ -204,7 +211,7 @@ def main():
     thr0 = thread_cpu()
     cpu0 = sum(os.times()[:2])
     t0 = time.perf_counter()
-    all_rows, nfev = run_steps(args.steps)
+    all_rows, nfev, last = run_steps(args.steps, keep_last=args.dump_outputs is not None)
     ev_end = torch.cuda.Event(enable_timing=True)
     ev_end.record()
     barrier()
@@ -214,6 +221,11 @@ def main():
     import threading
     names = {t.native_id: t.name for t in threading.enumerate()}
     by_thread = sorted(((names.get(i, 'native thread (HIP runtime / OpenMP / RCCL)'), thr1[i] - thr0.get(i, 0.0)) for i in thr1), key=lambda kv: -kv[1])
+    dumped = None
+    if last is not None and rank == 0:                     # to the host before the repeats below run the step again
+        dumped = dump_outputs({k: (v.double() if v.dtype == torch.float64 else v.float()).cpu().numpy()
+                               for k, v in last.items() if torch.is_tensor(v)}, args.dump_outputs)
+    last = None
     if pipe is not None:                                   # per-step latencies: a short sequential run after the timed region
         step_events.clear()
         run_steps(min(args.steps, 5), pipelined=False)
@@ -366,6 +378,7 @@ def main():
             'metrics_rows_gathered': int(all_rows.shape[0]),
             'host_cpu': host_cpu,
             'fabric': fabric,
+            'dump_outputs': dumped,
         }
         post_rows = lambda out, batch, engine: E.metric_rows(out, batch, gt_joint, gt_vert, 0, assets)
         if world == 1 and not args.no_opt_in and (score_mfma, conv_mfma) == ('f32', 'f32'):
@@ -386,6 +399,32 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     return result
+
+
+DUMP_BYTES = 60_000_000            # --dump-outputs: array data of one run, all files together (npy headers add ~128 bytes per file)
+
+
+def dump_outputs(arrays, path, limit=DUMP_BYTES, seed=0):
+    """Writes every array of `arrays` ({name: float32 / float64 ndarray}) as <path>/<name>.npy and returns {name: [shape, elements written]}.
+    The arrays share `limit` bytes, smallest first: an array larger than its share is replaced by a seeded sample of its flattened
+    elements, kept in their original order.  The sample depends only on the array's size and `seed`, so two builds run with the same
+    arguments write the same elements."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    left, info = limit, {}
+    order = sorted(arrays, key=lambda k: (arrays[k].nbytes, k))
+    for i, name in enumerate(order):
+        a = arrays[name]
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        flat = a
+        share = left // (len(order) - i)
+        if a.nbytes > share:
+            idx = np.random.default_rng(seed).choice(a.size, share // a.itemsize, replace=False)
+            flat = a.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(path, name + '.npy'), flat)
+        left -= flat.nbytes
+        info[name] = [list(a.shape), int(flat.size)]
+    return info
 
 
 DETAIL_PATH = os.path.join('gpurun_out', 'bench_detail.json')

@@ -70,3 +70,28 @@ def test_traffic_is_per_workload_and_launch_weighted(tmp_path):
     assert bench.pmc_traffic(bench.CONV_CLASS_KERNELS, workload='cfg4', root=str(tmp_path)) is None      # no pass of that workload: null, never another one's
     assert bench.pmc_traffic(bench.CONV_CLASS_KERNELS, workload=None, root=str(tmp_path)) is None
     assert bench.workload_key(64, 100, 50) == 'cfg2' and bench.workload_key(128, 256, 100) == 'cfg4' and bench.workload_key(32, 100, 50) is None
+
+
+def test_dump_outputs_keeps_small_arrays_whole_and_samples_large_ones_within_the_budget(tmp_path):
+    import numpy as np
+    rng = np.random.default_rng(5)
+    arrays = {'small': rng.standard_normal((3, 4)).astype(np.float32), 'rows64': rng.standard_normal((50, 9)),
+              'big': rng.standard_normal((400, 300)).astype(np.float32), 'big64': rng.standard_normal(200000)}
+    limit = 600_000
+    info = bench.dump_outputs(arrays, str(tmp_path / 'a'), limit=limit)
+    again = bench.dump_outputs(arrays, str(tmp_path / 'b'), limit=limit)
+    assert info == again and sorted(info) == sorted(arrays)
+    total = 0
+    for name, a in arrays.items():
+        got = np.load(tmp_path / 'a' / (name + '.npy'))
+        assert got.dtype == a.dtype and info[name][0] == list(a.shape)
+        assert np.array_equal(got, np.load(tmp_path / 'b' / (name + '.npy')))       # same arguments, same elements
+        total += got.nbytes
+        if a.nbytes <= limit // len(arrays):
+            assert np.array_equal(got, a)
+        else:
+            assert got.ndim == 1 and 0 < got.size == info[name][1] < a.size
+            assert np.isin(got, a.reshape(-1)).all()                                 # a sample of the array's own elements
+    assert total <= limit
+    with pytest.raises(AssertionError):
+        bench.dump_outputs({'ints': np.arange(4)}, str(tmp_path / 'c'))
