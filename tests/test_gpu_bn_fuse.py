@@ -14,6 +14,30 @@ def _rand(shape, seed, scale=1.0):
     return (torch.randn(shape, generator=torch.Generator().manual_seed(seed)) * scale).cuda()
 
 
+def _check_forward_rows(part, y2, bm=None):
+    """the centred planes of the forward partial rows [rows][6][C] (2 .. 5: pivot | sum (v - pivot) | sum (v - pivot)^2 | count) against
+    the stored output y2 (M, C) in fp64: merged, count / mean / centred sum of squares of the whole map; with ``bm`` (M-tiles of bm
+    consecutive rows) row by row"""
+    p, s, q, n = (part[:, i].double() for i in range(2, 6))
+    M = y2.shape[0]
+    assert torch.equal(n.sum(0), torch.full_like(n[0], M))
+    tm = p + s / n
+    mean = (n * tm).sum(0) / M
+    m2 = (q - s * s / n).sum(0) + (n * (tm - mean) ** 2).sum(0)
+    ref_mean = y2.mean(0)
+    ref_m2 = ((y2 - ref_mean) ** 2).sum(0)
+    np.testing.assert_allclose(mean.cpu().numpy(), ref_mean.cpu().numpy(), rtol=2e-5, atol=2e-5 * float(y2.abs().max()))
+    np.testing.assert_allclose(m2.cpu().numpy(), ref_m2.cpu().numpy(), rtol=2e-5)
+    if bm is not None:
+        assert part.shape[0] == (M + bm - 1) // bm
+        for t in range(part.shape[0]):
+            blk = y2[t * bm:(t + 1) * bm]
+            dv = blk - blk[0]
+            assert torch.equal(p[t], blk[0]) and torch.equal(n[t], torch.full_like(n[t], blk.shape[0])), t
+            np.testing.assert_allclose(s[t].cpu().numpy(), dv.sum(0).cpu().numpy(), rtol=2e-5, atol=2e-5 * float(dv.abs().sum(0).max()))
+            np.testing.assert_allclose(q[t].cpu().numpy(), (dv * dv).sum(0).cpu().numpy(), rtol=2e-5)
+
+
 # (N, H, W, cin, cout, k): 128x128 / 128x64 / 64x64 tile classes of the direct kernel, ragged pixel counts and channel tails, and the Winograd shapes
 SHAPES = [(64, 32, 32, 64, 256, 1), (16, 16, 16, 256, 64, 1), (2, 9, 7, 32, 40, 1), (3, 8, 8, 36, 132, 1), (64, 16, 16, 128, 128, 3),
           (4, 32, 32, 64, 64, 3), (2, 10, 6, 16, 64, 3), (2, 8, 8, 12, 20, 3),
@@ -40,6 +64,9 @@ def test_forward_partial_sums_match_the_column_sums_of_the_output(N, H, W, cin, 
     s, ss = y2.sum(0), (y2 * y2).sum(0)
     np.testing.assert_allclose(part[:, 0].sum(0).cpu().numpy(), s.cpu().numpy(), rtol=2e-5, atol=2e-5 * float(y2.abs().sum(0).max()))
     np.testing.assert_allclose(part[:, 1].sum(0).cpu().numpy(), ss.cpu().numpy(), rtol=2e-5)
+    M = N * H * W
+    bm = None if k == 3 else (64 if f.rows == (M + 63) // 64 else 128)      # 1x1: the direct / persistent kernels' M-tiles of consecutive rows
+    _check_forward_rows(f.stats[:f.rows], y2, bm)
     # bit-reproducible
     f2 = ops.BnFuse()
     (ops.conv2d_nhwc(x, w, b, bn=f2) if k == 1 else ops.conv3x3_train(x, w, b, bn=f2))
@@ -243,3 +270,4 @@ def test_phase_convolutions_append_their_sums():
     part = f2.stats[:f2.rows].double()
     np.testing.assert_allclose(part[:, 0].sum(0).cpu().numpy(), u2.sum(0).cpu().numpy(), rtol=2e-5, atol=2e-5 * float(u2.abs().sum(0).max()))
     np.testing.assert_allclose(part[:, 1].sum(0).cpu().numpy(), (u2 * u2).sum(0).cpu().numpy(), rtol=2e-5)
+    _check_forward_rows(f2.stats[:f2.rows], u2)

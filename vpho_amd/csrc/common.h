@@ -120,3 +120,26 @@ __device__ inline void lin_src(int dst, float scale, int in_size, int& i0, int& 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef double f64x2 __attribute__((ext_vector_type(2)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+// Forward BatchNorm partial sums of a convolution epilogue (vpho_conv_desc.stats, ABI 13): the items of one channel as (pivot p, sum
+// (v - p), sum (v - p)^2, count n), the pivot one of the items.  Two such sums are combined about the LOWER one's pivot (the upper one's
+// when the lower has no items), so every difference formed is one of values near the channel's mean and nothing cancels however large
+// |mean| / std is.  shift_sums_xor: both lanes of a pair end with the same bits.
+struct ShiftSums { float p, s, q, n; };
+__device__ __forceinline__ ShiftSums shift_sums_add(ShiftSums lo, ShiftSums hi) {
+    const float P = lo.n > 0.f ? lo.p : hi.p;
+    const float dl = lo.p - P, dh = hi.p - P;                       // (a side without items has s = q = n = 0: its terms vanish)
+    return ShiftSums{P, (lo.s + lo.n * dl) + (hi.s + hi.n * dh), (lo.q + dl * (2.f * lo.s + lo.n * dl)) + (hi.q + dh * (2.f * hi.s + hi.n * dh)),
+                     lo.n + hi.n};
+}
+// A partial row has BN_STAT_PLANES planes of Cout floats.  Forward: sum v | sum v^2 (the plain sums, formed from the centred ones at the
+// store) | pivot | sum (v - pivot) | sum (v - pivot)^2 | count -- the finish reads planes 2 .. 5.  Backward: sum dy | sum dy * xhat.
+constexpr int BN_STAT_PLANES = 6;
+__device__ __forceinline__ void store_bn_row(float* o, int C, ShiftSums t) {
+    o[0] = t.n * t.p + t.s; o[C] = t.q + t.p * (2.f * t.s + t.n * t.p);
+    o[2 * C] = t.p; o[3 * C] = t.s; o[4 * C] = t.q; o[5 * C] = t.n;
+}
+__device__ __forceinline__ ShiftSums shift_sums_xor(ShiftSums a, int mask) {
+    const ShiftSums b{__shfl_xor(a.p, mask), __shfl_xor(a.s, mask), __shfl_xor(a.q, mask), __shfl_xor(a.n, mask)};
+    return (__lane_id() & mask) ? shift_sums_add(b, a) : shift_sums_add(a, b);
+}

@@ -669,9 +669,12 @@ __global__ __launch_bounds__(64 * WM * WN, 4) void conv_igemm_glds_kernel(const 
         __syncthreads();
         if (!res_early) { if (d.res_up) load_res_up(); else load_res(); }
         // BatchNorm reductions in the epilogue (vpho_conv_desc.stats / bn_x): a thread's items all lie in ONE channel quad (NT % V_PER_ROW == 0),
-        // so its share of the column sums stays in two registers quads until the tile is out
+        // so its share of the column sums stays in two registers quads until the tile is out (forward: sums about the pivot `piv` = the
+        // first item of the lowest lane with the same channel quad -- one pivot for all lanes that are added below, see ShiftSums -- and
+        // `cnt` items; if that item is dead, so are all of the group's items: their rows are higher)
         static_assert(NT % V_PER_ROW == 0 && NT >= 2 * BN, "stats layout");
-        f32x4 st0 = {0.f, 0.f, 0.f, 0.f}, st1 = {0.f, 0.f, 0.f, 0.f};
+        f32x4 st0 = {0.f, 0.f, 0.f, 0.f}, st1 = {0.f, 0.f, 0.f, 0.f}, piv = st0;
+        float cnt = 0.f;
         f32x4 bn_m = st0, bn_i = st0, bn_g = st0, bn_b = st0;
         if (d.bn_x) {
             const int c = n0 + 4 * (tid % V_PER_ROW);
@@ -711,34 +714,55 @@ __global__ __launch_bounds__(64 * WM * WN, 4) void conv_igemm_glds_kernel(const 
                     st0[k] += o[k]; st1[k] += o[k] * xh;
                 }
             } else if (d.stats) {
+                if (it == 0) {
 #pragma unroll
-                for (int k = 0; k < 4; ++k) { st0[k] += o[k]; st1[k] += o[k] * o[k]; }
+                    for (int k = 0; k < 4; ++k) piv[k] = __shfl(o[k], lane & (V_PER_ROW - 1));
+                }
+                cnt += 1.f;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) { const float dv = o[k] - piv[k]; st0[k] += dv; st1[k] += dv * dv; }
             }
             *reinterpret_cast<f32x4*>(d.y + yoff) = o;
         }
         if (d.stats) {
-            // a wave's lanes with the same channel quad (lane bits >= log2 V_PER_ROW) are added on the vector ALU, the waves' sums in a fixed
-            // order through LDS; one partial row per M-tile: [tile_m][2][Cout]
+            // a wave's lanes with the same channel quad (lane bits >= log2 V_PER_ROW) are combined across lanes, the waves' sums in a fixed
+            // order through LDS; one partial row per M-tile: [tile_m][BN_STAT_PLANES][Cout] (store_bn_row), the forward pivot the tile's
+            // first row (the lowest lane of wave 0); backward: sum dy | sum dy * xhat in planes 0, 1
             static_assert(V_PER_ROW == 16 || V_PER_ROW == 32, "lane layout of the epilogue items");
             constexpr int NWAVES = NT / 64;
+            static_assert(4 * NWAVES * BN <= BM * C_LD, "stats staging");
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 if (V_PER_ROW == 16) { st0[k] = sum_lane_bit_4(st0[k]); st1[k] = sum_lane_bit_4(st1[k]); }
                 st0[k] = sum_lane_bit_5(st0[k]); st1[k] = sum_lane_bit_5(st1[k]);
             }
+            if (!d.bn_x) {
+                if (V_PER_ROW == 16) cnt = sum_lane_bit_4(cnt);
+                cnt = sum_lane_bit_5(cnt);
+            }
             __syncthreads();                                        // every thread has read its items of Cs
-            float* R = smem;                                        // [wave][2][BN]
+            float* R = smem;                                        // [wave][4][BN]
             if (lane < V_PER_ROW) {
-                *reinterpret_cast<f32x4*>(R + (wave * 2 + 0) * BN + 4 * lane) = st0;
-                *reinterpret_cast<f32x4*>(R + (wave * 2 + 1) * BN + 4 * lane) = st1;
+                *reinterpret_cast<f32x4*>(R + (wave * 4 + 0) * BN + 4 * lane) = st0;
+                *reinterpret_cast<f32x4*>(R + (wave * 4 + 1) * BN + 4 * lane) = st1;
+                *reinterpret_cast<f32x4*>(R + (wave * 4 + 2) * BN + 4 * lane) = piv;
+                *reinterpret_cast<f32x4*>(R + (wave * 4 + 3) * BN + 4 * lane) = f32x4{cnt, cnt, cnt, cnt};
             }
             __syncthreads();
-            if (tid < 2 * BN) {
-                const int pl = tid / BN, c = tid - pl * BN;
-                float t = R[pl * BN + c];
+            if (d.bn_x) {
+                if (tid < 2 * BN) {
+                    const int pl = tid / BN, c = tid - pl * BN;
+                    float t = R[pl * BN + c];
 #pragma unroll
-                for (int k = 1; k < NWAVES; ++k) t += R[(k * 2 + pl) * BN + c];
-                if (n0 + c < d.Cout) d.stats[((long long)tile_m * 2 + pl) * d.Cout + n0 + c] = t;
+                    for (int k = 1; k < NWAVES; ++k) t += R[(k * 4 + pl) * BN + c];
+                    if (n0 + c < d.Cout) d.stats[((long long)tile_m * BN_STAT_PLANES + pl) * d.Cout + n0 + c] = t;
+                }
+            } else if (tid < BN) {
+                const int c = tid;
+                ShiftSums t{R[2 * BN + c], R[c], R[BN + c], R[3 * BN + c]};
+#pragma unroll
+                for (int k = 1; k < NWAVES; ++k) t = shift_sums_add(t, ShiftSums{R[(k * 4 + 2) * BN + c], R[(k * 4) * BN + c], R[(k * 4 + 1) * BN + c], R[(k * 4 + 3) * BN + c]});
+                if (n0 + c < d.Cout) store_bn_row(d.stats + (long long)tile_m * BN_STAT_PLANES * d.Cout + n0 + c, d.Cout, t);
             }
         }
         VPHO_STAMP_AT(4);
@@ -935,16 +959,22 @@ __device__ __forceinline__ void conv_pers_body(const Geo& g) {
     // the stage-end barrier of that next tile.  (The store is issued behind the counted wait and is older than everything the next one counts.)
     // (STATS is a template parameter, conv_igemm_pers_bn_kernel: as a run-time switch its 16 registers cost the inference kernel 7 spills)
     constexpr bool stats_on = STATS;
-    static_assert(2 * (BN / WN) <= EPI && 2 * BN <= NT, "stats layout");
+    // (a wave's slice: [4][BN / WN] = sum (v - pivot) | sum (v - pivot)^2 | pivot | count, see ShiftSums; the partial row
+    // [tile][BN_STAT_PLANES][Cout] as in conv_igemm_glds_kernel, the pivot the tile's first row)
+    static_assert(4 * (BN / WN) <= EPI && BN <= NT, "stats layout");
     auto flush_stats = [&](int m0_, int n0_) {
-        if (tid < 2 * BN) {
-            const int pl = tid / BN, c = tid - pl * BN;
+        if (tid < BN) {
+            const int c = tid;
             const int wn_c = c / (BN / WN), cc = c - wn_c * (BN / WN);
-            const float* q = smem + 2 * TILE + wn_c * EPI + pl * (BN / WN) + cc;
-            float t = q[0];
+            const float* q = smem + 2 * TILE + wn_c * EPI + cc;
+            constexpr int PL = BN / WN;
+            ShiftSums t{q[2 * PL], q[0], q[PL], q[3 * PL]};
 #pragma unroll
-            for (int w = 1; w < WM; ++w) t += q[w * WN * EPI];
-            if (n0_ + c < d.Cout) d.stats[((long long)(m0_ / BM) * 2 + pl) * d.Cout + n0_ + c] = t;
+            for (int w = 1; w < WM; ++w) {
+                const float* r = q + w * WN * EPI;
+                t = shift_sums_add(t, ShiftSums{r[2 * PL], r[0], r[PL], r[3 * PL]});
+            }
+            if (n0_ + c < d.Cout) store_bn_row(d.stats + (long long)(m0_ / BM) * BN_STAT_PLANES * d.Cout + n0_ + c, d.Cout, t);
         }
     };
     int pm0 = 0, pn0 = 0;                                           // the tile whose sums wait in the slices
@@ -1008,9 +1038,9 @@ __device__ __forceinline__ void conv_pers_body(const Geo& g) {
         }
         // ---- epilogue through the wave's own LDS slice: no workgroup barrier (the LDS operations of one wave execute in order)
         const float* Bq = smem + 2 * TILE + NW * EPI + etp * BN + wn * (BN / WN) + ec;
-        f32x4 st0[TN], st1[TN];
+        f32x4 st0[TN], st1[TN], piv[TN];        // (sums about the pivot = the first item of lane & 7: the wave's lowest row, see ShiftSums)
 #pragma unroll
-        for (int j = 0; j < TN; ++j) { st0[j] = f32x4{0.f, 0.f, 0.f, 0.f}; st1[j] = st0[j]; }
+        for (int j = 0; j < TN; ++j) { st0[j] = f32x4{0.f, 0.f, 0.f, 0.f}; st1[j] = st0[j]; piv[j] = st0[j]; }
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -1029,11 +1059,18 @@ __device__ __forceinline__ void conv_pers_body(const Geo& g) {
                     for (int k = 0; k < 4; ++k) { const float t = v[k] + bq[k] + r[k]; o[k] = t > 0.f ? t : t * d.out_slope; }
                     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((__vector_size__(4 * sizeof(unsigned)))) unsigned, o), yr, yo, 0, 0);
                     if (stats_on) {
+                        if (i == 0 && gq == 0) {                            // (if that row is dead, so are all of the wave's)
 #pragma unroll
-                        for (int k = 0; k < 4; ++k) { const float u = yo != -1 ? o[k] : 0.f; st0[j][k] += u; st1[j][k] += u * u; }     // dead rows / columns: nothing
+                            for (int k = 0; k < 4; ++k) piv[j][k] = __shfl(o[k], lane & 7);
+                        }
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) { const float u = yo != -1 ? o[k] - piv[j][k] : 0.f; st0[j][k] += u; st1[j][k] += u * u; }     // dead rows / columns: nothing
                     }
                 }
         if (stats_on) {
+            // the wave's live rows: its BM / WM consecutive rows below M (a dead column's sums are never written)
+            const float n = (float)max(0, min(BM / WM, g.M - (em0 + wm * (BM / WM))));
+            static_assert(TM * 32 == BM / WM, "a wave's rows are one block");
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
 #pragma unroll
@@ -1041,6 +1078,8 @@ __device__ __forceinline__ void conv_pers_body(const Geo& g) {
                 if (lane < 8) {                                     // behind the last pass's read of the slice (one wave's LDS operations execute in order)
                     *reinterpret_cast<f32x4*>(Cw + j * 32 + ec) = st0[j];
                     *reinterpret_cast<f32x4*>(Cw + (BN / WN) + j * 32 + ec) = st1[j];
+                    *reinterpret_cast<f32x4*>(Cw + 2 * (BN / WN) + j * 32 + ec) = piv[j];
+                    *reinterpret_cast<f32x4*>(Cw + 3 * (BN / WN) + j * 32 + ec) = f32x4{n, n, n, n};
                 }
             }
             pm0 = em0; pn0 = en0;
@@ -1366,14 +1405,14 @@ extern "C" int vpho_conv2d_nhwc_f32(const vpho_conv_desc* dp, void* stream) {
         VPHO_REQUIRE(4.0 * d.N * d.ru_H * d.ru_W * (double)d.ru_ld < 3.9e9, "vpho_conv2d_nhwc_f32: res_up map too large");
     }
     hipStream_t s = (hipStream_t)stream;
-    // BatchNorm reductions in the epilogue (ABI 12): the direct-to-LDS kernels' 16-byte epilogue, one partial row per M-tile
+    // BatchNorm reductions in the epilogue (ABI 13): the direct-to-LDS kernels' 16-byte epilogue, one partial row per M-tile
     if (d.stats_rows) *d.stats_rows = 0;
     const bool stats_shape = g.vec_epilogue && splits == 1 && groups == 1 && !d.row_map && !d.w_planes && (d.in_scale == nullptr);
     if (d.bn_x) {
         VPHO_REQUIRE(d.stats && d.stats_rows && d.bn_mean && d.bn_invstd && (d.gate || (d.bn_gamma && d.bn_beta)),
                      "vpho_conv2d_nhwc_f32: bn_x needs stats, stats_rows, mean / invstd and -- without a stored gate -- gamma / beta");
-        VPHO_REQUIRE(stats_shape && al16(d.bn_x) && al16(d.bn_mean) && al16(d.bn_invstd) && (d.gate || (al16(d.bn_gamma) && al16(d.bn_beta))),
-                     "vpho_conv2d_nhwc_f32: bn_x is served by the direct-to-LDS 16-byte epilogue only (Cout %% 4 == 0, aligned, no splits / groups / pixel list / prologue / planes)");
+        VPHO_REQUIRE((stats_shape || d.gate) && al16(d.bn_x) && al16(d.bn_mean) && al16(d.bn_invstd) && (!d.bn_gamma || (al16(d.bn_gamma) && al16(d.bn_beta))),
+                     "vpho_conv2d_nhwc_f32: bn_x without a stored gate is served by the direct-to-LDS 16-byte epilogue only (Cout %% 4 == 0, aligned, no splits / groups / pixel list / prologue / planes)");
     }
     VPHO_REQUIRE(!d.stats || (d.stats_rows && d.stats_cap > 0 && al16(d.stats)), "vpho_conv2d_nhwc_f32: stats needs stats_rows (host) and stats_cap");
     const long long big_tiles = ((M + 127) / 128) * ((d.Cout + 127) / 128) * ny;
@@ -1396,8 +1435,15 @@ extern "C" int vpho_conv2d_nhwc_f32(const vpho_conv_desc* dp, void* stream) {
         g.ntiles = g.tiles_m * g.tiles_n;
         if (d.stats) {
             const bool on = stats_kernel && stats_shape && g.tiles_m <= d.stats_cap;
-            if (on) *d.stats_rows = g.tiles_m;
-            else { g.d.stats = nullptr; if (d.bn_x) { stats_failed = true; return; } }     // never drop the gate silently
+            if (on) {
+                *d.stats_rows = g.tiles_m;
+                if (d.bn_x && d.bn_gamma) g.d.gate = nullptr;       // the gate recomputed from bn_x; the stored one was the fall-back
+            } else {
+                // no BatchNorm epilogue: the stored gate as is, no partial rows (the caller runs the stand-alone reduction); without a
+                // stored gate to fall back to the call fails -- never drop the gate silently
+                g.d.stats = nullptr;
+                if (d.bn_x) { if (!d.gate) { stats_failed = true; return; } g.d.bn_x = nullptr; }
+            }
         }
         hipLaunchKernelGGL(kernel, dim3((g.ntiles + 7) / 8 * 8, ny), dim3(threads), 0, s, g);
     };

@@ -55,7 +55,7 @@ struct WinoArgs {
     int scatter;                               // with wins: 1 = y is the ordinary (N,H,W,y_ld) map, window pixels written in place, the rest untouched
     // grouped launch (blockIdx.y = group: the twin hand / object branches): the same problem on x + g*x_gs, u + g*u_gs, bias + g*b_gs, y + g*y_gs
     long long x_gs, u_gs, b_gs, y_gs;
-    // conv_winograd_bn_kernel only (ABI 12): BatchNorm reductions in the epilogue, see vpho_conv_desc.stats / bn_x
+    // conv_winograd_bn_kernel only (ABI 13): BatchNorm reductions in the epilogue, see vpho_conv_desc.stats / bn_x
     float* stats; const float* bn_x; const float* bn_mean; const float* bn_invstd; const float* bn_gamma; const float* bn_beta;
 };
 __device__ __forceinline__ WinoArgs wino_group(WinoArgs a, const unsigned g) {
@@ -417,6 +417,7 @@ __device__ __forceinline__ void wino_body(const WinoArgs& a_) {
     fetch_records(0);
     // BN: a lane owns one output channel and 16 tiles x 4 pixels of it -- its share of the column sums is two registers
     float st0 = 0.f, st1 = 0.f, bn_m = 0.f, bn_i = 0.f, bn_g = 0.f, bn_b = 0.f;
+    float piv = 0.f, cnt = 0.f;                                      // BN == 1: the sums are about the lane's first item (ShiftSums)
     constexpr int BNX_FLOATS = W_TB * 4 * W_CB;                      // the block's BatchNorm-input tile: 64 tiles x 4 pixels x 64 channels = 64 KB
     if constexpr (BN == 2) {
         bn_m = a.bn_mean[co]; bn_i = a.bn_invstd[co]; bn_g = a.bn_gamma[co]; bn_b = a.bn_beta[co];
@@ -475,7 +476,10 @@ __device__ __forceinline__ void wino_body(const WinoArgs& a_) {
                 }
                 if constexpr (BN == 1) {
                     v = v > 0.f ? v : v * a.out_slope;
-                    st0 += v; st1 += v * v;
+                    if (cnt == 0.f) piv = v;
+                    cnt += 1.f;
+                    const float dv = v - piv;
+                    st0 += dv; st1 += dv * dv;
                     yp[offs[p]] = v;
                     continue;
                 }
@@ -485,14 +489,31 @@ __device__ __forceinline__ void wino_body(const WinoArgs& a_) {
     }
     if constexpr (BN != 0) {
         // lanes li / li + 32 hold the two row halves of a channel, the waves wt = 0 / 1 the two tile halves: one partial row per tile
-        // block, [tb][2][Cout], combined in a fixed order (the stage buffers are free: every wave has passed the last stage's barrier)
-        st0 += __shfl_xor(st0, 32); st1 += __shfl_xor(st1, 32);
+        // block, [tb][BN_STAT_PLANES][Cout] (vpho_conv_desc.stats: forward store_bn_row; backward sum dy | sum dy * xhat), combined in a
+        // fixed order (the stage buffers are free: every wave has passed the last stage's barrier)
+        static_assert(BNX_FLOATS + 8 * W_CB <= 2 * W_STAGE, "stats staging");
         float* S = smem + BNX_FLOATS;                                // (behind the BatchNorm-input tile other waves may still be reading)
-        if (lh == 0) { S[(wt * 2 + 0) * W_CB + wc * 32 + li] = st0; S[(wt * 2 + 1) * W_CB + wc * 32 + li] = st1; }
-        __syncthreads();
-        if (tid < 2 * W_CB) {
-            const int pl = tid / W_CB, c = tid - pl * W_CB;
-            a.stats[((long long)tb * 2 + pl) * a.Cout + c0 + c] = S[pl * W_CB + c] + S[(2 + pl) * W_CB + c];
+        if constexpr (BN == 2) {
+            st0 += __shfl_xor(st0, 32); st1 += __shfl_xor(st1, 32);
+            if (lh == 0) { S[(wt * 2 + 0) * W_CB + wc * 32 + li] = st0; S[(wt * 2 + 1) * W_CB + wc * 32 + li] = st1; }
+            __syncthreads();
+            if (tid < 2 * W_CB) {
+                const int pl = tid / W_CB, c = tid - pl * W_CB;
+                a.stats[((long long)tb * BN_STAT_PLANES + pl) * a.Cout + c0 + c] = S[pl * W_CB + c] + S[(2 + pl) * W_CB + c];
+            }
+        } else {
+            const ShiftSums t = shift_sums_xor(ShiftSums{piv, st0, st1, cnt}, 32);
+            if (lh == 0) {
+                float* q = S + wt * 4 * W_CB + wc * 32 + li;
+                q[0] = t.p; q[W_CB] = t.s; q[2 * W_CB] = t.q; q[3 * W_CB] = t.n;
+            }
+            __syncthreads();
+            if (tid < W_CB) {
+                const float* q = S + tid;
+                const ShiftSums u = shift_sums_add(ShiftSums{q[0], q[W_CB], q[2 * W_CB], q[3 * W_CB]},
+                                                   ShiftSums{q[4 * W_CB], q[5 * W_CB], q[6 * W_CB], q[7 * W_CB]});
+                store_bn_row(a.stats + (long long)tb * BN_STAT_PLANES * a.Cout + c0 + tid, a.Cout, u);
+            }
         }
     }
     VPHO_STAMP_AT(4);

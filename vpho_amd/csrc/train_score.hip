@@ -298,21 +298,41 @@ __global__ __launch_bounds__(256) void col_reduce_kernel(const BnRedArgs a) {
         }
     }
 }
-// sum over the row chunks of one or two partial-sum planes (double: the chunks of col_reduce_kernel; float: the per-tile partial sums a
-// convolution's epilogue wrote, vpho_conv_desc.stats): block = 32 channels x 32 chunk groups (chunks g, g+32, ... per thread, the 32
-// group sums combined in a fixed order); the result is valid in the threads with g == 0.  (Round 6: 8 groups -> 32: a finishing kernel is
-// one short chain of dependent loads per thread, and a training step runs ~370 of them back to back with their consumers.)
+// The forward partial rows of a convolution's epilogue (vpho_conv_desc.stats, ABI 13): per M-tile and channel, in planes 2 .. 5, the
+// pivot p (the tile's first value), sum (v - p), sum (v - p)^2 and the count n (planes 0, 1: the plain sums, not read here).  They are merged in fp64 about ONE pivot per channel, the mean of tile 0:
+// S = sum n_t d_t, Q = sum (M2_t + n_t d_t^2), d_t = mean_t - pivot, M2_t = sum (v - p)^2 - (sum (v - p))^2 / n_t; then mean = pivot + S / rows
+// and var = (Q - S^2 / rows) / rows.  Every difference is one of values near the channel's mean: nothing cancels when |mean| >> std
+// (E[v^2] - mean^2 of fp32 tile sums lost up to 5e-2 of invstd at mean / std = 1000).
+template <typename T>
+__device__ inline double tile_pivot(const T* __restrict__ tiles, int C, int c) { return (double)tiles[2 * C + c] + (double)tiles[3 * C + c] / (double)tiles[5 * C + c]; }
+template <typename T>
+__device__ inline void tile_add(const T* __restrict__ tiles, long long t, int C, int c, double piv, double& S, double& Q) {
+    const T* r = tiles + t * BN_STAT_PLANES * C + c;
+    const double p = r[2 * C], s = r[3 * C], q = r[4 * C], n = r[5 * C];
+    const double d = p + s / n - piv;
+    S += n * d; Q += (q - s * s / n) + n * d * d;
+}
+// sum over the row chunks of one or two partial-sum planes (double: the chunks of col_reduce_kernel / bn_merge_tiles_kernel; float: the
+// per-tile partial rows a convolution's epilogue wrote, STRIDE = BN_STAT_PLANES planes a row -- TILES: the forward rows, merged about the pivot of
+// tile_pivot): block = 32 channels x 32 chunk groups (chunks g, g+32, ... per thread, the 32 group sums combined in a fixed order); the
+// result is valid in the threads with g == 0.  (Round 6: 8 groups -> 32: a finishing kernel is one short chain of dependent loads per
+// thread, and a training step runs ~370 of them back to back with their consumers.)
 constexpr int FIN_G = 32;
-template <int PLANES, typename T>
-__device__ inline bool finish_sums(const T* __restrict__ part, int chunks, int C, int& c, double& s0, double& s1) {
+template <int PLANES, typename T, int STRIDE = PLANES, bool TILES = false>
+__device__ inline bool finish_sums(const T* __restrict__ part, int chunks, int C, int& c, double& s0, double& s1, const float* tiles = nullptr,
+                                   double* piv = nullptr) {
     __shared__ double q0[FIN_G][32], q1[FIN_G][32];
     const int cl = threadIdx.x & 31, g = threadIdx.x >> 5;
     c = blockIdx.x * 32 + cl;
-    double a0 = 0.0, a1 = 0.0;
+    double a0 = 0.0, a1 = 0.0, pv = 0.0;
     if (c < C) {
+        if (tiles) pv = tile_pivot(tiles, C, c);
         for (int k = g; k < chunks; k += FIN_G) {
-            a0 += (double)part[((long long)k * PLANES) * C + c];
-            if (PLANES == 2) a1 += (double)part[((long long)k * PLANES + 1) * C + c];
+            if constexpr (TILES) tile_add(part, k, C, c, pv, a0, a1);
+            else {
+                a0 += (double)part[((long long)k * STRIDE) * C + c];
+                if (PLANES == 2) a1 += (double)part[((long long)k * STRIDE + 1) * C + c];
+            }
         }
     }
     q0[g][cl] = a0; q1[g][cl] = a1;
@@ -320,7 +340,20 @@ __device__ inline bool finish_sums(const T* __restrict__ part, int chunks, int C
     if (g != 0 || c >= C) return false;
     s0 = q0[0][cl]; s1 = q1[0][cl];
     for (int k = 1; k < FIN_G; ++k) { s0 += q0[k][cl]; s1 += q1[k][cl]; }
+    if (piv) *piv = pv;
     return true;
+}
+// more than 256 forward partial rows: chunks of them merged about the pivot first -> [chunks][2][C] doubles (S, Q), one thread per
+// channel walking its chunk in order
+__global__ __launch_bounds__(64) void bn_merge_tiles_kernel(const float* __restrict__ tiles, int P, int C, int per_chunk, double* __restrict__ out) {
+    const int c = blockIdx.x * 64 + threadIdx.x, k = blockIdx.y;
+    if (c >= C) return;
+    const double piv = tile_pivot(tiles, C, c);
+    double S = 0.0, Q = 0.0;
+    const int t1 = min(P, (k + 1) * per_chunk);
+    for (int t = k * per_chunk; t < t1; ++t) tile_add(tiles, t, C, c, piv, S, Q);
+    out[((long long)k * 2) * C + c] = S;
+    out[((long long)k * 2 + 1) * C + c] = Q;
 }
 __global__ __launch_bounds__(32 * FIN_G) void colsum_finish_kernel(const double* __restrict__ part, int chunks, int C, float* __restrict__ out) {
     int c; double s, unused;
@@ -348,15 +381,18 @@ int launch_col_reduce(BnRedArgs a, hipStream_t s) {
     else hipLaunchKernelGGL(col_reduce_kernel<1>, grid, dim3(256), 0, s, a);
     return chunks;
 }
-// statistics: mean, biased variance -> invstd = 1/sqrt(var + eps); running stats with the unbiased variance (torch semantics)
-template <typename T>
-__global__ __launch_bounds__(32 * FIN_G) void bn_finish_stats_kernel(const T* __restrict__ part, int chunks, int C, long long rows, float eps, float momentum,
-                                                              float* __restrict__ mean, float* __restrict__ invstd, float* __restrict__ running_mean,
-                                                              float* __restrict__ running_var) {
-    int c; double s, ss;
-    if (!finish_sums<2>(part, chunks, C, c, s, ss)) return;
-    const double m = s / (double)rows;
-    double var = ss / (double)rows - m * m;
+// statistics: mean, biased variance -> invstd = 1/sqrt(var + eps); running stats with the unbiased variance (torch semantics).
+// MODE 0: part = [chunks][2][C] doubles sum v | sum v^2 (col_reduce_kernel, fp64 from the first element); MODE 1: part = the forward
+// partial rows themselves, [chunks][BN_STAT_PLANES][C] floats; MODE 2: part = [chunks][2][C] doubles S | Q of bn_merge_tiles_kernel over `tiles`
+template <int MODE, typename T>
+__global__ __launch_bounds__(32 * FIN_G) void bn_finish_stats_kernel(const T* __restrict__ part, int chunks, const float* __restrict__ tiles, int C,
+                                                              long long rows, float eps, float momentum, float* __restrict__ mean,
+                                                              float* __restrict__ invstd, float* __restrict__ running_mean, float* __restrict__ running_var) {
+    int c; double s, ss, piv = 0.0;
+    if (!finish_sums<2, T, MODE == 1 ? BN_STAT_PLANES : 2, MODE == 1>(part, chunks, C, c, s, ss, MODE ? tiles : nullptr, &piv)) return;
+    const double n = (double)rows;
+    const double m = MODE ? piv + s / n : s / n;
+    double var = MODE ? (ss - s * s / n) / n : ss / n - m * m;
     if (var < 0.0) var = 0.0;
     mean[c] = (float)m;
     invstd[c] = (float)(1.0 / sqrt(var + (double)eps));
@@ -366,10 +402,11 @@ __global__ __launch_bounds__(32 * FIN_G) void bn_finish_stats_kernel(const T* __
         running_var[c] = (float)((1.0 - momentum) * (double)running_var[c] + momentum * unbiased);
     }
 }
-template <typename T>
+// STRIDE: planes a partial row (BN_STAT_PLANES: a convolution's epilogue rows, sum dy | sum dy * xhat in the first two; 2: fp64 chunks)
+template <typename T, int STRIDE>
 __global__ __launch_bounds__(32 * FIN_G) void bn_finish_grads_kernel(const T* __restrict__ part, int chunks, int C, float* __restrict__ dbeta, float* __restrict__ dgamma) {
     int c; double s, ss;
-    if (finish_sums<2>(part, chunks, C, c, s, ss)) { dbeta[c] = (float)s; dgamma[c] = (float)ss; }
+    if (finish_sums<2, T, STRIDE>(part, chunks, C, c, s, ss)) { dbeta[c] = (float)s; dgamma[c] = (float)ss; }
 }
 // y = lrelu((x - mean) * invstd * gamma + beta, slope); a thread handles V consecutive channels of a row
 template <int V>
@@ -937,24 +974,35 @@ extern "C" int vpho_im2col_t_f32(const float* x, int N, int H, int W, int Cin, i
 
 extern "C" long long vpho_bn_workspace_bytes(int C) { return C > 0 ? (long long)256 * 2 * C * 8 : -1; }
 
-// the statistics of a [rows][C] matrix from partial sums: double chunks of col_reduce_kernel, or the float partial rows of a convolution's
-// epilogue -- finished directly when there are few, through one column reduction of the partial matrix itself (1/64 ... 1/256 of the data) first
-static const void* reduce_partials(const float* stats, int P, int C, void* workspace, hipStream_t s, int* chunks, bool* is_double) {
+// the statistics of a [rows][C] matrix from the partial rows of a convolution's epilogue ([P][BN_STAT_PLANES][C] floats, vpho_conv_desc.stats) --
+// finished directly when there are few, through one pass over the partial matrix itself (1/64 ... 1/256 of the data) first: the forward
+// rows merged in chunks about the pivot (bn_merge_tiles_kernel), the backward sums column-reduced (col_reduce_kernel)
+static const void* reduce_partials(const float* stats, int P, int C, bool forward, void* workspace, hipStream_t s, int* chunks, bool* is_double) {
     if (P <= 256) { *chunks = P; *is_double = false; return stats; }
-    BnRedArgs ra{stats, nullptr, nullptr, nullptr, P, 2 * C, 2 * C, 2, 0, (double*)workspace};      // [P][2C] -> [chunks][2C] doubles = [chunks][2][C]
-    *chunks = launch_col_reduce(ra, s);
     *is_double = true;
+    if (forward) {
+        const int per = (P + 255) / 256;
+        *chunks = (P + per - 1) / per;
+        hipLaunchKernelGGL(bn_merge_tiles_kernel, dim3((C + 63) / 64, *chunks), dim3(64), 0, s, stats, P, C, per, (double*)workspace);
+        return workspace;
+    }
+    BnRedArgs ra{stats, nullptr, nullptr, nullptr, P, 2 * C, BN_STAT_PLANES * C, 2, 0, (double*)workspace};     // planes 0, 1 -> [chunks][2][C] doubles
+    *chunks = launch_col_reduce(ra, s);
     return workspace;
 }
-static int bn_forward_tail(const float* x, long long rows, int C, int ld, const void* part, int chunks, bool part_double, const float* gamma, const float* beta,
+// tiles: the convolution's forward partial rows the statistics come from (null: part = col_reduce_kernel's fp64 sums)
+static int bn_forward_tail(const float* x, long long rows, int C, int ld, const void* part, int chunks, bool part_double, const float* tiles, const float* gamma, const float* beta,
                            float eps, float momentum, float slope, float* running_mean, float* running_var, float* save_mean, float* save_invstd,
                            const float* res, float* y, hipStream_t s) {
-    if (part_double)
-        hipLaunchKernelGGL(bn_finish_stats_kernel<double>, dim3(nblk(C, 32)), dim3(32 * FIN_G), 0, s, (const double*)part, chunks, C, rows, eps, momentum, save_mean, save_invstd,
-                           running_mean, running_var);
+    if (!tiles)
+        hipLaunchKernelGGL((bn_finish_stats_kernel<0, double>), dim3(nblk(C, 32)), dim3(32 * FIN_G), 0, s, (const double*)part, chunks, tiles, C, rows, eps, momentum,
+                           save_mean, save_invstd, running_mean, running_var);
+    else if (part_double)
+        hipLaunchKernelGGL((bn_finish_stats_kernel<2, double>), dim3(nblk(C, 32)), dim3(32 * FIN_G), 0, s, (const double*)part, chunks, tiles, C, rows, eps, momentum,
+                           save_mean, save_invstd, running_mean, running_var);
     else
-        hipLaunchKernelGGL(bn_finish_stats_kernel<float>, dim3(nblk(C, 32)), dim3(32 * FIN_G), 0, s, (const float*)part, chunks, C, rows, eps, momentum, save_mean, save_invstd,
-                           running_mean, running_var);
+        hipLaunchKernelGGL((bn_finish_stats_kernel<1, float>), dim3(nblk(C, 32)), dim3(32 * FIN_G), 0, s, (const float*)part, chunks, tiles, C, rows, eps, momentum,
+                           save_mean, save_invstd, running_mean, running_var);
     if (C % 4 == 0 && ld % 4 == 0 && aligned16(x) && aligned16(y) && aligned16(gamma) && aligned16(beta) && aligned16(save_mean) && aligned16(save_invstd) &&
         (!res || aligned16(res)))
         hipLaunchKernelGGL(bn_apply_kernel<4>, dim3(nblk(rows * (C / 4))), dim3(256), 0, s, x, (const float*)save_mean, (const float*)save_invstd, gamma, beta, res, rows, C, ld, slope, y);
@@ -965,8 +1013,8 @@ static int bn_forward_tail(const float* x, long long rows, int C, int ld, const 
 static int bn_backward_tail(const float* x, const float* dy, long long rows, int C, int ld, const void* part, int chunks, bool part_double, const float* gamma,
                             const float* save_mean, const float* save_invstd, float* dx, float* dgamma, float* dbeta, hipStream_t s,
                             const float* res = nullptr, float* dx_colsum = nullptr, void* workspace = nullptr) {
-    if (part_double) hipLaunchKernelGGL(bn_finish_grads_kernel<double>, dim3(nblk(C, 32)), dim3(32 * FIN_G), 0, s, (const double*)part, chunks, C, dbeta, dgamma);
-    else hipLaunchKernelGGL(bn_finish_grads_kernel<float>, dim3(nblk(C, 32)), dim3(32 * FIN_G), 0, s, (const float*)part, chunks, C, dbeta, dgamma);
+    if (part_double) hipLaunchKernelGGL((bn_finish_grads_kernel<double, 2>), dim3(nblk(C, 32)), dim3(32 * FIN_G), 0, s, (const double*)part, chunks, C, dbeta, dgamma);
+    else hipLaunchKernelGGL((bn_finish_grads_kernel<float, BN_STAT_PLANES>), dim3(nblk(C, 32)), dim3(32 * FIN_G), 0, s, (const float*)part, chunks, C, dbeta, dgamma);
     if (res || dx_colsum) {
         // (the finishing kernel above has consumed the partial sums: the workspace is free for the column sums of dx)
         const bool vec = C % 4 == 0 && ld % 4 == 0 && aligned16(x) && aligned16(dy) && aligned16(dx) && aligned16(gamma) && aligned16(save_mean) && aligned16(save_invstd) &&
@@ -995,7 +1043,7 @@ extern "C" int vpho_bn_train_forward_f32(const float* x, long long rows, int C, 
     hipStream_t s = (hipStream_t)stream;
     BnRedArgs ra{x, nullptr, nullptr, nullptr, rows, C, ld, 0, 0, (double*)workspace};
     const int chunks = launch_col_reduce(ra, s);
-    return bn_forward_tail(x, rows, C, ld, workspace, chunks, true, gamma, beta, eps, momentum, slope, running_mean, running_var, save_mean, save_invstd, res, y, s);
+    return bn_forward_tail(x, rows, C, ld, workspace, chunks, true, nullptr, gamma, beta, eps, momentum, slope, running_mean, running_var, save_mean, save_invstd, res, y, s);
 }
 
 extern "C" int vpho_bn_train_forward_stats_f32(const float* x, long long rows, int C, int ld, const float* stats, int stats_rows, const float* gamma,
@@ -1006,8 +1054,8 @@ extern "C" int vpho_bn_train_forward_stats_f32(const float* x, long long rows, i
     VPHO_REQUIRE((running_mean == nullptr) == (running_var == nullptr), "vpho_bn_train_forward_stats_f32: running_mean/var must come together");
     hipStream_t s = (hipStream_t)stream;
     int chunks; bool dbl;
-    const void* part = reduce_partials(stats, stats_rows, C, workspace, s, &chunks, &dbl);
-    return bn_forward_tail(x, rows, C, ld, part, chunks, dbl, gamma, beta, eps, momentum, slope, running_mean, running_var, save_mean, save_invstd, res, y, s);
+    const void* part = reduce_partials(stats, stats_rows, C, true, workspace, s, &chunks, &dbl);
+    return bn_forward_tail(x, rows, C, ld, part, chunks, dbl, stats, gamma, beta, eps, momentum, slope, running_mean, running_var, save_mean, save_invstd, res, y, s);
 }
 
 extern "C" int vpho_bn_train_backward_f32(const float* x, const float* dy, long long rows, int C, int ld, const float* gamma, const float* save_mean,
@@ -1027,7 +1075,7 @@ extern "C" int vpho_bn_train_backward_stats_f32(const float* x, const float* dy,
     hipStream_t s = (hipStream_t)stream;
     int chunks; bool dbl;
     const void* part;
-    if (stats) part = reduce_partials(stats, stats_rows, C, workspace, s, &chunks, &dbl);
+    if (stats) part = reduce_partials(stats, stats_rows, C, false, workspace, s, &chunks, &dbl);
     else {
         BnRedArgs ra{x, dy, save_mean, save_invstd, rows, C, ld, 1, 0, (double*)workspace};
         chunks = launch_col_reduce(ra, s); dbl = true; part = workspace;

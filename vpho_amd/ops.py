@@ -17,7 +17,7 @@ if not os.path.exists(LIB_PATH):
 lib = C.CDLL(LIB_PATH)
 lib.vpho_last_error.restype = C.c_char_p
 lib.vpho_abi_version.restype = C.c_int
-ABI_VERSION = 12                        # include/vpho_hip.h; a stale library must not be found out by a missing symbol halfway through a run
+ABI_VERSION = 13                        # include/vpho_hip.h; a stale library must not be found out by a missing symbol halfway through a run
 if lib.vpho_abi_version() != ABI_VERSION:
     raise ImportError(f'{LIB_PATH} implements ABI version {lib.vpho_abi_version()}, this binding expects {ABI_VERSION}: rebuild the '
                       f'extension (python -m vpho_amd.build --force)')
@@ -82,6 +82,9 @@ def _addr(t):
 
 
 FUSE_BN = os.environ.get('VPHO_TRAIN_FUSE_BN', '1') != '0'     # A/B aid: 0 = every train-mode BatchNorm runs its own reduction pass
+
+
+BN_STAT_PLANES = 6                      # planes of a partial row (include/vpho_hip.h, vpho_conv_desc.stats)
 
 
 class BnFuse:
@@ -248,18 +251,17 @@ def conv2d_nhwc(x, w, bias=None, *, kh=1, kw=1, stride=1, pad=0, pad_y=None, pad
     if bn is not None and FUSE_BN and G == 1 and split is None and rows is None and in_scale is None and (out_view is None or bn.parts > 1) and not d.w_planes and cout % 4 == 0:
         cap = (N * OH * OW + 63) // 64                          # the smallest M-tile is 64 rows
         if bn.stats is None:
-            bn.stats = torch.empty((cap * bn.parts, 2, cout), device=x.device, dtype=torch.float32)
+            bn.stats = torch.empty((cap * bn.parts, BN_STAT_PLANES, cout), device=x.device, dtype=torch.float32)
         base = bn.rows                                          # parts > 1: this launch appends behind the rows of the earlier parts
         assert base + cap <= bn.stats.shape[0] and bn.stats.shape[2] == cout
         rows_out = C.c_int(0)
-        d.stats, d.stats_cap, d.stats_rows = bn.stats.data_ptr() + base * 2 * cout * 4, cap, C.cast(C.pointer(rows_out), C.c_void_p)
+        d.stats, d.stats_cap, d.stats_rows = bn.stats.data_ptr() + base * BN_STAT_PLANES * cout * 4, cap, C.cast(C.pointer(rows_out), C.c_void_p)
         if bn.x is not None:
             assert gate is not None and bn.x.shape == ret.shape and bn.x.is_contiguous() and ret.is_contiguous()
             bx = _ptr(bn.x, torch.float32).value + (4 * out_view[4] if out_view is not None else 0)      # laid out like y, like the gate
             if bn.stored_gate:
                 d.bn_x, d.bn_mean, d.bn_invstd = bx, _ptr(bn.mean, torch.float32).value, _ptr(bn.invstd, torch.float32).value
-            else:
-                d.gate, d.gate_slope = None, gate[1]
+            else:                                               # gate recomputed; the stored gate stays as the kernel's fall-back
                 d.bn_x = bx
                 d.bn_mean, d.bn_invstd, d.bn_gamma, d.bn_beta = (_ptr(t, torch.float32).value for t in (bn.mean, bn.invstd, bn.gamma, bn.beta))
     elif bn is not None:
@@ -400,7 +402,7 @@ def _winograd_bn(x, u, bias, out_slope, cin, cout, bn, gate_slope=1.0):
     N, H, W, x_ld = x.shape
     out = torch.empty((N, H, W, cout), device=x.device, dtype=torch.float32)
     cap = (N * H * W + 255) // 256
-    bn.stats = torch.empty((cap, 2, cout), device=x.device, dtype=torch.float32)
+    bn.stats = torch.empty((cap, BN_STAT_PLANES, cout), device=x.device, dtype=torch.float32)
     rows_out = C.c_int(0)
     bx = (bn.x, bn.mean, bn.invstd, bn.gamma, bn.beta) if bn.x is not None else (None,) * 5
     if bn.x is not None:
