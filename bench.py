@@ -7,8 +7,10 @@
 
 One "step" = one forward pass over one per-rank batch (inputs resident in HBM), incl. the CPU prior draw the reference
 makes (sde.py:26-28); after the K timed steps the ranks exchange their per-image metric rows with ONE all-gather.
-Prints one JSON line (rank 0) with `roofline` (dominant kernel: conv_igemm 128x128 tile, timed with HIP events on its
-launch stream during the timed steps) and `cpu_baseline` (the oracle on the host cores, bounded sample, N=1 only).
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints one JSON line (rank 0) with the headline.
+--full adds everything else the benchmark measures, each after the timed steps: the per-step spread, `roofline` and `hbm` (per-kernel
+HIP events in an instrumented repeat of the steps), the split-bf16 and full-map variants, and `cpu_baseline` with `parity` (the
+oracle on the host cores, bounded sample, N=1 only); that takes minutes.
 """
 import argparse
 import json
@@ -49,10 +51,13 @@ def parse():
     p.add_argument('--topk_hand', type=int, default=30)
     p.add_argument('--topk_obj', type=int, default=10)
     p.add_argument('--sample_T0', type=float, default=0.65)
-    p.add_argument('--no_cpu_baseline', action='store_true')
-    p.add_argument('--no_kernel_timing', action='store_true')
-    p.add_argument('--no_fp64_judge', action='store_true', help='skip the end-to-end float64 judge of the parity leg (~75 s of CPU on 16 cores)')
-    p.add_argument('--no_opt_in', action='store_true', help='skip the secondary measurement of the opt-in split-bf16 product path (N=1 only)')
+    p.add_argument('--full', action='store_true',
+                   help='after the timed steps, also measure the per-step spread, the per-kernel roofline and HBM figures, the opt-in split-bf16 and '
+                        'full-map variants and the CPU oracle baseline with its parity checks (minutes); a plain run reports the headline only')
+    p.add_argument('--no_cpu_baseline', action='store_true', help='with --full: skip the CPU oracle baseline and its parity checks')
+    p.add_argument('--no_kernel_timing', action='store_true', help='with --full: skip the per-kernel roofline / HBM repeat of the steps')
+    p.add_argument('--no_fp64_judge', action='store_true', help='with --full: skip the end-to-end float64 judge of the parity leg (~75 s of CPU on 16 cores)')
+    p.add_argument('--no_opt_in', action='store_true', help='with --full: skip the secondary measurement of the opt-in split-bf16 product path (N=1 only)')
     p.add_argument('--cpu_images', type=int, default=64, help='images of the oracle / parity leg (one batch)')
     p.add_argument('--weights', choices=('conditioned', 'random'), default='conditioned', help='synthetic weight set (vpho_amd.synth)')
     p.add_argument('--pipeline', type=int, default=3, help='evaluation batches kept in flight (1 = sequential loop)')
@@ -133,9 +138,9 @@ def main():
     os.environ['VPHO_CONV_MFMA'] = conv_mfma
     model._engine = Engine(model)
     eng = model._engine
-    # share of the stride-4 FPN pixels the RoIAligns of a batch can read (= what the two smoothing convolutions compute)
-    roi_frac = []
-    for b in batches:
+    # share of the stride-4 FPN pixels the RoIAligns of a batch can read (= what the two smoothing convolutions compute); --full only
+    roi_frac = [] if args.full else None
+    for b in (batches if args.full else ()):
         fh, fw = b['rgb'].shape[2] // 4, b['rgb'].shape[3] // 4
         wh = ops.roi_windows(b['bbox_hand'].float().contiguous(), b['bbox_hand_rect'].float().contiguous(), lbs, fh, fw, 0.25)
         wo = ops.roi_windows(b['bbox_obj_rect'].float().contiguous(), None, lbs, fh, fw, 0.25)
@@ -208,7 +213,7 @@ def main():
             return {t.id: t.user_time + t.system_time for t in psutil.Process().threads()}
         except Exception:
             return {}
-    thr0 = thread_cpu()
+    thr0 = thread_cpu() if args.full else {}
     cpu0 = sum(os.times()[:2])
     t0 = time.perf_counter()
     all_rows, nfev, last = run_steps(args.steps, keep_last=args.dump_outputs is not None)
@@ -217,7 +222,7 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     host_cpu_s = sum(os.times()[:2]) - cpu0                 # user+system CPU seconds of this process over the timed region
-    thr1 = thread_cpu()
+    thr1 = thread_cpu() if args.full else {}
     import threading
     names = {t.native_id: t.name for t in threading.enumerate()}
     by_thread = sorted(((names.get(i, 'native thread (HIP runtime / OpenMP / RCCL)'), thr1[i] - thr0.get(i, 0.0)) for i in thr1), key=lambda kv: -kv[1])
@@ -226,12 +231,13 @@ def main():
         dumped = dump_outputs({k: (v.double() if v.dtype == torch.float64 else v.float()).cpu().numpy()
                                for k, v in last.items() if torch.is_tensor(v)}, args.dump_outputs)
     last = None
-    if pipe is not None:                                   # per-step latencies: a short sequential run after the timed region
-        step_events.clear()
-        run_steps(min(args.steps, 5), pipelined=False)
-        ev_end = torch.cuda.Event(enable_timing=True)
-        ev_end.record()
-        torch.cuda.synchronize()
+    if pipe is not None:
+        step_events.clear()                                # the pipelined steps record no events
+        if args.full:                                      # per-step latencies: a short sequential run after the timed region
+            run_steps(min(args.steps, 5), pipelined=False)
+            ev_end = torch.cuda.Event(enable_timing=True)
+            ev_end.record()
+            torch.cuda.synchronize()
     ev_all = step_events + [ev_end]
     step_ms_seq = [a.elapsed_time(b) for a, b in zip(ev_all[:-1], ev_all[1:])]
     step_ms = sorted(step_ms_seq)
@@ -242,7 +248,8 @@ def main():
     hbm_classes = ('mano_fk', 'obj_physics', 'hand_fuse', 'roi_align', 'resize_bilinear')
     timed_classes = ('conv_igemm_128x128', 'conv_igemm_128x64', 'conv_igemm_64x64', 'score_head', 'conv_winograd', 'pose_encoder') + hbm_classes
     prof = {c: dict(total_ms=0.0, launches=0, flops=0.0, bytes=0.0) for c in timed_classes}
-    if not args.no_kernel_timing:
+    kernel_timing = args.full and not args.no_kernel_timing
+    if kernel_timing:
         for c in timed_classes:
             ops.prof_enable(c, True)
         graphs_were = eng.use_graphs
@@ -266,7 +273,7 @@ def main():
         pe_excl = ops.prof_collect('pose_encoder')
         eng.use_graphs = graphs_were
     conv, head = prof['conv_igemm_128x128'], prof['score_head']
-    if args.no_kernel_timing:
+    if not kernel_timing:
         head_excl = dict(total_ms=0.0, launches=0, flops=0.0, bytes=0.0)
         pe_excl = dict(total_ms=0.0, launches=0, flops=0.0, bytes=0.0)
     tmax = torch.tensor([dt], device=dev, dtype=torch.float64)
@@ -287,20 +294,11 @@ def main():
     wl_key = workload_key(args.bs, args.sample_num, args.sampling_steps)
     if rank == 0:
         images = world * args.steps * lbs                  # strong: world * lbs = --bs per step
-        host_cpu = {'cpu_seconds_per_step': host_cpu_s / args.steps, 'busy_threads_equivalent': host_cpu_s / dt,
-                    # the eight busiest threads over the timed region, CPU ms per step (psutil; Python threads by name, the rest are the runtime's)
-                    'cpu_ms_per_step_by_thread': [[n_, 1e3 * c_ / args.steps] for n_, c_ in by_thread[:8] if c_ > 0]}
-        conv_tf = conv['flops'] / (conv['total_ms'] * 1e-3) / 1e12 if conv['total_ms'] > 0 else 0.0
-        head_tf = head['flops'] / (head['total_ms'] * 1e-3) / 1e12 if head['total_ms'] > 0 else 0.0
-        head_excl_tf = head_excl['flops'] / (head_excl['total_ms'] * 1e-3) / 1e12 if head_excl['total_ms'] > 0 else 0.0
-        # fp32-equivalent peak of the score head: the fp32 MFMA peak, or the dense bf16 peak over the 6 / 9 products per fp32 product
-        head_peak = FP32_MFMA_PEAK_TFLOPS if score_mfma == 'f32' else BF16_MFMA_PEAK_TFLOPS / int(score_mfma[-1])
-        conv_peak = FP32_MFMA_PEAK_TFLOPS if conv_mfma == 'f32' else BF16_MFMA_PEAK_TFLOPS / int(conv_mfma[-1])
         result = {
             # BASELINE.json's metric string at the default arguments; another --bs / --sample_num / --sampling_steps names itself
             'metric': f'eval images/sec (bs={args.bs}, sample_num={args.sample_num}, steps={args.sampling_steps}); MPJPE delta vs ref',
             'value': images / dt, 'unit': 'images/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
-            'ms_per_step': dt / args.steps * 1e3, 'step_ms_min_median_max': [step_ms[0], step_ms[len(step_ms) // 2], step_ms[-1]], 'higher_is_better': True, 'scaling': args.scaling, 'vs_baseline': None,
+            'ms_per_step': dt / args.steps * 1e3, 'step_ms_min_median_max': [step_ms[0], step_ms[len(step_ms) // 2], step_ms[-1]] if step_ms else None, 'higher_is_better': True, 'scaling': args.scaling, 'vs_baseline': None,
             'dtype': 'f32' if (score_mfma, conv_mfma) == ('f32', 'f32') else f'f32 storage and accumulation; products as split-bf16 (score head {score_mfma}, convolutions {conv_mfma}; opt-in, NOT the default)',
             'data': 'synthetic',
             'config': {'workload': 'vpho_net.forward(mode=predict), ' + ('README eval config (BASELINE.json configs[1])' if
@@ -318,81 +316,93 @@ def main():
                        'weights': ('vpho_amd.synth.bench_state_dict(seed=1): seeded, heat-map contrast 0.7, conditioned score networks' if args.weights == 'conditioned' else 'vpho_amd.synth.synth_state_dict(seed=1): round-1 random set') + '; synthetic MANO/YCB tables', 'parallelism': f'dp{world}',
                        'nfev_hand_obj_per_step': nfev[-1],
                        'prior_draw': 'device generator (Philox), opt-in: NOT the reference RNG stream' if eng.device_prior else 'CPU generator inside the timed step (sde.py:26-28)'},
-            'roofline': {'bound': 'mfma', 'kernel': CONV_CLASS_NAME if conv_mfma == 'f32'
-                         else f'conv_igemm_split_kernel<128,128,4,2,{conv_mfma[-1]}> (split-bf16 products, opt-in)', 'achieved': conv_tf,
-                         'peak': conv_peak, 'unit': 'TFLOP/s', 'frac': conv_tf / conv_peak,
-                         # launch-weighted over BOTH kernels of the class (one-tile and persistent multi-tile), and only from a counter
-                         # pass taken at this batch size / sample count
-                         'traffic': pmc_traffic(CONV_CLASS_KERNELS, workload=wl_key),
-                         'traffic_source': (pmc_traffic(CONV_CLASS_KERNELS, per_kernel=True, workload=wl_key) or {}).get('source'),
-                         'timing': 'HIP events around every launch, in a separate instrumented repeat of the K steps',
-                         'algorithmic_bytes_per_launch': conv['bytes'] / max(conv['launches'], 1),
-                         'pose_encoder': ({'TFLOP/s': prof['pose_encoder']['flops'] / (prof['pose_encoder']['total_ms'] * 1e-3) / 1e12, 'frac': prof['pose_encoder']['flops'] / (prof['pose_encoder']['total_ms'] * 1e-3) / 1e12 / FP32_MFMA_PEAK_TFLOPS,
-                                           'avg_launch_us': prof['pose_encoder']['total_ms'] * 1e3 / max(prof['pose_encoder']['launches'], 1), 'launches_per_step': prof['pose_encoder']['launches'] / max(args.steps, 1),
-                                           'note': 'durations span the other solve\'s kernels, like score_head',
-                                           'samplers_serialised': ({'TFLOP/s': pe_excl['flops'] / (pe_excl['total_ms'] * 1e-3) / 1e12, 'frac': pe_excl['flops'] / (pe_excl['total_ms'] * 1e-3) / 1e12 / FP32_MFMA_PEAK_TFLOPS,
-                                                                    'avg_launch_us': pe_excl['total_ms'] * 1e3 / max(pe_excl['launches'], 1),
-                                                                    'what': 'same kernels, object solve after the hand solve: exclusive durations (flops as executed: the object state padded to 32 inputs)'}
-                                                                   if pe_excl['total_ms'] > 0 else None)} if prof.get('pose_encoder', {}).get('total_ms', 0) > 0 else None),
-                         'other_kernels': {k: {'TFLOP/s': (v['flops'] / (v['total_ms'] * 1e-3) / 1e12 if v['total_ms'] > 0 else 0.0),
-                                               'kernel_ms_per_step': v['total_ms'] / max(args.steps, 1),
-                                               'launches_per_step': v['launches'] / max(args.steps, 1)}
-                                           for k, v in prof.items() if k in ('conv_igemm_128x64', 'conv_igemm_64x64', 'conv_winograd')},
-                         'launches_per_step': conv['launches'] / max(args.steps, 1),
-                         'avg_launch_us': conv['total_ms'] * 1e3 / max(conv['launches'], 1),
-                         'flop_per_launch_avg': conv['flops'] / max(conv['launches'], 1),
-                         'kernel_ms_per_step': conv['total_ms'] / max(args.steps, 1),
-                         'score_head': {'achieved': head_tf, 'frac': head_tf / head_peak, 'peak': head_peak,
-                                        'kernel_ms_per_step': head['total_ms'] / max(args.steps, 1),
-                                        'launches_per_step': head['launches'] / max(args.steps, 1),
-                                        'note': 'hand and object solves run concurrently: these durations span the other solve\'s kernels',
-                                        'samplers_serialised': {'achieved': head_excl_tf, 'frac': head_excl_tf / head_peak,
-                                                                'avg_launch_us': head_excl['total_ms'] * 1e3 / max(head_excl['launches'], 1),
-                                                                'what': 'same kernels, object solve after the hand solve: exclusive durations (hand 32 heads + object 3 heads, averaged over launches by time)'}},
-                         # the convolutions of the step as ONE family, in ALGORITHMIC flops (2 x pixels x Cout x taps x Cin of the direct form,
-                         # whatever algorithm ran): the three direct tile classes + the Winograd launches, whose 2.25 x fewer multiply-adds
-                         # make their algorithmic rate exceed the executed one
-                         'conv_family_algorithmic': (lambda fam, ms: {
-                             'achieved': fam / (ms * 1e-3) / 1e12 if ms > 0 else 0.0, 'frac': (fam / (ms * 1e-3) / 1e12 / conv_peak) if ms > 0 else 0.0,
-                             'kernel_ms_per_step': ms / max(args.steps, 1), 'unit': 'TFLOP/s',
-                             'what': 'direct-form flops of every convolution launch / summed kernel time: conv_igemm 128x128 + 128x64 + 64x64 (executed = algorithmic) '
-                                     '+ conv_winograd (algorithmic = 2.25 x executed)'})(
-                             sum(prof[k]['flops'] for k in ('conv_igemm_128x128', 'conv_igemm_128x64', 'conv_igemm_64x64')) + 2.25 * prof['conv_winograd']['flops'],
-                             sum(prof[k]['total_ms'] for k in ('conv_igemm_128x128', 'conv_igemm_128x64', 'conv_igemm_64x64', 'conv_winograd'))),
-                         'note': 'kernel = the direct-convolution tile class with the most kernel time.  Since round 3 its most efficient layers (the 3x3 / stride-1 '
-                                 'convolutions, 113-135 TFLOP/s) run as conv_winograd launches instead, so the class average is lower than in round 2 although no '
-                                 'launch got slower; by summed exclusive time the score head (score_head below, samplers_serialised) is the largest single kernel of the step',
-                         'feature_path_gflop_per_image_ref': FEATURE_GFLOP_PER_IMAGE},
-            # HBM-bound kernels of the path (north star: MANO skinning, distance kernels, top-k as GB/s against the chip's HBM peak):
-            # achieved = ALGORITHMIC bytes (operands read once + results written once, stated at the launch site) / HIP-event kernel time
-            'hbm': {'peak_GBps': HBM_PEAK_GBPS, 'note': 'achieved = algorithmic bytes / kernel time (HIP events, instrumented repeat of the K steps); '
-                                                          'traffic = HBM bytes per launch from the newest committed rocprofv3 --pmc summary (2 x FETCH_SIZE + WRITE_SIZE; traffic_by_kernel names the file and every kernel of the class, traffic is their launch-weighted mean), null when absent',
-                    'kernels': {k: {'GB/s': (prof[k]['bytes'] / (prof[k]['total_ms'] * 1e-3) / 1e9 if prof[k]['total_ms'] > 0 else 0.0),
-                                    'frac': (prof[k]['bytes'] / (prof[k]['total_ms'] * 1e-3) / 1e9 / HBM_PEAK_GBPS if prof[k]['total_ms'] > 0 else 0.0),
-                                    'avg_launch_us': prof[k]['total_ms'] * 1e3 / max(prof[k]['launches'], 1),
-                                    'launches_per_step': prof[k]['launches'] / max(args.steps, 1),
-                                    'kernel_ms_per_step': prof[k]['total_ms'] / max(args.steps, 1),
-                                    'algorithmic_bytes_per_launch': prof[k]['bytes'] / max(prof[k]['launches'], 1),
-                                    'traffic': pmc_traffic(HBM_KERNEL_NAMES[k], workload=wl_key), 'traffic_by_kernel': pmc_traffic(HBM_KERNEL_NAMES[k], per_kernel=True, workload=wl_key),
-                                    'limited_by': HBM_LIMITS[k]} for k in hbm_classes}},
             'metrics_rows_gathered': int(all_rows.shape[0]),
-            'host_cpu': host_cpu,
             'fabric': fabric,
             'dump_outputs': dumped,
         }
+        if args.full:                                      # the per-kernel figures of the instrumented repeat, host CPU of the timed region
+            host_cpu = {'cpu_seconds_per_step': host_cpu_s / args.steps, 'busy_threads_equivalent': host_cpu_s / dt,
+                        # the eight busiest threads over the timed region, CPU ms per step (psutil; Python threads by name, the rest are the runtime's)
+                        'cpu_ms_per_step_by_thread': [[n_, 1e3 * c_ / args.steps] for n_, c_ in by_thread[:8] if c_ > 0]}
+            conv_tf = conv['flops'] / (conv['total_ms'] * 1e-3) / 1e12 if conv['total_ms'] > 0 else 0.0
+            head_tf = head['flops'] / (head['total_ms'] * 1e-3) / 1e12 if head['total_ms'] > 0 else 0.0
+            head_excl_tf = head_excl['flops'] / (head_excl['total_ms'] * 1e-3) / 1e12 if head_excl['total_ms'] > 0 else 0.0
+            # fp32-equivalent peak of the score head: the fp32 MFMA peak, or the dense bf16 peak over the 6 / 9 products per fp32 product
+            head_peak = FP32_MFMA_PEAK_TFLOPS if score_mfma == 'f32' else BF16_MFMA_PEAK_TFLOPS / int(score_mfma[-1])
+            conv_peak = FP32_MFMA_PEAK_TFLOPS if conv_mfma == 'f32' else BF16_MFMA_PEAK_TFLOPS / int(conv_mfma[-1])
+            result.update({
+                'roofline': {'bound': 'mfma', 'kernel': CONV_CLASS_NAME if conv_mfma == 'f32'
+                             else f'conv_igemm_split_kernel<128,128,4,2,{conv_mfma[-1]}> (split-bf16 products, opt-in)', 'achieved': conv_tf,
+                             'peak': conv_peak, 'unit': 'TFLOP/s', 'frac': conv_tf / conv_peak,
+                             # launch-weighted over BOTH kernels of the class (one-tile and persistent multi-tile), and only from a counter
+                             # pass taken at this batch size / sample count
+                             'traffic': pmc_traffic(CONV_CLASS_KERNELS, workload=wl_key),
+                             'traffic_source': (pmc_traffic(CONV_CLASS_KERNELS, per_kernel=True, workload=wl_key) or {}).get('source'),
+                             'timing': 'HIP events around every launch, in a separate instrumented repeat of the K steps',
+                             'algorithmic_bytes_per_launch': conv['bytes'] / max(conv['launches'], 1),
+                             'pose_encoder': ({'TFLOP/s': prof['pose_encoder']['flops'] / (prof['pose_encoder']['total_ms'] * 1e-3) / 1e12, 'frac': prof['pose_encoder']['flops'] / (prof['pose_encoder']['total_ms'] * 1e-3) / 1e12 / FP32_MFMA_PEAK_TFLOPS,
+                                               'avg_launch_us': prof['pose_encoder']['total_ms'] * 1e3 / max(prof['pose_encoder']['launches'], 1), 'launches_per_step': prof['pose_encoder']['launches'] / max(args.steps, 1),
+                                               'note': 'durations span the other solve\'s kernels, like score_head',
+                                               'samplers_serialised': ({'TFLOP/s': pe_excl['flops'] / (pe_excl['total_ms'] * 1e-3) / 1e12, 'frac': pe_excl['flops'] / (pe_excl['total_ms'] * 1e-3) / 1e12 / FP32_MFMA_PEAK_TFLOPS,
+                                                                        'avg_launch_us': pe_excl['total_ms'] * 1e3 / max(pe_excl['launches'], 1),
+                                                                        'what': 'same kernels, object solve after the hand solve: exclusive durations (flops as executed: the object state padded to 32 inputs)'}
+                                                                       if pe_excl['total_ms'] > 0 else None)} if prof.get('pose_encoder', {}).get('total_ms', 0) > 0 else None),
+                             'other_kernels': {k: {'TFLOP/s': (v['flops'] / (v['total_ms'] * 1e-3) / 1e12 if v['total_ms'] > 0 else 0.0),
+                                                   'kernel_ms_per_step': v['total_ms'] / max(args.steps, 1),
+                                                   'launches_per_step': v['launches'] / max(args.steps, 1)}
+                                               for k, v in prof.items() if k in ('conv_igemm_128x64', 'conv_igemm_64x64', 'conv_winograd')},
+                             'launches_per_step': conv['launches'] / max(args.steps, 1),
+                             'avg_launch_us': conv['total_ms'] * 1e3 / max(conv['launches'], 1),
+                             'flop_per_launch_avg': conv['flops'] / max(conv['launches'], 1),
+                             'kernel_ms_per_step': conv['total_ms'] / max(args.steps, 1),
+                             'score_head': {'achieved': head_tf, 'frac': head_tf / head_peak, 'peak': head_peak,
+                                            'kernel_ms_per_step': head['total_ms'] / max(args.steps, 1),
+                                            'launches_per_step': head['launches'] / max(args.steps, 1),
+                                            'note': 'hand and object solves run concurrently: these durations span the other solve\'s kernels',
+                                            'samplers_serialised': {'achieved': head_excl_tf, 'frac': head_excl_tf / head_peak,
+                                                                    'avg_launch_us': head_excl['total_ms'] * 1e3 / max(head_excl['launches'], 1),
+                                                                    'what': 'same kernels, object solve after the hand solve: exclusive durations (hand 32 heads + object 3 heads, averaged over launches by time)'}},
+                             # the convolutions of the step as ONE family, in ALGORITHMIC flops (2 x pixels x Cout x taps x Cin of the direct form,
+                             # whatever algorithm ran): the three direct tile classes + the Winograd launches, whose 2.25 x fewer multiply-adds
+                             # make their algorithmic rate exceed the executed one
+                             'conv_family_algorithmic': (lambda fam, ms: {
+                                 'achieved': fam / (ms * 1e-3) / 1e12 if ms > 0 else 0.0, 'frac': (fam / (ms * 1e-3) / 1e12 / conv_peak) if ms > 0 else 0.0,
+                                 'kernel_ms_per_step': ms / max(args.steps, 1), 'unit': 'TFLOP/s',
+                                 'what': 'direct-form flops of every convolution launch / summed kernel time: conv_igemm 128x128 + 128x64 + 64x64 (executed = algorithmic) '
+                                         '+ conv_winograd (algorithmic = 2.25 x executed)'})(
+                                 sum(prof[k]['flops'] for k in ('conv_igemm_128x128', 'conv_igemm_128x64', 'conv_igemm_64x64')) + 2.25 * prof['conv_winograd']['flops'],
+                                 sum(prof[k]['total_ms'] for k in ('conv_igemm_128x128', 'conv_igemm_128x64', 'conv_igemm_64x64', 'conv_winograd'))),
+                             'note': 'kernel = the direct-convolution tile class with the most kernel time.  Since round 3 its most efficient layers (the 3x3 / stride-1 '
+                                     'convolutions, 113-135 TFLOP/s) run as conv_winograd launches instead, so the class average is lower than in round 2 although no '
+                                     'launch got slower; by summed exclusive time the score head (score_head below, samplers_serialised) is the largest single kernel of the step',
+                             'feature_path_gflop_per_image_ref': FEATURE_GFLOP_PER_IMAGE},
+                # HBM-bound kernels of the path (north star: MANO skinning, distance kernels, top-k as GB/s against the chip's HBM peak):
+                # achieved = ALGORITHMIC bytes (operands read once + results written once, stated at the launch site) / HIP-event kernel time
+                'hbm': {'peak_GBps': HBM_PEAK_GBPS, 'note': 'achieved = algorithmic bytes / kernel time (HIP events, instrumented repeat of the K steps); '
+                                                              'traffic = HBM bytes per launch from the newest committed rocprofv3 --pmc summary (2 x FETCH_SIZE + WRITE_SIZE; traffic_by_kernel names the file and every kernel of the class, traffic is their launch-weighted mean), null when absent',
+                        'kernels': {k: {'GB/s': (prof[k]['bytes'] / (prof[k]['total_ms'] * 1e-3) / 1e9 if prof[k]['total_ms'] > 0 else 0.0),
+                                        'frac': (prof[k]['bytes'] / (prof[k]['total_ms'] * 1e-3) / 1e9 / HBM_PEAK_GBPS if prof[k]['total_ms'] > 0 else 0.0),
+                                        'avg_launch_us': prof[k]['total_ms'] * 1e3 / max(prof[k]['launches'], 1),
+                                        'launches_per_step': prof[k]['launches'] / max(args.steps, 1),
+                                        'kernel_ms_per_step': prof[k]['total_ms'] / max(args.steps, 1),
+                                        'algorithmic_bytes_per_launch': prof[k]['bytes'] / max(prof[k]['launches'], 1),
+                                        'traffic': pmc_traffic(HBM_KERNEL_NAMES[k], workload=wl_key), 'traffic_by_kernel': pmc_traffic(HBM_KERNEL_NAMES[k], per_kernel=True, workload=wl_key),
+                                        'limited_by': HBM_LIMITS[k]} for k in hbm_classes}},
+                'host_cpu': host_cpu,
+            })
         post_rows = lambda out, batch, engine: E.metric_rows(out, batch, gt_joint, gt_vert, 0, assets)
-        if world == 1 and not args.no_opt_in and (score_mfma, conv_mfma) == ('f32', 'f32'):
+        if args.full and world == 1 and not args.no_opt_in and (score_mfma, conv_mfma) == ('f32', 'f32'):
             result['opt_in'] = {'split_bf16x6': secondary_leg(args, model, batches, E, post_rows, {'VPHO_SCORE_MFMA': 'bf16x6', 'VPHO_CONV_MFMA': 'bf16x6'},
                 'same step, same evaluator; fp32 products of the score head and of the direct convolutions as 6 exact bf16 products each '
                 '(--score_mfma bf16x6 --conv_mfma bf16x6), fp32 storage and accumulation; opt-in, not `value`'),
                                # all nine cross products: every fp32 product exact (nothing dropped), fp32 accumulation -- VERDICT r5 item 10: reported beside x6
                                'split_bf16x9': secondary_leg(args, model, batches, E, post_rows, {'VPHO_SCORE_MFMA': 'bf16x9', 'VPHO_CONV_MFMA': 'bf16x9'},
                 'same step with all nine bf16 products per fp32 product (--score_mfma bf16x9 --conv_mfma bf16x9): no term dropped; opt-in, not `value`')}
-        if world == 1 and not args.no_opt_in and eng.roi_window and not args.no_roi_window:
+        if args.full and world == 1 and not args.no_opt_in and eng.roi_window and not args.no_roi_window:
             # the RoI-window saving is data dependent (boxes that span the crop lose it): the same step with the full stride-4 maps
             result['value_full_maps'] = secondary_leg(args, model, batches, E, post_rows, {'VPHO_ROI_WINDOW': '0'},
                 'same step with --no_roi_window: the last convolution of each FPN branch on every pixel (what boxes spanning the crop would cost)')
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             result.update(cpu_baseline_leg(args, cfg, model, sd, assets, ANCHOR_SKELETON, dev))
         emit(result)
     if world > 1:
@@ -467,8 +477,8 @@ def _r(x, sig=5):
 
 
 def compact_line(full):
-    """The one JSON line the driver parses: the contract keys, `roofline`, `cpu_baseline` and a short numeric `parity` summary --
-    a pure function of the full record (tests/test_bench_line_cpu.py holds it under LINE_LIMIT)."""
+    """The one JSON line the driver parses: the contract keys and, from a --full run, `roofline`, `cpu_baseline` and a short numeric
+    `parity` summary -- a pure function of the full record (tests/test_bench_line_cpu.py holds it under LINE_LIMIT)."""
     g = lambda d, *ks: (g(d.get(ks[0]), *ks[1:]) if (isinstance(d, dict) and len(ks) > 1) else (d.get(ks[0]) if isinstance(d, dict) else None))
     cfgf, rf = full.get('config', {}), full.get('roofline', {})
     line = {k: full.get(k) for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling',
@@ -477,20 +487,22 @@ def compact_line(full):
                                                'topk_obj', 'sample_T0', 'crop', 'pipeline_depth', 'parallelism', 'score_mfma', 'conv_mfma',
                                                'winograd_3x3', 'nfev_hand_obj_per_step')}
     line['config']['roi_window_pixel_share'] = g(cfgf, 'fpn_roi_window', 'pixel_share_hand_obj_per_batch') if g(cfgf, 'fpn_roi_window', 'enabled') else None
-    ser = g(rf, 'score_head', 'samplers_serialised') or {}
-    line['roofline'] = {k: rf.get(k) for k in ('bound', 'kernel', 'achieved', 'peak', 'unit', 'frac', 'traffic', 'traffic_source',
-                                               'algorithmic_bytes_per_launch', 'flop_per_launch_avg', 'avg_launch_us', 'launches_per_step', 'kernel_ms_per_step')}
-    line['roofline']['timing'] = 'HIP events per launch on the launch stream, instrumented repeat of the K steps'
-    # the largest kernel BY TIME is the score head; `frac` there is from exclusive durations (the object solve after the hand solve)
-    line['roofline']['dominant_by_time'] = {'kernel': 'score_head_kernel<true>', 'frac': ser.get('frac'), 'achieved': ser.get('achieved'),
-                                            'avg_launch_us': ser.get('avg_launch_us'), 'kernel_ms_per_step': g(rf, 'score_head', 'kernel_ms_per_step'),
-                                            'launches_per_step': g(rf, 'score_head', 'launches_per_step'), 'frac_overlapped': g(rf, 'score_head', 'frac')}
-    line['roofline']['classes_TFLOPs_ms'] = {k: [v.get('TFLOP/s'), v.get('kernel_ms_per_step')] for k, v in (rf.get('other_kernels') or {}).items()}
-    pe = g(rf, 'pose_encoder', 'samplers_serialised') or {}
-    line['roofline']['classes_TFLOPs_ms']['pose_encoder'] = [pe.get('TFLOP/s'), None]
-    line['roofline']['conv_family_algorithmic_frac'] = g(rf, 'conv_family_algorithmic', 'frac')
-    hb = g(full, 'hbm', 'kernels') or {}
-    line['hbm_GBps_frac'] = {k: [v.get('GB/s'), v.get('frac')] for k, v in hb.items()}
+    if 'roofline' in full:                                # --full only, like `hbm`, `cpu_baseline` and `parity`
+        ser = g(rf, 'score_head', 'samplers_serialised') or {}
+        line['roofline'] = {k: rf.get(k) for k in ('bound', 'kernel', 'achieved', 'peak', 'unit', 'frac', 'traffic', 'traffic_source',
+                                                   'algorithmic_bytes_per_launch', 'flop_per_launch_avg', 'avg_launch_us', 'launches_per_step', 'kernel_ms_per_step')}
+        line['roofline']['timing'] = 'HIP events per launch on the launch stream, instrumented repeat of the K steps'
+        # the largest kernel BY TIME is the score head; `frac` there is from exclusive durations (the object solve after the hand solve)
+        line['roofline']['dominant_by_time'] = {'kernel': 'score_head_kernel<true>', 'frac': ser.get('frac'), 'achieved': ser.get('achieved'),
+                                                'avg_launch_us': ser.get('avg_launch_us'), 'kernel_ms_per_step': g(rf, 'score_head', 'kernel_ms_per_step'),
+                                                'launches_per_step': g(rf, 'score_head', 'launches_per_step'), 'frac_overlapped': g(rf, 'score_head', 'frac')}
+        line['roofline']['classes_TFLOPs_ms'] = {k: [v.get('TFLOP/s'), v.get('kernel_ms_per_step')] for k, v in (rf.get('other_kernels') or {}).items()}
+        pe = g(rf, 'pose_encoder', 'samplers_serialised') or {}
+        line['roofline']['classes_TFLOPs_ms']['pose_encoder'] = [pe.get('TFLOP/s'), None]
+        line['roofline']['conv_family_algorithmic_frac'] = g(rf, 'conv_family_algorithmic', 'frac')
+    if 'hbm' in full:
+        hb = g(full, 'hbm', 'kernels') or {}
+        line['hbm_GBps_frac'] = {k: [v.get('GB/s'), v.get('frac')] for k, v in hb.items()}
     if full.get('cpu_baseline') is not None:
         line['cpu_baseline'] = full['cpu_baseline']
     par = full.get('parity')

@@ -1,7 +1,7 @@
 """Shared by the rocpd_* scripts: where in a trace of `bench.py` the PIPELINED evaluator ran.
 
-bench.py runs, in this order: warm-up, the timed pipelined steps, sequential steps (step-time spread), the parity legs.  The END of
-a trace is therefore sequential work; the pipelined steps are the kernels launched by the evaluator's slot threads (the threads other
+bench.py --full runs, in this order: warm-up, the timed pipelined steps, sequential steps (step-time spread), the parity legs.  The END
+of such a trace is therefore sequential work; the pipelined steps are the kernels launched by the evaluator's slot threads (the threads other
 than the main one that launch whole feature passes).  Their first launches are the slots' graph captures, one after the other, so the
 window is cut by launch-count percentiles: from the 35th to the 93rd percentile of the slot threads' launches lies inside the dense,
 pipelined region and leaves out its drain."""

@@ -15,7 +15,7 @@ csv() { find $O/$1 -name "*$2.csv" | head -1; }
 prof() { local out=$1; shift; (cd /tmp && TMPDIR=/tmp gstep 400 $O/${out}.log rocprofv3 "$@"); }
 has() { case " $PART " in *" $1 "*|*" all "*) return 0;; esac; return 1; }
 scrub() { for d in "$@"; do [ -n "$d" ] && [ -d "$O/$d" ] && rm -r "$O/$d"; done; return 0; }
-B="python3 $R/bench.py --no_cpu_baseline --no_opt_in"
+B="python3 $R/bench.py --full --no_cpu_baseline --no_opt_in"
 cd $R
 if has cfg2; then
   scrub ${T}_seq ${T}_pipe ${T}_pmc_f ${T}_pmc_w ${T}_pmc_m
@@ -28,7 +28,7 @@ if has cfg2; then
   python3 scripts/rocpd_stats.py $(db ${T}_pipe) 30 --pipelined > $O/${T}_pipe_ss.txt && python3 scripts/rocpd_exposed.py $(db ${T}_pipe) --pipelined > $O/${T}_exposed.txt &&
   python3 scripts/pmc_summary.py $(csv ${T}_pmc_f counter_collection) $(csv ${T}_pmc_w counter_collection) $O/${T}_pmc_hbm.json > $O/${T}_pmc_hbm.txt &&
   python3 scripts/pmc_mfma_summary.py $(csv ${T}_pmc_m counter_collection) $(csv ${T}_pmc_m kernel_trace) > $O/${T}_pmc_mfma.txt &&
-  gstep 400 $O/${T}_bench_default.log python3 bench.py && grep '^{' $O/${T}_bench_default.log > $O/${T}_bench_default.json && cp $O/bench_detail.json $O/${T}_bench_default_detail.json
+  gstep 400 $O/${T}_bench_default.log python3 bench.py --full && grep '^{' $O/${T}_bench_default.log > $O/${T}_bench_default.json && cp $O/bench_detail.json $O/${T}_bench_default_detail.json
   scrub ${T}_seq ${T}_pipe ${T}_pmc_f ${T}_pmc_w ${T}_pmc_m; head -12 $O/${T}_seq_ss.txt | cut -c1-160
 fi
 if has exposed; then

@@ -1,7 +1,7 @@
 """What the pipelined step pays beyond its chip-filling kernels: the time in which NO convolution / score-head kernel is executing,
 split by the kernels that run there (or idle), from a rocprofv3 rocpd database (steady state = the last MS ms).
 usage: rocpd_exposed.py DB [--last-ms MS | --pipelined] [--big 'conv_igemm,conv_winograd,score_head']
-(--pipelined: the steady state of bench.py's pipelined steps, scripts/_rocpd.py; the END of a bench trace is its sequential legs)"""
+(--pipelined: the steady state of bench.py's pipelined steps, scripts/_rocpd.py; the END of a bench --full trace is its sequential legs)"""
 import collections, sqlite3, sys
 a = sys.argv
 last_ms = float(a[a.index('--last-ms') + 1]) if '--last-ms' in a else 300.0

@@ -3,7 +3,7 @@
 usage: rocpd_stats.py DB [top_n] [--last-ms MS | --pipelined]
        --last-ms: only dispatches that start in the final MS of the trace (a sequential run: the steady-state steps without model
        packing / warm-up); --pipelined: only the steady state of bench.py's pipelined steps (scripts/_rocpd.py: the END of a bench
-       trace is its sequential legs)
+       --full trace is its sequential legs)
 """
 import sqlite3
 import sys

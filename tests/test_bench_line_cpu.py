@@ -95,3 +95,20 @@ def test_dump_outputs_keeps_small_arrays_whole_and_samples_large_ones_within_the
     assert total <= limit
     with pytest.raises(AssertionError):
         bench.dump_outputs({'ints': np.arange(4)}, str(tmp_path / 'c'))
+
+
+def test_a_plain_run_prints_the_headline_without_the_full_blocks():
+    full = json.load(open(CANNED[0]))
+    plain = {k: full[k] for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling',
+                                  'vs_baseline', 'dtype', 'data', 'config')}
+    line = json.loads(json.dumps(bench.compact_line(plain), allow_nan=False, separators=(',', ':')))
+    for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+        assert line[k] == full[k], k
+    assert not {'roofline', 'hbm_GBps_frac', 'cpu_baseline', 'parity'} & set(line)
+
+
+def test_full_is_off_by_default(monkeypatch):
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1', '--steps', '3', '--warmup', '1'])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1', '--full'])
+    assert bench.parse().full is True
