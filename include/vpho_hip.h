@@ -431,6 +431,25 @@ VPHO_API int vpho_obj_metrics_f64(const vpho_obj_metric_tables* t, const double*
                          const int* obj_id, int n_img, int max_verts, double* out, void* workspace, long long workspace_bytes,
                          void* stream);
 
+/* Multi-hypothesis evaluation: every one of the n_hyp sampled candidates of an image scored against the image's ground truth,
+ * which is broadcast over the candidates (test_diff_hand / test_diff_object with is_eval_best, train_diff_hand_obj.py:454-523).
+ * vpho_hand_metrics_multi_f32: TesterHand.__call__ on pd_* [n_img][n_hyp][P][3] (lib/engine/test.py:589-597,657-679).
+ *   pd [n_img][n_hyp][n_pts][3] fp32 in the model frame, as predict returns diff_final_hand_joint / diff_final_hand_vert; the
+ *   postprocess of train_diff_hand_obj.py:578-602 (x un-flipped where !is_right, root_joint [n_img][3] added) is applied on load.
+ *   gt [n_img][n_pts][3]; is_right [n_img] (0 / 1).  mean_err, pa_mean_err [n_img][n_hyp]: MJE and PA-MJE in metres.
+ * vpho_obj_metrics_multi_f64: TesterObject.__call__ (test.py:240-503) once per candidate slice pd_rt[:, s], and
+ *   TesterObject.postprocess (test.py:522-567).  pd_rt [n_img][n_hyp][3][4] fp64; gt_rt, cam_intr, obj_id, max_verts as in
+ *   vpho_obj_metrics_f64.  out [n_img][n_hyp][16] in the column order of vpho_obj_metrics_f64; best [n_img][16] = per-image
+ *   min over the candidates (max for ADD<0.1d, ADD-S<0.1d, REP<5px and the F-scores, test.py:529-538); mean [n_img][16] =
+ *   mean over the candidates.  best and mean may be NULL.  The workspace is O(n_img * n_hyp); its size comes from
+ *   vpho_obj_metrics_multi_workspace_bytes (-1 on a bad argument).  Deterministic: fixed reduction orders throughout. */
+VPHO_API int vpho_hand_metrics_multi_f32(const float* pd, const float* gt, const float* root_joint, const unsigned char* is_right, int n_img,
+                                int n_hyp, int n_pts, float* mean_err, float* pa_mean_err, void* stream);
+VPHO_API long long vpho_obj_metrics_multi_workspace_bytes(const vpho_obj_metric_tables* t, int n_img, int n_hyp, int max_verts);
+VPHO_API int vpho_obj_metrics_multi_f64(const vpho_obj_metric_tables* t, const double* pd_rt, const double* gt_rt, const double* cam_intr,
+                               const int* obj_id, int n_img, int n_hyp, int max_verts, double* out, double* best, double* mean,
+                               void* workspace, long long workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Pseudo-force label optimisation (force_optim.py / lib/engine/force_optimization.py:110-207).
  * vpho_anchor_frames_f32: ForceAnchor.__call__ (lib/utils/physics_fn.py:224-257) -> pts [n][32][3], frames [n][32][3][3]

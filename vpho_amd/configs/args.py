@@ -12,6 +12,7 @@ class Config:
     def __init__(self):
         self.mode = 'train'
         self.eval_full = False
+        self.eval_best = False        # also score every sampled hypothesis: one-candidate, best-of-S and mean-of-S tables (is_eval_best)
         self.mark = ''
         self.random_seed = 0
         self.output_dir = 'output'
@@ -58,6 +59,7 @@ def _parser():
     p = argparse.ArgumentParser(description='Hand-Object Pose Estimation (MI355X hot path)')
     p.add_argument('--mode', type=str, default='train', choices=['train', 'eval', 'infer'])
     p.add_argument('--eval_full', action='store_true')
+    p.add_argument('--eval_best', action='store_true')
     p.add_argument('--mark', type=str, default='')
     p.add_argument('--random_seed', type=int, default=0)
     p.add_argument('--output_dir', type=str, default='output')

@@ -9,6 +9,8 @@ The forward pass itself needs no collective: the image batch is the only sharded
 import torch
 import torch.distributed as dist
 
+from .ops_names import MULTI_TABLES  # noqa: F401  (table names of summarize with eval_best)
+
 # row layout: [global image index, MJE(regression), MJE(first hypothesis), MJE(aggregated), MVE(aggregated),
 #              |agg - regression| mean joint distance (mm), object translation norm (m), is_right,
 #              PA-MJE(regression), PA-MJE(aggregated), PA-MVE(aggregated), 0,
@@ -16,6 +18,15 @@ import torch.distributed as dist
 #              test.py:240-503: MCE, OCE, MCE2, ADD, ADD-S, ADD<0.1d, ADD-S<0.1d, REP, REP<5px, CD, F-score x6)]
 ROW = 28
 OBJ_COL = 12
+# with eval_best (cfg.eval_best, the reference's is_eval_best) every row carries MULTI more columns from ROW on, in the order of
+# ops_names.MULTI_COLUMNS: hand one_candidate / best_of_S / mean_of_S (MJE, PA-MJE, MVE, PA-MVE in mm, 4 each), then object
+# one_candidate / best_of_S / mean_of_S (the 16 OBJ_METRIC_NAMES each).  Columns 0-27 are the same with and without the flag.
+MULTI = 60
+ROW_BEST = ROW + MULTI
+
+
+def row_width(eval_best=False):
+    return ROW_BEST if eval_best else ROW
 
 
 def mje_mm(pd, gt):
@@ -53,11 +64,45 @@ def object_metric_block(out, data, assets):
     return M(pd_rt, data['gt_obj_rt'].double().contiguous(), data['cam_intr'].double().contiguous(), M.obj_ids(data['obj_name']))
 
 
-def metric_rows(out, data, gt_joint, gt_vert, first_index, assets=None):
-    """(bs, ROW) fp32 on the model's device."""
+def multi_hypothesis_block(out, data, gt_joint, gt_vert, assets=None):
+    """(bs, MULTI) fp32: every sampled hypothesis scored (test_diff_hand / test_diff_object with is_eval_best,
+    train_diff_hand_obj.py:454-523) and reduced per image to hypothesis 0, best-of-S and mean-of-S.  Hand by the multi-hypothesis
+    Procrustes kernel on the model-frame candidates (postprocess on load), object by ObjectMetrics.multi on obj_9D_to_mat + root of
+    every candidate; object columns stay 0 without object tables or data['gt_obj_rt'], as in the 28-column block."""
+    from . import ops
+    if not gt_joint.is_cuda:
+        raise RuntimeError('multi_hypothesis_block: the multi-hypothesis metrics run on the GPU only (no CPU path)')
+    bs = gt_joint.shape[0]
+    blk = torch.zeros((bs, MULTI), device=gt_joint.device, dtype=torch.float32)
+    root = data['root_joint'].float().contiguous()
+    c = lambda t: t.float().contiguous()
+    mje, pa_mje = ops.hand_metrics_multi(c(out['diff_final_hand_joint']), c(gt_joint), root, data['is_right'])
+    mve, pa_mve = ops.hand_metrics_multi(c(out['diff_final_hand_vert']), c(gt_vert), root, data['is_right'])
+    hand = torch.stack([mje, pa_mje, mve, pa_mve], -1) * 1000.0                 # (bs, S, 4) mm
+    blk[:, 0:4] = hand[:, 0]
+    blk[:, 4:8] = hand.amin(1)
+    blk[:, 8:12] = hand.mean(1)
+    if assets is not None and 'gt_obj_rt' in data:
+        key = (id(assets), str(gt_joint.device))
+        if key not in _OBJ_METRICS:
+            _OBJ_METRICS[key] = ops.ObjectMetrics(assets['ycb'], gt_joint.device)
+        M = _OBJ_METRICS[key]
+        x = out['diff_final_obj_6d']
+        S = x.shape[1]
+        pd_rt = ops.obj_9d_to_rt(x.reshape(bs * S, 9).double().contiguous(), root.repeat_interleave(S, 0).contiguous()).view(bs, S, 3, 4)
+        per, best, mean = M.multi(pd_rt, data['gt_obj_rt'].double().contiguous(), data['cam_intr'].double().contiguous(),
+                                  M.obj_ids(data['obj_name']))
+        blk[:, 12:28] = per[:, 0].float()
+        blk[:, 28:44] = best.float()
+        blk[:, 44:60] = mean.float()
+    return blk
+
+
+def metric_rows(out, data, gt_joint, gt_vert, first_index, assets=None, eval_best=False):
+    """(bs, ROW) fp32 on the model's device; (bs, ROW_BEST) with eval_best (multi_hypothesis_block appended)."""
     pp = postprocess(out, data['root_joint'], data['is_right'])
     bs = gt_joint.shape[0]
-    rows = torch.empty((bs, ROW), device=gt_joint.device, dtype=torch.float32)
+    rows = torch.empty((bs, row_width(eval_best)), device=gt_joint.device, dtype=torch.float32)
     if torch.is_tensor(first_index):                 # per-image ids (a loader batch that is not a run of the data set)
         rows[:, 0] = first_index.to(device=rows.device, dtype=torch.float32).reshape(bs)
     else:
@@ -69,7 +114,7 @@ def metric_rows(out, data, gt_joint, gt_vert, first_index, assets=None):
     rows[:, 5] = mje_mm(pp['agg_hand_joint'], pp['reg_hand_joint'])
     rows[:, 6] = out['agg_obj_6d'][:, 6:].float().norm(dim=-1)
     rows[:, 7] = data['is_right'].float()
-    rows[:, 8:] = 0.0
+    rows[:, 8:ROW] = 0.0
     if gt_joint.is_cuda:                 # Procrustes-aligned metrics by the HIP kernel (test.py:657-680 on the device)
         from . import ops
         c = lambda t: t.float().contiguous()
@@ -78,6 +123,8 @@ def metric_rows(out, data, gt_joint, gt_vert, first_index, assets=None):
         rows[:, 10] = ops.hand_metrics(c(pp['agg_hand_vert']), c(gt_vert))[1] * 1000.0
         if assets is not None and 'gt_obj_rt' in data:
             rows[:, OBJ_COL:OBJ_COL + 16] = object_metric_block(out, data, assets).float()
+    if eval_best:
+        rows[:, ROW:] = multi_hypothesis_block(out, data, gt_joint, gt_vert, assets)
     return rows
 
 
@@ -199,6 +246,19 @@ def summarize(rows):
     # object table (test.py:521-584 'average_instance' column: distances in mm, hit rates / F-scores in percent, REP in pixels)
     from .ops_names import OBJ_METRIC_NAMES
     obj = rows[:, OBJ_COL:OBJ_COL + 16].double().mean(0)
-    res['object'] = {k: float(obj[i] * (1000.0 if k in ('MCE', 'OCE', 'MCE2', 'ADD', 'ADDS', 'CD') else (1.0 if k == 'REP' else 100.0)))
-                     for i, k in enumerate(OBJ_METRIC_NAMES)}
+    res['object'] = _object_table(obj)
+    if rows.shape[1] >= ROW_BEST:
+        # multi-hypothesis tables (train_diff_hand_obj.py:466-469,494-496 one_candidate; TesterObject.postprocess best_candidate_pose),
+        # over all images: hand in mm, object in the units of the object table
+        from .ops_names import HAND_METRIC_NAMES, MULTI_TABLES
+        blk = rows[:, ROW:ROW_BEST].double().mean(0)
+        for t, name in enumerate(MULTI_TABLES):
+            res[name] = dict(hand={k: float(blk[4 * t + i]) for i, k in enumerate(HAND_METRIC_NAMES)},
+                             object=_object_table(blk[12 + 16 * t:28 + 16 * t]))
     return res
+
+
+def _object_table(obj):
+    from .ops_names import OBJ_METRIC_NAMES
+    return {k: float(obj[i] * (1000.0 if k in ('MCE', 'OCE', 'MCE2', 'ADD', 'ADDS', 'CD') else (1.0 if k == 'REP' else 100.0)))
+            for i, k in enumerate(OBJ_METRIC_NAMES)}

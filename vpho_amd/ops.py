@@ -22,6 +22,7 @@ if lib.vpho_abi_version() != ABI_VERSION:
     raise ImportError(f'{LIB_PATH} implements ABI version {lib.vpho_abi_version()}, this binding expects {ABI_VERSION}: rebuild the '
                       f'extension (python -m vpho_amd.build --force)')
 lib.vpho_obj_metrics_workspace_bytes.restype = C.c_longlong
+lib.vpho_obj_metrics_multi_workspace_bytes.restype = C.c_longlong
 lib.vpho_bn_workspace_bytes.restype = C.c_longlong
 lib.vpho_conv2d_wgrad_workspace_bytes.restype = C.c_longlong
 lib.vpho_mha_bwd_workspace_bytes.restype = C.c_longlong
@@ -1011,6 +1012,19 @@ def hand_metrics(pd, gt, per_point=False):
     return (me, pa, pp) if per_point else (me, pa)
 
 
+def hand_metrics_multi(pd, gt, root_joint, is_right):
+    """Every sampled hand hypothesis against the image's ground truth (TesterHand.__call__ on pd (n,S,P,3), test.py:589-597,657-679).
+    pd (n,S,P,3) fp32 in the model frame as predict returns it (diff_final_hand_joint / _vert); the postprocess of
+    train_diff_hand_obj.py:578-602 (un-flip x of left hands, add the root) happens in the kernel as points are loaded.
+    gt (n,P,3) fp32, root_joint (n,3) fp32, is_right (n,) bool -> MJE (n,S), PA-MJE (n,S) in metres."""
+    n, S, P, _ = pd.shape
+    assert gt.shape == (n, P, 3) and root_joint.shape == (n, 3) and is_right.shape == (n,)
+    me, pa = _new((n, S), pd), _new((n, S), pd)
+    flag = is_right.to(device=pd.device, dtype=torch.uint8).contiguous()
+    _call('vpho_hand_metrics_multi_f32', _f32(pd), _f32(gt), _f32(root_joint), _u8(flag), I(n), I(S), I(P), _f32(me), _f32(pa))
+    return me, pa
+
+
 def obj_9d_to_rt(pose9, root_joint):
     """(n,9) fp64 [rot6d | t], (n,3) fp32 root -> (n,3,4) fp64 [R | t + root]  (transform_fn.py:85-90, train_diff_hand_obj.py:594-597)"""
     n = pose9.shape[0]
@@ -1066,6 +1080,21 @@ class ObjectMetrics:
         _call('vpho_obj_metrics_f64', C.byref(self.c), _f64(pd_rt), _f64(gt_rt), _f64(cam_intr), _i32(obj_id), I(n), I(self.max_verts),
               _f64(out), _ptr(ws), LL(ws.numel()))
         return out
+
+    def multi(self, pd_rt, gt_rt, cam_intr, obj_id):
+        """Every sampled object hypothesis (TesterObject.__call__ per candidate slice pd_rt[:, s], then TesterObject.postprocess,
+        test.py:240-567).  pd_rt (n,S,3,4), gt_rt (n,3,4), cam_intr (n,3,3) fp64, obj_id (n,) int32 ->
+        per-candidate (n,S,16), best-of-S (n,16) and mean-of-S (n,16) fp64, columns in the order of OBJ_METRIC_NAMES."""
+        n, S = pd_rt.shape[:2]
+        assert pd_rt.shape == (n, S, 3, 4) and gt_rt.shape == (n, 3, 4) and cam_intr.shape == (n, 3, 3) and obj_id.shape == (n,)
+        need = lib.vpho_obj_metrics_multi_workspace_bytes(C.byref(self.c), I(n), I(S), I(self.max_verts))
+        if need < 0:
+            raise VphoError('vpho_obj_metrics_multi_workspace_bytes: bad argument')
+        ws = torch.empty(need, dtype=torch.uint8, device=self.device)          # per call, as in __call__
+        per, best, mean = _new((n, S, 16), pd_rt, torch.float64), _new((n, 16), pd_rt, torch.float64), _new((n, 16), pd_rt, torch.float64)
+        _call('vpho_obj_metrics_multi_f64', C.byref(self.c), _f64(pd_rt), _f64(gt_rt), _f64(cam_intr), _i32(obj_id), I(n), I(S),
+              I(self.max_verts), _f64(per), _f64(best), _f64(mean), _ptr(ws), LL(ws.numel()))
+        return per, best, mean
 
 
 # ----------------------------------------------------------------------------------------------- score-network training

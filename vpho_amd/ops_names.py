@@ -1,3 +1,10 @@
 """Column names shared by the device metric kernels and the host-side tables (importable without the HIP library)."""
 OBJ_METRIC_NAMES = ('MCE', 'OCE', 'MCE2', 'ADD', 'ADDS', 'ADD01d', 'ADDS01d', 'REP', 'REP5', 'CD',
                     'FSCORE@2mm', 'FSCORE@5mm', 'FSCORE@10mm', 'FSCORE@2cm', 'FSCORE@5cm', 'FSCORE@10cm')
+HAND_METRIC_NAMES = ('MJE', 'PA_MJE', 'MVE', 'PA_MVE')
+# the block that evaluate.metric_rows appends after its 28 columns with eval_best: three hand tables (mm), then three object tables
+# (OBJ_METRIC_NAMES units: metres / pixels / {0,1} / [0,1]); one_candidate = hypothesis 0, best_of_S = per-image min over the S
+# hypotheses (max for the hit rates and F-scores, TesterObject.postprocess), mean_of_S = per-image mean over the S hypotheses
+MULTI_TABLES = ('one_candidate', 'best_of_S', 'mean_of_S')
+MULTI_COLUMNS = tuple(f'{t}/hand/{k}' for t in MULTI_TABLES for k in HAND_METRIC_NAMES) + \
+    tuple(f'{t}/object/{k}' for t in MULTI_TABLES for k in OBJ_METRIC_NAMES)
