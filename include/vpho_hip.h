@@ -450,6 +450,34 @@ VPHO_API int vpho_obj_metrics_multi_f64(const vpho_obj_metric_tables* t, const d
                                const int* obj_id, int n_img, int n_hyp, int max_verts, double* out, double* best, double* mean,
                                void* workspace, long long workspace_bytes, void* stream);
 
+/* Hand-object penetration and contact (--eval_physics).  The object meshes as per-triangle records
+ * tri [tri_offset[n_obj]][VPHO_PEN_TRI_STRIDE] fp64, objects concatenated (vpho_amd/physics_eval.py builds them on the host):
+ *   fields 0-18 in the object's hash frame (q = scale * p + translate, the mesh bbox mapped onto [0.5, 511.5]^3; corners t1, t2, t3):
+ *     0-1 t3.xy, 2-5 A = (t1.x - t3.x, t2.x - t3.x; t1.y - t3.y, t2.y - t3.y) row-major, 6 sign(det A), 7 |det A|,
+ *     8-9 t1.xy, 10-11 n.xy, 12 sign(n.z), 13 |n.z| with n = (t3 - t1) x (t2 - t1), 14 t1.z |n.z| (NaN where n.z == 0),
+ *     15-18 the xy hash cells of the triangle's bbox (int-truncated, clamped to [0, 511]): x0, x1, y0, y1;
+ *   fields 19-27 in the model frame (metres): corner a, b - a, c - a.
+ * scale, translate [n_obj][3].
+ * vpho_hand_obj_penetration_f64: verts [n][V][3] fp32 in the camera frame, obj_rt [n][3][4] fp64 [R | t] (model -> camera),
+ * obj_id [n].  Per vertex p = R^T (v - t); inside(p) by the z-ray parity rule at resolution VPHO_PEN_RESOLUTION, d(p) = exact
+ * distance to the nearest triangle; sd [n][V] = -d if inside else d (metres), inside [n][V] = 0 / 1; per_image [n][4] =
+ * penetration depth (max d over the inside vertices, 0 if none), inside-vertex count, min sd, contact (min sd <= contact_thresh).
+ * sd and inside may be NULL (then a stream-ordered temporary holds them).  An obj_id outside [0, n_obj) cannot be refused without a
+ * host sync: its image gets NaN in sd and per_image and inside = 0 (vpho_amd.ops.HandObjectPenetration refuses such ids on the host).
+ * n == 0 is a no-op.  Deterministic (max / min / count). */
+#define VPHO_PEN_TRI_STRIDE 28
+#define VPHO_PEN_RESOLUTION 512
+typedef struct vpho_obj_mesh_tables {
+    const double* tri;             /* [tri_offset[n_obj]][VPHO_PEN_TRI_STRIDE] */
+    const int* tri_offset;         /* [n_obj + 1] */
+    const double* scale;           /* [n_obj][3] */
+    const double* translate;       /* [n_obj][3] */
+    int n_obj;
+} vpho_obj_mesh_tables;
+VPHO_API int vpho_hand_obj_penetration_f64(const vpho_obj_mesh_tables* t, const float* verts, int n, int V, const double* obj_rt,
+                                  const int* obj_id, double contact_thresh, double* sd, unsigned char* inside, double* per_image,
+                                  void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Pseudo-force label optimisation (force_optim.py / lib/engine/force_optimization.py:110-207).
  * vpho_anchor_frames_f32: ForceAnchor.__call__ (lib/utils/physics_fn.py:224-257) -> pts [n][32][3], frames [n][32][3][3]

@@ -23,10 +23,14 @@ OBJ_COL = 12
 # one_candidate / best_of_S / mean_of_S (the 16 OBJ_METRIC_NAMES each).  Columns 0-27 are the same with and without the flag.
 MULTI = 60
 ROW_BEST = ROW + MULTI
+# with eval_physics (cfg.eval_physics) every row carries PHYS more columns, last (after the eval_best block if there is one), in the
+# order of ops_names.PHYSICS_COLUMNS: PD (m), n_inside, min sd (m), contact of (aggregated hand, aggregated object), then of (ground-truth
+# hand, ground-truth object).  The columns before them are the same with and without the flag.
+PHYS = 8
 
 
-def row_width(eval_best=False):
-    return ROW_BEST if eval_best else ROW
+def row_width(eval_best=False, eval_physics=False):
+    return (ROW_BEST if eval_best else ROW) + (PHYS if eval_physics else 0)
 
 
 def mje_mm(pd, gt):
@@ -98,11 +102,45 @@ def multi_hypothesis_block(out, data, gt_joint, gt_vert, assets=None):
     return blk
 
 
-def metric_rows(out, data, gt_joint, gt_vert, first_index, assets=None, eval_best=False):
-    """(bs, ROW) fp32 on the model's device; (bs, ROW_BEST) with eval_best (multi_hypothesis_block appended)."""
+_PHYSICS = {}
+
+
+def physics_meter(assets, device):
+    """the HandObjectPenetration of an asset set on a device, built once (object meshes: physics_eval.object_meshes)"""
+    key = (id(assets), str(device))
+    if key not in _PHYSICS:
+        from . import ops
+        from .configs.args import cfg
+        from .physics_eval import object_meshes
+        _PHYSICS[key] = ops.HandObjectPenetration(object_meshes(assets, cfg.asset_root), device)
+    return _PHYSICS[key]
+
+
+def physics_block(pp, out, data, gt_vert, meshes):
+    """(bs, PHYS) fp32: hand-object penetration and contact of the aggregated hand vertices (pp['agg_hand_vert'],
+    postprocessed: camera frame) with the aggregated object pose (obj_9D_to_mat + root, as object_metric_block), then of the ground-truth
+    vertices gt_vert with data['gt_obj_rt'] (NaN without it).  ``meshes``: an ops.HandObjectPenetration (physics_meter)."""
+    from . import ops
+    from .configs.args import cfg
+    if not gt_vert.is_cuda:
+        raise RuntimeError('physics_block: the penetration metrics run on the GPU only (no CPU path)')
+    bs = gt_vert.shape[0]
+    blk = torch.full((bs, PHYS), float('nan'), device=gt_vert.device, dtype=torch.float32)
+    ids = meshes.obj_ids(data['obj_name'])
+    th = float(cfg.physics_contact_thresh)
+    pd_rt = ops.obj_9d_to_rt(out['agg_obj_6d'].double().contiguous(), data['root_joint'].float().contiguous())
+    blk[:, 0:4] = meshes(pp['agg_hand_vert'].float().contiguous(), pd_rt, ids, th).float()
+    if 'gt_obj_rt' in data:
+        blk[:, 4:8] = meshes(gt_vert.float().contiguous(), data['gt_obj_rt'].double().contiguous(), ids, th).float()
+    return blk
+
+
+def metric_rows(out, data, gt_joint, gt_vert, first_index, assets=None, eval_best=False, eval_physics=False):
+    """(bs, ROW) fp32 on the model's device; (bs, ROW_BEST) with eval_best (multi_hypothesis_block appended); PHYS more columns with
+    eval_physics (physics_block, last)."""
     pp = postprocess(out, data['root_joint'], data['is_right'])
     bs = gt_joint.shape[0]
-    rows = torch.empty((bs, row_width(eval_best)), device=gt_joint.device, dtype=torch.float32)
+    rows = torch.empty((bs, row_width(eval_best, eval_physics)), device=gt_joint.device, dtype=torch.float32)
     if torch.is_tensor(first_index):                 # per-image ids (a loader batch that is not a run of the data set)
         rows[:, 0] = first_index.to(device=rows.device, dtype=torch.float32).reshape(bs)
     else:
@@ -124,7 +162,11 @@ def metric_rows(out, data, gt_joint, gt_vert, first_index, assets=None, eval_bes
         if assets is not None and 'gt_obj_rt' in data:
             rows[:, OBJ_COL:OBJ_COL + 16] = object_metric_block(out, data, assets).float()
     if eval_best:
-        rows[:, ROW:] = multi_hypothesis_block(out, data, gt_joint, gt_vert, assets)
+        rows[:, ROW:ROW_BEST] = multi_hypothesis_block(out, data, gt_joint, gt_vert, assets)
+    if eval_physics:
+        if assets is None:
+            raise ValueError('metric_rows: eval_physics needs the asset tables (object meshes)')
+        rows[:, -PHYS:] = physics_block(pp, out, data, gt_vert, physics_meter(assets, gt_joint.device))
     return rows
 
 
@@ -247,6 +289,8 @@ def summarize(rows):
     from .ops_names import OBJ_METRIC_NAMES
     obj = rows[:, OBJ_COL:OBJ_COL + 16].double().mean(0)
     res['object'] = _object_table(obj)
+    if rows.shape[1] in (ROW + PHYS, ROW_BEST + PHYS):
+        res['physics'] = _physics_table(rows[:, -PHYS:])
     if rows.shape[1] >= ROW_BEST:
         # multi-hypothesis tables (train_diff_hand_obj.py:466-469,494-496 one_candidate; TesterObject.postprocess best_candidate_pose),
         # over all images: hand in mm, object in the units of the object table
@@ -262,3 +306,17 @@ def _object_table(obj):
     from .ops_names import OBJ_METRIC_NAMES
     return {k: float(obj[i] * (1000.0 if k in ('MCE', 'OCE', 'MCE2', 'ADD', 'ADDS', 'CD') else (1.0 if k == 'REP' else 100.0)))
             for i, k in enumerate(OBJ_METRIC_NAMES)}
+
+
+def _physics_table(blk):
+    """physics table over all images, per source (pred / gt): mean and largest PD (mm), % of images with a hand vertex inside the object,
+    mean inside-vertex count, % of images in contact (NaN for a source without values, e.g. gt without object ground truth)"""
+    from .ops_names import PHYSICS_SOURCES
+    blk = blk.double()
+    res = {}
+    for s, name in enumerate(PHYSICS_SOURCES):
+        b = blk[:, 4 * s:4 * s + 4]
+        res[name] = dict(PD_mm=float(b[:, 0].mean() * 1000.0), PD_max_mm=float(b[:, 0].max() * 1000.0) if b.shape[0] else float('nan'),
+                         penetration_rate_pct=float((b[:, 1] > 0).double().mean() * 100.0) if not b[:, 1].isnan().any() else float('nan'),
+                         inside_verts=float(b[:, 1].mean()), contact_rate_pct=float(b[:, 3].mean() * 100.0))
+    return res

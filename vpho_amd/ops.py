@@ -1097,6 +1097,61 @@ class ObjectMetrics:
         return per, best, mean
 
 
+class ObjMeshTables(C.Structure):
+    _fields_ = [('tri', C.c_void_p), ('tri_offset', C.c_void_p), ('scale', C.c_void_p), ('translate', C.c_void_p), ('n_obj', I)]
+
+
+class HandObjectPenetration:
+    """Hand-object penetration and contact (--eval_physics) on the device: per-triangle tables of every object mesh,
+    built once (physics_eval.mesh_tables), + thin wrapper of vpho_hand_obj_penetration_f64.  ``meshes``: {name: {'verts', 'faces'}}
+    (physics_eval.object_meshes)."""
+
+    def __init__(self, meshes, device):
+        import numpy as np
+        from .physics_eval import mesh_tables
+        self.names = list(meshes.keys())
+        self.name_to_id = {n: i for i, n in enumerate(self.names)}
+        tabs = [mesh_tables(meshes[n]['verts'], meshes[n]['faces']) for n in self.names]
+        counts = [t[0].shape[0] for t in tabs]
+        d = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64)).to(device)
+        self.tri = d(np.concatenate([t[0] for t in tabs]))
+        self.tri_offset = torch.as_tensor(np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)).to(device)
+        self.scale = d(np.stack([t[1] for t in tabs]))
+        self.translate = d(np.stack([t[2] for t in tabs]))
+        self.n_tri = counts
+        self.c = ObjMeshTables(self.tri.data_ptr(), self.tri_offset.data_ptr(), self.scale.data_ptr(), self.translate.data_ptr(),
+                               len(self.names))
+        self.device = device
+
+    def obj_ids(self, names):
+        """class indices of a batch as a device tensor (pinned host memory, asynchronous copy on the caller's stream, as
+        ObjectMetrics.obj_ids); an unknown name raises VphoError"""
+        bad = [n for n in names if n not in self.name_to_id]
+        if bad:
+            raise VphoError(f'HandObjectPenetration: no mesh for the objects {bad}')
+        return _ids_to_device([self.name_to_id[n] for n in names], self.device)
+
+    def __call__(self, verts, obj_rt, obj_id, contact_thresh=0.005, per_vertex=False):
+        """verts (n,V,3) fp32 hand vertices and obj_rt (n,3,4) fp64 [R | t] object poses, both in the camera frame; obj_id: (n,) int32
+        device tensor (obj_ids) or a host sequence of ints, which is range-checked here (the kernel cannot refuse a device id without
+        a host sync: an out-of-range device id gives NaN rows).  -> per_image (n,4) fp64 = PD (m), n_inside, min sd (m), contact;
+        with per_vertex also sd (n,V) fp64 and inside (n,V) uint8."""
+        n, V = verts.shape[:2]
+        assert verts.shape == (n, V, 3) and obj_rt.shape == (n, 3, 4)
+        if not torch.is_tensor(obj_id):
+            ids = [int(i) for i in obj_id]
+            if len(ids) != n or any(i < 0 or i >= len(self.names) for i in ids):
+                raise VphoError(f'HandObjectPenetration: object ids {ids} outside [0, {len(self.names)}) or not one per image')
+            obj_id = _ids_to_device(ids, self.device)
+        assert obj_id.shape == (n,)
+        per = _new((n, 4), obj_rt, torch.float64)
+        sd = _new((n, V), obj_rt, torch.float64)
+        inside = _new((n, V), obj_rt, torch.uint8)
+        _call('vpho_hand_obj_penetration_f64', C.byref(self.c), _f32(verts), I(n), I(V), _f64(obj_rt), _i32(obj_id), C.c_double(contact_thresh),
+              _f64(sd), _u8(inside), _f64(per))
+        return (per, sd, inside) if per_vertex else per
+
+
 # ----------------------------------------------------------------------------------------------- score-network training
 def _at(t, off=0):
     """device address of element `off` of a contiguous fp32 tensor"""

@@ -8,3 +8,13 @@ HAND_METRIC_NAMES = ('MJE', 'PA_MJE', 'MVE', 'PA_MVE')
 MULTI_TABLES = ('one_candidate', 'best_of_S', 'mean_of_S')
 MULTI_COLUMNS = tuple(f'{t}/hand/{k}' for t in MULTI_TABLES for k in HAND_METRIC_NAMES) + \
     tuple(f'{t}/object/{k}' for t in MULTI_TABLES for k in OBJ_METRIC_NAMES)
+# the block that evaluate.metric_rows appends last with eval_physics (after the eval_best block if there is one): penetration and
+# contact (physics_eval) of the aggregated hand vertices with the aggregated object pose ('pred'), then of the
+# ground-truth hand vertices with the ground-truth object pose ('gt', NaN without object ground truth); per image PD (m), the number of
+# hand vertices inside the object, the smallest signed distance (m) and contact (min sd <= cfg.physics_contact_thresh)
+PHYSICS_SOURCES = ('pred', 'gt')
+PHYSICS_METRIC_NAMES = ('PD', 'n_inside', 'min_sd', 'contact')
+PHYSICS_COLUMNS = tuple(f'physics/{s}/{k}' for s in PHYSICS_SOURCES for k in PHYSICS_METRIC_NAMES)
+# the summarize / EVAL_JSON table 'physics', per source: mean PD (mm), largest PD (mm), share of images with a vertex inside (%), mean
+# number of inside vertices, share of images in contact (%)
+PHYSICS_TABLE = ('PD_mm', 'PD_max_mm', 'penetration_rate_pct', 'inside_verts', 'contact_rate_pct')

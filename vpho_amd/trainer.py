@@ -212,12 +212,16 @@ class Trainer:
             seen += n
 
     @torch.no_grad()
-    def eval(self, loader=None, eval_best=None):
+    def eval(self, loader=None, eval_best=None, eval_physics=None):
         """``evaluate(testing_dataloader)`` (train_diff_hand_obj.py:202-357).  ``loader``: see ``_eval_batches``; default synthetic.
         ``eval_best`` (default: cfg.eval_best, the reference's is_eval_best): also score every sampled hypothesis and report the
-        one_candidate, best_of_S and mean_of_S tables (rows of evaluate.ROW_BEST columns)."""
+        one_candidate, best_of_S and mean_of_S tables (rows of evaluate.ROW_BEST columns).  ``eval_physics`` (default:
+        cfg.eval_physics): also report hand-object penetration and contact, the ``physics`` table (evaluate.PHYS more columns, last)."""
         from .configs.args import cfg
         eval_best = bool(cfg.eval_best if eval_best is None else eval_best)
+        eval_physics = bool(cfg.eval_physics if eval_physics is None else eval_physics)
+        if eval_physics:
+            E.physics_meter(self.assets, self.device)          # object meshes and their tables, once, before the timed loop
         rows = []
         t0 = time.perf_counter()
         # three batches in flight (independent images; see evaluate.PipelinedPredictor)
@@ -232,10 +236,10 @@ class Trainer:
                     # synthetic run: batch 0 provides the ground truth (its own regression output), so it is evaluated first
                     out0 = pipe.submit(b).result()
                     gt = (out0['reg_hand_joint'] + b['root_joint'][:, None], out0['reg_hand_vert'] + b['root_joint'][:, None])
-                    rows.append(E.metric_rows(out0, b, gt[0], gt[1], first, self.assets, eval_best))
+                    rows.append(E.metric_rows(out0, b, gt[0], gt[1], first, self.assets, eval_best, eval_physics))
                 else:
                     futs.append(pipe.submit(b, lambda out, batch, eng, first=first, gt=gt: E.metric_rows(out, batch, gt[0], gt[1], first, self.assets,
-                                                                                                    eval_best)))
+                                                                                                    eval_best, eval_physics)))
                 item = gen.send(gt)
         except StopIteration:
             pass
@@ -243,7 +247,7 @@ class Trainer:
         pipe.close()
         # a rank whose shard is empty still takes part in the collective (with zero rows: the ragged gather carries the counts first);
         # raising here would leave the other ranks blocked in their all-gather.  Only an evaluation without ANY image is an error
-        mine = torch.cat(rows, 0) if rows else torch.zeros((0, E.row_width(eval_best)), device=self.device, dtype=torch.float32)
+        mine = torch.cat(rows, 0) if rows else torch.zeros((0, E.row_width(eval_best, eval_physics)), device=self.device, dtype=torch.float32)
         rows = E.gather_rows(mine)
         if rows.shape[0] == 0:
             raise ValueError('Trainer.eval: the loader yielded no batch on any rank')
@@ -254,13 +258,16 @@ class Trainer:
             print(f'evaluated {rows.shape[0]} {what} on {self.world} GPU(s) in {dt:.2f} s ({rows.shape[0] / dt:.1f} images/s)')
             table = E.summarize(rows.cpu())
             for name, r in table.items():
-                if name not in ('object',) + E.MULTI_TABLES:
+                if name not in ('object', 'physics') + E.MULTI_TABLES:
                     print(f'{name:>5s}: n={r["n"]:5d}  MJE reg {r["MJE_reg"]:.2f}  first {r["MJE_first"]:.2f}  agg {r["MJE_agg"]:.2f}  MVE agg {r["MVE_agg"]:.2f}  (mm)')
             print('object (aggregated pose): ' + '  '.join(f'{k} {v:.2f}' for k, v in table['object'].items()))
             for name in E.MULTI_TABLES:
                 if name in table:
                     print(f'{name} hand (mm): ' + '  '.join(f'{k} {v:.2f}' for k, v in table[name]['hand'].items()))
                     print(f'{name} object: ' + '  '.join(f'{k} {v:.2f}' for k, v in table[name]['object'].items()))
+            if 'physics' in table:
+                for src, r in table['physics'].items():
+                    print(f'physics {src}: ' + '  '.join(f'{k} {v:.2f}' for k, v in r.items()))
             import json
             print('EVAL_JSON ' + json.dumps({'images': int(rows.shape[0]), 'world': self.world, 'table': table}))
         if self.world > 1:
