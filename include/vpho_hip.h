@@ -401,6 +401,30 @@ VPHO_API int vpho_hand_phys_score_f32(const float* force_point, const float* for
                              int bs, int n_cand, float* finger_score, void* stream);
 VPHO_API int vpho_hand_phys_fuse_f32(const float* cand, int n_cand, const int* idx, int bs, int k, float* out, void* stream);
 
+/* The ablation aggregators (--aggregation_mode_hand / --aggregation_mode_obj other than heatmap_cascade), appended
+ * within ABI version 13.  The object side fuses with vpho_obj_fuse_f64 (NULL weights).
+ * vpho_heatmap_peak_f32 (aggregation.py:313-323, :1025-1035): per map of heatmap [n_maps][H][W] the arg-max in torch.argmax's order
+ * (first maximum; a NaN is a maximum), as the pair the reference reads from its transposed grid: peak [n_maps][2] =
+ * (X[ind / W], X[ind % W]), X[i] = i / (W - 1) * 2 - 1; ind [n_maps] (optional) the flat index.  H == W is required. */
+VPHO_API int vpho_heatmap_peak_f32(const float* heatmap, long long n_maps, int H, int W, float* peak, int* ind, void* stream);
+/* select_by_2D_pt score of the hand (aggregation.py:303-327): joints [bs][C][21][3] root-relative (vpho_mano_fk_f32), peak [bs][21][2];
+ * score [bs][C][21] = -distance of each projected joint to its map's peak in the bbox's (-1, 1) frame (per_joint != 0, the layout
+ * vpho_topk_f32 takes with F = 21) or its sum over the joints [bs][C]; fp32 */
+VPHO_API int vpho_hand_pt2d_score_f32(const float* joints, const float* root, const float* Kmat, const float* bbox, const float* peak,
+                             int bs, int C, int per_joint, float* score, void* stream);
+/* the same for the object's key-points (aggregation.py:1015-1039): pose [bs][n][9] fp64, peak [bs][t->n_kpt][2]; score [bs][n], the
+ * chain in fp64 like vpho_obj_heat_score; an obj_id outside [0, n_obj) gives NaN scores */
+VPHO_API int vpho_obj_pt2d_score(const double* pose, int n, const float* root, const vpho_obj_tables* t, const int* obj_id,
+                        const unsigned char* is_right, const float* Kmat, const float* bbox, const float* peak, int bs,
+                        float* score, void* stream);
+/* quaternion mean of WHOLE hand poses (aggregation.py:221-233 with all 48 parameters, :331-336, :401-405): pose rows of ld_pose
+ * floats (first 48 = axis-angle), C per image; idx [bs][n] (NULL: candidates 0 .. n-1), w [bs][n] (NULL: unweighted);
+ * fused [bs][48].  n <= 2 C.  An index outside [0, C) is not read: that image's row is NaN. */
+VPHO_API int vpho_hand_pose_fuse_f32(const float* pose, int ld_pose, int C, const int* idx, const float* w, int bs, int n, float* fused,
+                            void* stream);
+/* 2D_pt_joint (aggregation.py:357-362): fused [bs][21][3] = mean over idx [bs][21][k] (vpho_topk_f32, F = 21) of joints [bs][C][21][3] */
+VPHO_API int vpho_hand_joint_gather_mean_f32(const float* joints, const int* idx, int bs, int C, int k, float* fused, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Evaluation metrics on the device: TesterHand.criterion_MJE_PAMJE (lib/engine/test.py:657-680) with
  * rigid_align_AtoB (lib/utils/transform_fn.py:43-66).  pd, gt: [n_img][n_pts][3] fp32 (metres); outputs per image the

@@ -8,6 +8,11 @@ import argparse
 import sys
 
 
+# lib/configs/args.py:235-245 (the object side offers no `2D_pt_joint`)
+AGGREGATION_MODES_HAND = ('heatmap_cascade', 'heatmap', '2D_pt_pose', '2D_pt_joint', 'average_all', 'random')
+AGGREGATION_MODES_OBJ = ('heatmap_cascade', 'heatmap', '2D_pt_pose', 'average_all', 'random')
+
+
 class Config:
     def __init__(self):
         self.mode = 'train'
@@ -37,6 +42,10 @@ class Config:
         self.sample_num = 50
         self.topk_hand = 15
         self.topk_obj = 5
+        # how the S hypotheses become one answer: the visual-physical cascade, or one of the reference's ablation baselines
+        self.aggregation_mode_hand = 'heatmap_cascade'
+        self.aggregation_mode_obj = 'heatmap_cascade'
+        self.do_weighted_average = True   # is_weight of the hand's `heatmap` mode only (the cascade is always weighted)
         self.asset_root = 'asset'
         self.base_learning_rate = 2e-4
         self.gradient_clip = -1.0
@@ -86,6 +95,9 @@ def _parser():
     p.add_argument('--sample_num', type=int, default=50)
     p.add_argument('--topk_hand', type=int, default=15)
     p.add_argument('--topk_obj', type=int, default=5)
+    p.add_argument('--do_weighted_average', action='store_false')          # the reference's spelling (args.py:233): the flag turns it OFF
+    p.add_argument('--aggregation_mode_hand', type=str, default='heatmap_cascade', choices=list(AGGREGATION_MODES_HAND))
+    p.add_argument('--aggregation_mode_obj', type=str, default='heatmap_cascade', choices=list(AGGREGATION_MODES_OBJ))
     p.add_argument('--asset_root', type=str, default='asset')
     p.add_argument('--base_learning_rate', type=float, default=2e-4)
     p.add_argument('--gradient_clip', type=float, default=-1.)

@@ -167,6 +167,13 @@ def metric_rows(out, data, gt_joint, gt_vert, first_index, assets=None, eval_bes
         if assets is None:
             raise ValueError('metric_rows: eval_physics needs the asset tables (object meshes)')
         rows[:, -PHYS:] = physics_block(pp, out, data, gt_vert, physics_meter(assets, gt_joint.device))
+    from .configs.args import cfg
+    if cfg.aggregation_mode_hand == '2D_pt_joint':
+        # that mode fuses joints only; its vertices are the reference's all-zero mesh (aggregation.py:364-366): no vertex metric of it
+        rows[:, 4] = float('nan')
+        rows[:, 10] = float('nan')
+        if eval_physics:
+            rows[:, -PHYS:-PHYS + 4] = float('nan')
     return rows
 
 

@@ -9,11 +9,12 @@ import os
 import torch
 
 from .. import ops
-from ..configs.args import cfg
+from ..configs.args import cfg, AGGREGATION_MODES_HAND, AGGREGATION_MODES_OBJ
 from . import pack as P
 
 MANO_JOINT_LEVEL = {0: [0], 1: [1, 5, 9, 13, 17], 2: [2, 6, 10, 14, 18], 3: [3, 7, 11, 15, 19], 4: [4, 8, 12, 16, 20]}
 PHY_TOPK = 5          # aggregation.py:1246
+DEFAULT_MODE = 'heatmap_cascade'
 
 
 def _signature(model):
@@ -509,20 +510,125 @@ class Engine:
         f['mano_ctx'] = (t['f_ctx_v'], t['f_ctx_j'])
         data = {k: t['d_' + k] for k in self._AGG_D}
         S = t['obj_pose'].shape[1]
-        return self.aggregate(f, data, t['final58'], t['obj_pose'], S, self._agg_k[0], self._agg_k[1], oid=t['oid'])
+        k_hand, k_obj, mode_hand, mode_obj, weighted = self._agg_k
+        return self.aggregate(f, data, t['final58'], t['obj_pose'], S, k_hand, k_obj, oid=t['oid'], mode_hand=mode_hand, mode_obj=mode_obj,
+                              weighted=weighted)
 
-    def aggregate_graphed(self, f, data, final58, obj_pose, S, k_hand, k_obj):
+    def aggregate_graphed(self, f, data, final58, obj_pose, S, k_hand, k_obj, mode_hand=DEFAULT_MODE, mode_obj=DEFAULT_MODE, weighted=True):
+        self._check_modes(f, S, k_hand, k_obj, mode_hand, mode_obj)          # before anything is captured
         t = {'f_' + k: f[k] for k in self._AGG_F}
         t['f_ctx_v'], t['f_ctx_j'] = f['mano_ctx']
         t.update({'d_' + k: data[k] for k in self._AGG_D})
         t.update(final58=final58, obj_pose=obj_pose, oid=self.agg.obj_ids(data['obj_name']))
-        self._agg_k = (k_hand, k_obj)
-        return self._aggregate_graph(t, (k_hand, k_obj, self.keep_states))
+        self._agg_k = (k_hand, k_obj, mode_hand, mode_obj, bool(weighted))
+        return self._aggregate_graph(t, (k_hand, k_obj, self.keep_states, mode_hand, mode_obj, bool(weighted)))
 
-    def aggregate(self, f, data, final58, obj_pose, S, k_hand, k_obj, oid=None):
-        """aggregation.py:1167-1353.  final58 (bs*S,58) f32, obj_pose (bs,S,9) f64."""
+    @staticmethod
+    def _check_modes(f, S, k_hand, k_obj, mode_hand, mode_obj):
+        """the limits of the modes other than the cascade, as messages instead of a kernel's argument check"""
+        if mode_hand not in AGGREGATION_MODES_HAND:
+            raise ops.VphoError(f'aggregation_mode_hand {mode_hand!r}: one of {AGGREGATION_MODES_HAND}')
+        if mode_obj not in AGGREGATION_MODES_OBJ:
+            raise ops.VphoError(f'aggregation_mode_obj {mode_obj!r}: one of {AGGREGATION_MODES_OBJ}')
+        if mode_hand != DEFAULT_MODE and k_hand > S:
+            raise ops.VphoError(f'aggregation_mode_hand {mode_hand}: topk_hand = {k_hand} exceeds sample_num = {S} (only the cascade adds the '
+                                f'regression candidates)')
+        if mode_obj != DEFAULT_MODE and k_obj > S:
+            raise ops.VphoError(f'aggregation_mode_obj {mode_obj}: topk_obj = {k_obj} exceeds sample_num = {S}')
+        for side, mode in (('hand', mode_hand), ('obj', mode_obj)):
+            H, W = f[f'{side}_heatmap'].shape[-2:]
+            if mode.startswith('2D_pt') and H != W:
+                raise ops.VphoError(f'aggregation_mode_{side} {mode}: the heat maps must be square (got {H} x {W}); the reference reads the '
+                                    f'peak through a transposed grid that is only defined for H = W')
+
+    def _aggregate_hand_mode(self, mode, f, final58, root_flip, Kmat, bb_h, S, k, weighted):
+        """HandAggregator.__call__ in a mode other than the cascade (aggregation.py:82-113,286-467) on the S diffusion candidates.
+        -> (mano (bs,58), vert, joint), info (selected indices / scores / peaks of the mode)"""
+        A, M = self.agg, self.mano
+        bs = final58.shape[0] // S
+        ctx = f['mano_ctx']
+        cand = final58.view(bs, S, 58)
+        info = {}
+        if mode in ('heatmap', '2D_pt_pose', '2D_pt_joint'):
+            _, joints = M.fk(final58, ctx, S, False)
+            joints = joints.view(bs, S, 21, 3)
+        if mode == 'heatmap':
+            hv = A.hand_heat(joints, root_flip, Kmat, bb_h, f['hand_heatmap'], list(range(21)))
+            # level 0 of the cascade IS "sum over the observed joints, top-k" (aggregation.py:215-218); the wrist it fuses lands in a scratch copy
+            val, idx, _, score = A.hand_fuse_level(hv, cand[:, :, :48].contiguous(), k, 0, want_scores=True)
+            val, idx = val.view(bs, k), idx.view(bs, k)
+            w = A.topk_weights(val) if weighted else None
+            pose48 = A.hand_pose_fuse(cand, idx, w)
+            info.update(topk=idx, val=val, score=score.view(bs, S), weight=w)
+        elif mode == '2D_pt_pose':
+            peak, ind = A.heatmap_peak(f['hand_heatmap'])
+            score = A.hand_pt2d_score(joints, root_flip, Kmat, bb_h, peak)
+            val, idx = A.topk(score, k)
+            val, idx = val.view(bs, k), idx.view(bs, k)
+            pose48 = A.hand_pose_fuse(cand, idx, None)
+            info.update(topk=idx, val=val, score=score, peak=peak, peak_index=ind)
+        elif mode == '2D_pt_joint':
+            peak, ind = A.heatmap_peak(f['hand_heatmap'])
+            score = A.hand_pt2d_score(joints, root_flip, Kmat, bb_h, peak, per_joint=True)
+            val, idx = A.topk(score, k, 21)                                            # (bs,21,k): top-k PER JOINT
+            joint = A.hand_joint_gather_mean(joints, idx)
+            info.update(topk=idx, val=val, score=score, peak=peak, peak_index=ind)
+            # no pose comes out of this mode: the reference returns zeros for the parameters and the vertices (aggregation.py:364-366)
+            return (torch.zeros((bs, 58), device=self.dev), torch.zeros((bs, 778, 3), device=self.dev), joint), info
+        elif mode == 'average_all':
+            pose48 = A.hand_pose_fuse(cand, None, None, n=S)
+        else:                                                                          # 'random': candidate 0 as it stands
+            pose48 = cand[:, 0, :48]
+        mano = torch.cat([pose48, cand[:, 0, 48:]], -1).contiguous()                   # candidate 0's shape row
+        vert, joint = M.fk(mano, ctx, 1, True)
+        return (mano, vert, joint), info
+
+    def _aggregate_obj_mode(self, mode, f, obj_pose, root, oid, isr, Kmat, bb_or, k):
+        """ObjectAggregator.__call__ in a mode other than the cascade (aggregation.py:646-659,1001-1112): unweighted fuse_topk of
+        the heat-map / 2-D point top-k, of the FIRST k candidates (`average_all`, as the reference) or of candidate 0 (`random`)"""
+        A = self.agg
+        bs = obj_pose.shape[0]
+        info = {}
+        if mode == 'heatmap':
+            score = A.obj_heat_score(obj_pose, root, oid, isr, Kmat, bb_or, f['obj_heatmap'])
+            val, idx = A.topk(score, k)
+            info.update(val=val.view(bs, k), score=score)
+        elif mode == '2D_pt_pose':
+            peak, ind = A.heatmap_peak(f['obj_heatmap'])
+            score = A.obj_pt2d_score(obj_pose, root, oid, isr, Kmat, bb_or, peak)
+            val, idx = A.topk(score, k)
+            info.update(val=val.view(bs, k), score=score, peak=peak, peak_index=ind)
+        else:
+            n = k if mode == 'average_all' else 1
+            idx = torch.arange(n, device=self.dev, dtype=torch.int32).repeat(bs, 1)
+        idx = idx.view(bs, -1).contiguous()
+        info['topk'] = idx
+        return A.obj_fuse(obj_pose, idx, None), info
+
+    def aggregate(self, f, data, final58, obj_pose, S, k_hand, k_obj, oid=None, mode_hand=DEFAULT_MODE, mode_obj=DEFAULT_MODE, weighted=True):
+        """aggregation.py:1167-1353.  final58 (bs*S,58) f32, obj_pose (bs,S,9) f64.  A side whose mode is not `heatmap_cascade` gets the
+        answer of the reference's aggregator of that name instead (INTEGRATION.md §1) and takes no part in the pseudo-force steps;
+        the other side still reports the default chain's result.  ``weighted``: is_weight of the hand's `heatmap` mode."""
+        self._check_modes(f, S, k_hand, k_obj, mode_hand, mode_obj)
         A, M = self.agg, self.mano
         bs = obj_pose.shape[0]
+        if mode_hand != DEFAULT_MODE or mode_obj != DEFAULT_MODE:
+            f32 = lambda k: data[k].float().contiguous()
+            Kmat = f32('cam_intr_crop_flip').view(bs, 9)
+            res, dbg = {}, {}
+            if mode_hand == DEFAULT_MODE or mode_obj == DEFAULT_MODE:                  # the side still in the cascade: today's chain, whole
+                res, dbg = self.aggregate(f, data, final58, obj_pose, S, k_hand, k_obj, oid=oid)
+            dbg.update(mode_hand=mode_hand, mode_obj=mode_obj)
+            if mode_hand != DEFAULT_MODE:
+                (mano, vert, joint), dbg['hand_mode'] = self._aggregate_hand_mode(mode_hand, f, final58, f32('root_joint_flip'), Kmat, f32('bbox_hand'),
+                                                                                  S, k_hand, weighted)
+                res.update(hand_agg_mano=mano, hand_agg_vert=vert, hand_agg_joint=joint)
+            if mode_obj != DEFAULT_MODE:
+                oid = A.obj_ids(data['obj_name']) if oid is None else oid
+                isr = data['is_right'].to(torch.uint8).contiguous()
+                res['obj_agg_6d'], dbg['obj_mode'] = self._aggregate_obj_mode(mode_obj, f, obj_pose, f32('root_joint'), oid, isr, Kmat,
+                                                                              f32('bbox_obj_rect'), k_obj)
+            return res, dbg
         f32 = lambda k: data[k].float().contiguous()
         root_flip, root, Kmat = f32('root_joint_flip'), f32('root_joint'), f32('cam_intr_crop_flip').view(bs, 9)
         bb_h, bb_or = f32('bbox_hand'), f32('bbox_obj_rect')
@@ -581,8 +687,11 @@ class Engine:
 
     # ------------------------------------------------------------------------------------------------ whole path
     @torch.no_grad()
-    def predict(self, data, noise_hand=None, noise_obj=None):
+    def predict(self, data, noise_hand=None, noise_obj=None, mode_hand=None, mode_obj=None):
+        """``mode_hand`` / ``mode_obj``: the aggregation modes (default: cfg.aggregation_mode_hand / _obj, read at call time)"""
         S, T0, steps = cfg.sample_num, cfg.sample_T0, cfg.sampling_steps
+        modes = dict(mode_hand=cfg.aggregation_mode_hand if mode_hand is None else mode_hand,
+                     mode_obj=cfg.aggregation_mode_obj if mode_obj is None else mode_obj, weighted=bool(cfg.do_weighted_average))
         with torch.cuda.device(self.dev):
             if self.use_graphs:
                 f = self._features_graph({k: v for k, v in data.items() if torch.is_tensor(v)}, (cfg.roi_size, cfg.heatmap_size, self.conv_terms, self.roi_window, self.feature_streams, self.winograd, self.fpn_fuse, self.down_fuse))
@@ -641,9 +750,9 @@ class Engine:
                     print("\033[31mWarning: NaN detected in score evaluation. \033[0m")
             x_o9 = out['diff_final_obj_6d']
             if self.use_graphs:
-                agg, dbg = self.aggregate_graphed(f, data, final, x_o9, S, cfg.topk_hand, cfg.topk_obj)
+                agg, dbg = self.aggregate_graphed(f, data, final, x_o9, S, cfg.topk_hand, cfg.topk_obj, **modes)
             else:
-                agg, dbg = self.aggregate(f, data, final, x_o9, S, cfg.topk_hand, cfg.topk_obj)
+                agg, dbg = self.aggregate(f, data, final, x_o9, S, cfg.topk_hand, cfg.topk_obj, **modes)
             out['agg_obj_6d'] = keep(agg['obj_agg_6d'])
             out['agg_hand_mano'] = keep(agg['hand_agg_mano'])
             out['agg_hand_vert'] = keep(agg['hand_agg_vert'])

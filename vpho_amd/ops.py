@@ -999,6 +999,44 @@ class Aggregation:
         _call('vpho_hand_phys_fuse_f32', _f32(cand), I(n_cand), _i32(idx), I(bs), I(idx.shape[-1]), _f32(out))
         return out
 
+    # ---- the ablation aggregators (aggregation modes other than heatmap_cascade; csrc/aggregate_modes.hip)
+    def heatmap_peak(self, heatmap):
+        """heatmap (bs,J,H,W) -> peak (bs,J,2) in the reference's transposed (-1, 1) grid, flat arg-max index (bs,J) int32"""
+        bs, J, H, W = heatmap.shape
+        peak, ind = _new((bs, J, 2), heatmap), _new((bs, J), heatmap, torch.int32)
+        _call('vpho_heatmap_peak_f32', _f32(heatmap), LL(bs * J), I(H), I(W), _f32(peak), _i32(ind))
+        return peak, ind
+
+    def hand_pt2d_score(self, joints, root, K, bbox, peak, per_joint=False):
+        """joints (bs,C,21,3), peak (bs,21,2) -> (bs,C) or, per_joint, (bs,C,21)"""
+        bs, Cn = joints.shape[:2]
+        score = _new((bs, Cn, 21) if per_joint else (bs, Cn), joints)
+        _call('vpho_hand_pt2d_score_f32', _f32(joints), _f32(root), _f32(K), _f32(bbox), _f32(peak), I(bs), I(Cn), I(int(per_joint)), _f32(score))
+        return score
+
+    def obj_pt2d_score(self, pose, root, obj_id, is_right, K, bbox, peak):
+        bs, n = pose.shape[:2]
+        assert peak.shape[1] == self.obj.n_kpt
+        score = _new((bs, n), root)
+        _call('vpho_obj_pt2d_score', _f64(pose), I(n), _f32(root), C.byref(self.obj), _i32(obj_id), _u8(is_right), _f32(K), _f32(bbox), _f32(peak),
+              I(bs), _f32(score))
+        return score
+
+    def hand_pose_fuse(self, pose, idx=None, w=None, n=None):
+        """pose (bs,C,>=48) rows; idx / w (bs,n) or None (candidates 0 .. n-1 / unweighted) -> fused axis-angle (bs,48)"""
+        bs, Cn, ld = pose.shape
+        n = idx.shape[-1] if idx is not None else (Cn if n is None else n)
+        fused = _new((bs, 48), pose)
+        _call('vpho_hand_pose_fuse_f32', _f32(pose), I(ld), I(Cn), None if idx is None else _i32(idx), _f32(w), I(bs), I(n), _f32(fused))
+        return fused
+
+    def hand_joint_gather_mean(self, joints, idx):
+        """joints (bs,C,21,3), idx (bs,21,k) -> (bs,21,3)"""
+        bs, Cn = joints.shape[:2]
+        fused = _new((bs, 21, 3), joints)
+        _call('vpho_hand_joint_gather_mean_f32', _f32(joints), _i32(idx), I(bs), I(Cn), I(idx.shape[-1]), _f32(fused))
+        return fused
+
 
 # ----------------------------------------------------------------------------------------------- metrics
 def hand_metrics(pd, gt, per_point=False):

@@ -256,6 +256,7 @@ class Trainer:
         if self.rank == 0:
             what = 'synthetic images' if loader is None else 'images'
             print(f'evaluated {rows.shape[0]} {what} on {self.world} GPU(s) in {dt:.2f} s ({rows.shape[0] / dt:.1f} images/s)')
+            print(f'aggregation_mode_hand {cfg.aggregation_mode_hand}  aggregation_mode_obj {cfg.aggregation_mode_obj}')
             table = E.summarize(rows.cpu())
             for name, r in table.items():
                 if name not in ('object', 'physics') + E.MULTI_TABLES:
@@ -269,7 +270,8 @@ class Trainer:
                 for src, r in table['physics'].items():
                     print(f'physics {src}: ' + '  '.join(f'{k} {v:.2f}' for k, v in r.items()))
             import json
-            print('EVAL_JSON ' + json.dumps({'images': int(rows.shape[0]), 'world': self.world, 'table': table}))
+            print('EVAL_JSON ' + json.dumps({'images': int(rows.shape[0]), 'world': self.world, 'aggregation_mode_hand': cfg.aggregation_mode_hand,
+                                             'aggregation_mode_obj': cfg.aggregation_mode_obj, 'table': table}))
         if self.world > 1:
             dist.barrier()
         return rows
