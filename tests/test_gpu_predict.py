@@ -217,8 +217,9 @@ def test_device_prior_switch_is_seeded_and_off_by_default(model_cpu, assets):
 @pytest.mark.parametrize('bs,roi_window', [(5, '1'), (8, '0'), (64, '1')])
 def test_grouped_twin_branches_are_bit_identical_to_one_launch_per_branch(model_contrast_cpu, assets, bs, roi_window):
     """round 6 (vpho_conv_desc.groups): hand | object layer2 / layer3, the FPN top layer and coarse laterals, the heat-map heads and both
-    encoders run as ONE grouped launch each (Engine._features_grouped).  Every output element keeps its k order, so the whole feature path
-    -- heat-maps, encodings, the cross modules' stage inputs, the regression head, the forces -- equals the per-branch plan bit for bit."""
+    encoders run as ONE grouped launch each (Engine._twin_grouped).  Every output element keeps its k order, so the whole feature path
+    -- heat-maps, encodings, the cross modules' stage inputs, the regression head, the forces -- equals the per-branch plan
+    (Engine._twin_per_branch) bit for bit, and Engine.features returns the same keys, shapes and types from both."""
     import copy
     import os
     from vpho_amd.model.engine import Engine
@@ -243,6 +244,11 @@ def test_grouped_twin_branches_are_bit_identical_to_one_launch_per_branch(model_
               'tok_hand', 'tok_obj', 'force_local', 'hf_hr', 'hm_hand_nhwc', 'hm_obj_nhwc'):
         a, b = feats['0'][k], feats['1'][k]
         assert a.shape == b.shape and torch.equal(a, b), (k, float((a - b).abs().max()))
-    # the encoder inputs: 277 / 283 channels of data; the grouped plan pads both to 284 (the per-branch plan 280 / 284)
-    assert torch.equal(feats['0']['enc_in_hand'][..., :277], feats['1']['enc_in_hand'][..., :277]) and float(feats['1']['enc_in_hand'][..., 277:].abs().max()) == 0.0
-    assert torch.equal(feats['0']['enc_in_obj'], feats['1']['enc_in_obj'])
+    # both plans return the same tensors under the same names, shapes and types
+    assert feats['0'].keys() == feats['1'].keys()
+    for k in feats['0']:
+        assert feats['0'][k].shape == feats['1'][k].shape and feats['0'][k].dtype == feats['1'][k].dtype, k
+    # the encoder inputs: 277 / 283 channels of data, padded to 280 / 284 (the grouped plan's hand input is a view of a 284-wide buffer)
+    for k in ('enc_in_hand', 'enc_in_obj'):
+        assert torch.equal(feats['0'][k], feats['1'][k]), k
+    assert float(feats['1']['enc_in_hand'][..., 277:].abs().max()) == 0.0

@@ -27,6 +27,21 @@ def _signature(model):
     return v, p, str(next(model.parameters()).device)
 
 
+def _stack2(a, b):
+    """The packed weights of two branches of one shape as ONE grouped set (vpho_conv_desc.groups): the same structure with the
+    tensors stacked (2, ...); plain values (strides, paddings, padded widths) must agree."""
+    if torch.is_tensor(a):
+        return torch.stack([a, b]).contiguous()
+    if isinstance(a, dict):
+        assert a.keys() == b.keys()
+        return {k: _stack2(a[k], b[k]) for k in a}
+    if isinstance(a, (list, tuple)):
+        assert len(a) == len(b)
+        return type(a)(_stack2(u, v) for u, v in zip(a, b))
+    assert a == b, (a, b)
+    return a
+
+
 class Engine:
     def __init__(self, model):
         dev = next(model.parameters()).device
@@ -92,29 +107,12 @@ class Engine:
         # cascade's regression copies inherit, amplified by the 6-D normalisation (VPHO_HEAD_F64=0: the fp32-MFMA GEMM kernel; A/B aid)
         self.head64 = os.environ.get('VPHO_HEAD_F64', '1') != '0'
         if self.grouped:
-            pair = lambda a, b: (torch.stack([a[0], b[0]]).contiguous(), torch.stack([a[1], b[1]]).contiguous())
-
-            def pair_blocks(name_h, name_o):
-                out = []
-                for bh, bo in zip(self.layers[name_h], self.layers[name_o]):
-                    blk = dict(c1=pair(bh['c1'], bo['c1']), c2=pair(bh['c2'], bo['c2']), c3=pair(bh['c3'], bo['c3']), stride=bh['stride'], down=None)
-                    if bh['down'] is not None:
-                        blk['down'] = pair(bh['down'], bo['down'])
-                        blk['c3_down'] = pair(bh['c3_down'], bo['c3_down'])
-                    out.append(blk)
-                return out
-
-            self.g_layers = dict(layer2=pair_blocks('layer2_h', 'layer2_o'), layer3=pair_blocks('layer3_h', 'layer3_o'))
-            self.g_fpn = {k: pair(self.fpn[k + '_h'], self.fpn[k + '_o']) for k in ('toplayer', 'latlayer1', 'latlayer2')}
-            hh, ho = self.hm['hand'], self.hm['obj']
-            self.g_hm = dict(c0=pair(hh['c0'], ho['c0']), c1=pair(hh['c1'], ho['c1']), deconv_b=torch.stack([hh['deconv_b'], ho['deconv_b']]).contiguous(),
-                             deconv={k: (torch.stack([hh['deconv'][k][0], ho['deconv'][k][0]]).contiguous(), hh['deconv'][k][1], hh['deconv'][k][2]) for k in hh['deconv']})
-            e2 = dict(hand=encoder('encoder_hand', 283), obj=self.enc['obj'])          # the hand encoder's 277 inputs padded to 284 like the object's 283
-            assert e2['hand']['cin_pad'] == e2['obj']['cin_pad']
-            self.g_enc = dict(project=pair(e2['hand']['project'], e2['obj']['project']), cin_pad=e2['obj']['cin_pad'],
-                              blocks=[dict(pre=(torch.stack([a['pre'][0], b['pre'][0]]).contiguous(), torch.stack([a['pre'][1], b['pre'][1]]).contiguous()),
-                                           c1=pair(a['c1'], b['c1']), c2=pair(a['c2'], b['c2']), c3=pair(a['c3'], b['c3']))
-                                      for a, b in zip(e2['hand']['blocks'], e2['obj']['blocks'])])
+            L, F = self.layers, self.fpn
+            self.g_layers = dict(layer2=_stack2(L['layer2_h'], L['layer2_o']), layer3=_stack2(L['layer3_h'], L['layer3_o']))
+            self.g_fpn = {k: _stack2(F[k + '_h'], F[k + '_o']) for k in ('toplayer', 'latlayer1', 'latlayer2')}
+            self.g_hm = _stack2(*({k: v for k, v in self.hm[s].items() if k != 'final'} for s in ('hand', 'obj')))
+            # the hand encoder's 277 inputs padded to 284 like the object's 283 (_stack2 asserts the equal cin_pad)
+            self.g_enc = _stack2(encoder('encoder_hand', 283), self.enc['obj'])
 
         lin = lambda p: (d(sd[p + '.weight']), d(sd[p + '.bias']))
         self.head_mano = dict(l0=lin('head_mano.base_layer.0'), l2=lin('head_mano.base_layer.2'), pose=lin('head_mano.fc_pose'),
@@ -174,6 +172,7 @@ class Engine:
         # of the selection chain is given (tests / bench parity block)
         self.keep_states = False
         self._feat_side = None
+        self._two_streams = False               # set by features(): the per-branch plan with VPHO_FEATURE_STREAMS=2
         from .graphs import GraphedCall
         self._features_graph = GraphedCall(self.features, dev)
         self._aggregate_graph = GraphedCall(self._aggregate_from_tensors, dev)
@@ -182,44 +181,36 @@ class Engine:
         return _signature(model) != self.sig
 
     # ------------------------------------------------------------------------------------------------ feature path
-    def _bottleneck(self, x, b, out=None):
-        y = ops.conv2d_nhwc(x, *b['c1'], out_slope=0.01)
+    # The blocks below run one branch (groups=1, the packed weights of self.layers / fpn / hm / enc) or the twin branches at once
+    # (two groups, the stacked weights of self.g_*): the tensors then hold the hand images [0, N) and the object images [N, 2N), and
+    # ``x_shared`` says that the input is still ONE (N, ...) tensor that both groups read
+    def _bottleneck(self, x, b, out=None, groups=1, x_shared=False):
+        y = ops.conv2d_nhwc(x, *b['c1'], out_slope=0.01, groups=groups, x_shared=x_shared)
         if b['stride'] == 1:
-            y = ops.conv3x3(y, *b['c2'], out_slope=0.01, winograd=self.winograd)
+            y = ops.conv3x3(y, *b['c2'], out_slope=0.01, winograd=self.winograd, groups=groups)
         else:
-            y = ops.conv2d_nhwc(y, *b['c2'], kh=3, kw=3, stride=b['stride'], pad=1, out_slope=0.01)
+            y = ops.conv2d_nhwc(y, *b['c2'], kh=3, kw=3, stride=b['stride'], pad=1, out_slope=0.01, groups=groups)
         if b['down'] is not None and self.down_fuse and x.shape[-1] % 32 == 0 and y.shape[-1] % 32 == 0:
             # the first block of a stage: its projection shortcut (1x1 convolution + BatchNorm of the block input, stride 1 or 2) rides in
             # conv3 as a second input: one launch, and the 4C-wide shortcut map is neither written nor re-read
-            return ops.conv2d_nhwc(y, *b['c3_down'], x2=x, stride2=b['stride'], out_slope=0.01, out=out)
-        r = x if b['down'] is None else ops.conv2d_nhwc(x, *b['down'], stride=b['stride'])
-        return ops.conv2d_nhwc(y, *b['c3'], res=r, out_slope=0.01, out=out)
+            return ops.conv2d_nhwc(y, *b['c3_down'], x2=x, stride2=b['stride'], out_slope=0.01, out=out, groups=groups, x2_shared=x_shared)
+        r = x if b['down'] is None else ops.conv2d_nhwc(x, *b['down'], stride=b['stride'], groups=groups, x_shared=x_shared)
+        return ops.conv2d_nhwc(y, *b['c3'], res=r, out_slope=0.01, out=out, groups=groups)
 
-    def _layer(self, x, name, out=None):
+    def _layer(self, x, blocks, out=None, groups=1, x_shared=False):
         """``out``: where the layer's LAST block writes its result (a slice of a larger buffer)"""
-        blocks = self.layers[name]
         for i, b in enumerate(blocks):
-            x = self._bottleneck(x, b, out if i == len(blocks) - 1 else None)
+            x = self._bottleneck(x, b, out if i == len(blocks) - 1 else None, groups, x_shared and i == 0)
         return x
-
-    def _fpn(self, rgb, windows=None):
-        """FPN.forward.  ``windows`` = {'h': (RoiWindows, the same dilated by 1), 'o': ...}: the two stride-4 outputs are produced
-        only on the pixels the RoIAligns read, as compact (rows, 256) matrices (vpho_roi_windows_i32); the lateral convolution and
-        the top-down add of that level run on the dilated windows."""
-        tr = self._fpn_trunk(rgb)
-        with self._side():
-            obj = self._fpn_branch('o', tr, windows)
-        hand = self._fpn_branch('h', tr, windows)
-        self._join()
-        return [hand, obj]
 
     # The hand and the object branch are independent between the shared stem / layer1 and the shared layer4, and again from the
     # top-down path to the cross modules.  With VPHO_FEATURE_STREAMS=2 the object branch is issued on a second stream (a parallel
     # branch of the captured HIP graph), so the many sub-chip launches of the two branches (16 x 16 and 8 x 8 maps, 32 x 32 RoI
-    # crops) overlap instead of queueing; same kernels, same results.
+    # crops) overlap instead of queueing; same kernels, same results.  Only the per-branch plan has a side stream: while the
+    # grouped plan runs (self._two_streams is False) both calls do nothing, also in the tail the two plans share.
     def _side(self):
         import contextlib
-        if self.feature_streams < 2:
+        if not self._two_streams:
             return contextlib.nullcontext()
         if self._feat_side is None:
             self._feat_side = torch.cuda.Stream(self.dev)
@@ -227,59 +218,55 @@ class Engine:
         return torch.cuda.stream(self._feat_side)
 
     def _join(self):
-        if self.feature_streams >= 2 and self._feat_side is not None:
+        if self._two_streams:
             torch.cuda.current_stream().wait_stream(self._feat_side)
 
-    def _fpn_trunk(self, rgb):
+    def _stem(self, rgb):
+        """the part of the backbone that both branches share: stem and layer1 -> c2 (N,64,64,256)"""
         x = ops.nchw_to_nhwc(rgb, 4)
         c1 = ops.maxpool_nhwc(ops.conv2d_nhwc(x, *self.stem, kh=7, kw=7, stride=2, pad=3, out_slope=0.01), 3, 2, 1)
-        c2 = self._layer(c1, 'layer1_h')
-        # shared layer4 (quirk Q6): both branches go through the same weights, so they run as ONE batch of 2N images
-        # (twice the tiles per launch at 8x8 resolution, half the launches); convolutions are per-image, results unchanged.  The two
-        # layer3 stacks write their last block straight into the halves of that batch: no concatenation copy
-        n = c2.shape[0]
-        c4 = torch.empty((2 * n, c2.shape[1] // 4, c2.shape[2] // 4, self.layers['layer3_h'][-1]['c3'][0].shape[0]), device=c2.device)
-        with self._side():
-            c3o = self._layer(c2, 'layer2_o')
-            c4o = self._layer(c3o, 'layer3_o', out=c4[n:])
-        c3h = self._layer(c2, 'layer2_h')
-        c4h = self._layer(c3h, 'layer3_h', out=c4[:n])
-        self._join()
-        c5 = self._layer(c4, 'layer4_h')
-        return dict(c2=c2, h=(c5[:n], c4h, c3h), o=(c5[n:], c4o, c3o))
+        return self._layer(c1, self.layers['layer1_h'])
 
-    def _fpn_branch(self, br, tr, windows):
-        c5, c4, c3 = tr[br]
-        c2 = tr['c2']
-        p = ops.conv2d_nhwc(c5, *self.fpn[f'toplayer_{br}'])
-        for lat, c in ((f'latlayer1_{br}', c4), (f'latlayer2_{br}', c3), (f'latlayer3_{br}', c2)):
-            # the stride-4 level: lateral convolution and top-down add only inside the windows dilated by the 3x3 halo
-            halo = windows[br][1] if (windows is not None and c is c2) else None
-            if self.fpn_fuse:       # top-down add inside the lateral convolution's epilogue: the finer map is written once
-                p = ops.conv2d_nhwc(c, *self.fpn[lat], rows=halo, rows_scatter=halo is not None, res_up=p)
-                continue
-            q = ops.conv2d_nhwc(c, *self.fpn[lat], rows=halo, rows_scatter=halo is not None)
-            p = ops.resize_bilinear_nhwc(p, q.shape[1], q.shape[2], out=q, accumulate=True, rows=halo)
-        return ops.conv3x3(p, *self.fpn[f'smooth3_{br}'], winograd=self.winograd, rows=None if windows is None else windows[br][0])
+    def _lateral(self, c, wb, p, rows=None, groups=1):
+        """One top-down step of the FPN: the lateral 1x1 convolution of ``c`` plus the coarser map ``p`` up-sampled to its grid.
+        ``rows``: only inside these windows (the stride-4 level: the RoI windows dilated by the 3x3 halo of the smoothing convolution)"""
+        if self.fpn_fuse:           # top-down add inside the lateral convolution's epilogue: the finer map is written once
+            return ops.conv2d_nhwc(c, *wb, rows=rows, rows_scatter=rows is not None, res_up=p, groups=groups)
+        q = ops.conv2d_nhwc(c, *wb, rows=rows, rows_scatter=rows is not None, groups=groups)
+        return ops.resize_bilinear_nhwc(p, q.shape[1], q.shape[2], out=q, accumulate=True, rows=rows)
 
-    def _hm_head(self, x, h):
-        y = ops.conv3x3(x, *h['c0'], winograd=self.winograd)
-        y = ops.conv3x3(y, *h['c1'], winograd=self.winograd)                             # BN folded; LeakyReLU(1.0) = identity (Q1)
+    def _top_down(self, fpn, sfx, c5, c4, c3, groups=1):
+        """top layer and the two coarse laterals -> the stride-8 map p3"""
+        p = ops.conv2d_nhwc(c5, *fpn['toplayer' + sfx], groups=groups)
+        p = self._lateral(c4, fpn['latlayer1' + sfx], p, groups=groups)
+        return self._lateral(c3, fpn['latlayer2' + sfx], p, groups=groups)
+
+    def _fpn_out(self, br, c2, p3, win, halo):
+        """The stride-4 output of one branch (its windows are its own, so never grouped).  ``win`` / ``halo`` = RoiWindows / the same
+        dilated by 1, or None: the output is produced only on the pixels the RoIAligns read, as a compact (rows, 256) matrix
+        (vpho_roi_windows_i32); the lateral convolution and the top-down add run on the dilated windows."""
+        p = self._lateral(c2, self.fpn[f'latlayer3_{br}'], p3, rows=halo)
+        return ops.conv3x3(p, *self.fpn[f'smooth3_{br}'], winograd=self.winograd, rows=win)
+
+    def _hm_up(self, x, h, groups=1):
+        """a heat-map head up to its last 1x1 convolution (21 / 27 output maps: always one launch per branch, at the call sites)"""
+        y = ops.conv3x3(x, *h['c0'], winograd=self.winograd, groups=groups)
+        y = ops.conv3x3(y, *h['c1'], winograd=self.winograd, groups=groups)                # BN folded; LeakyReLU(1.0) = identity (Q1)
         N, H, W, _ = y.shape
-        co = h['deconv_b'].shape[0]
+        co = h['deconv_b'].shape[-1]
         up = torch.empty((N, 2 * H, 2 * W, co), device=y.device)
         for (py, px), (w, pady, padx) in h['deconv'].items():
-            ops.conv2d_nhwc(y, w, h['deconv_b'], kh=2, kw=2, pad_y=pady, pad_x=padx, out_hw=(H, W), out_slope=0.0,
+            ops.conv2d_nhwc(y, w, h['deconv_b'], kh=2, kw=2, pad_y=pady, pad_x=padx, out_hw=(H, W), out_slope=0.0, groups=groups,
                             out_view=(up, 4 * H * W * co, 4 * W * co, 2 * co, (py * 2 * W + px) * co))
-        return ops.conv2d_nhwc(up, *h['final'])
+        return up
 
-    def _encoder(self, x, e):
-        x = ops.conv2d_nhwc(x, *e['project'])
+    def _encoder(self, x, e, groups=1):
+        x = ops.conv2d_nhwc(x, *e['project'], groups=groups)
         stages = []
         for i, b in enumerate(e['blocks']):
-            y = ops.conv2d_nhwc(x, *b['c1'], in_scale=b['pre'][0], in_shift=b['pre'][1], in_slope=0.01, out_slope=0.01)
-            y = ops.conv3x3(y, *b['c2'], out_slope=0.01, winograd=self.winograd)
-            x = ops.conv2d_nhwc(y, *b['c3'], res=x)
+            y = ops.conv2d_nhwc(x, *b['c1'], in_scale=b['pre'][0], in_shift=b['pre'][1], in_slope=0.01, out_slope=0.01, groups=groups)
+            y = ops.conv3x3(y, *b['c2'], out_slope=0.01, winograd=self.winograd, groups=groups)
+            x = ops.conv2d_nhwc(y, *b['c3'], res=x, groups=groups)
             if i % 2 == 1:
                 x = ops.maxpool_nhwc(x, 2, 2, 0)
                 stages.append(x)
@@ -298,96 +285,64 @@ class Engine:
         ff = ops.linear(ops.linear(x, *c['l1'], out_slope=0.0), *c['l2'])
         return ops.add_layernorm(x, ff, *c['n2'])                                       # (bs*65, 512)
 
-    # ---- the same blocks on the two branches at once: tensors hold the hand images [0, N) and the object images [N, 2N)
-    def _bottleneck_g(self, x, b, out=None, x_shared=False):
-        y = ops.conv2d_nhwc(x, *b['c1'], out_slope=0.01, groups=2, x_shared=x_shared)
-        if b['stride'] == 1:
-            y = ops.conv3x3(y, *b['c2'], out_slope=0.01, winograd=self.winograd, groups=2)
-        else:
-            y = ops.conv2d_nhwc(y, *b['c2'], kh=3, kw=3, stride=b['stride'], pad=1, out_slope=0.01, groups=2)
-        if b['down'] is not None and self.down_fuse and x.shape[-1] % 32 == 0 and y.shape[-1] % 32 == 0:
-            return ops.conv2d_nhwc(y, *b['c3_down'], x2=x, stride2=b['stride'], out_slope=0.01, out=out, groups=2, x2_shared=x_shared)
-        r = x if b['down'] is None else ops.conv2d_nhwc(x, *b['down'], stride=b['stride'], groups=2, x_shared=x_shared)
-        return ops.conv2d_nhwc(y, *b['c3'], res=r, out_slope=0.01, out=out, groups=2)
-
-    def _layer_g(self, x, name, x_shared=False):
-        for i, b in enumerate(self.g_layers[name]):
-            x = self._bottleneck_g(x, b, x_shared=x_shared and i == 0)
-        return x
-
-    def _hm_head_g(self, x):
-        h = self.g_hm
-        y = ops.conv3x3(x, *h['c0'], winograd=self.winograd, groups=2)
-        y = ops.conv3x3(y, *h['c1'], winograd=self.winograd, groups=2)                     # BN folded; LeakyReLU(1.0) = identity (Q1)
-        N2, H, W, _ = y.shape
-        co = h['deconv_b'].shape[1]
-        up = torch.empty((N2, 2 * H, 2 * W, co), device=y.device)
-        for (py, px), (w, pady, padx) in h['deconv'].items():
-            ops.conv2d_nhwc(y, w, h['deconv_b'], kh=2, kw=2, pad_y=pady, pad_x=padx, out_hw=(H, W), out_slope=0.0, groups=2,
-                            out_view=(up, 4 * H * W * co, 4 * W * co, 2 * co, (py * 2 * W + px) * co))
-        n = N2 // 2                                                                          # the last 1x1 has 21 / 27 output maps: one launch per branch
-        return ops.conv2d_nhwc(up[:n], *self.hm['hand']['final']), ops.conv2d_nhwc(up[n:], *self.hm['obj']['final'])
-
-    def _encoder_g(self, x):
-        e = self.g_enc
-        x = ops.conv2d_nhwc(x, *e['project'], groups=2)
-        stages = []
-        for i, b in enumerate(e['blocks']):
-            y = ops.conv2d_nhwc(x, *b['c1'], in_scale=b['pre'][0], in_shift=b['pre'][1], in_slope=0.01, out_slope=0.01, groups=2)
-            y = ops.conv3x3(y, *b['c2'], out_slope=0.01, winograd=self.winograd, groups=2)
-            x = ops.conv2d_nhwc(y, *b['c3'], res=x, groups=2)
-            if i % 2 == 1:
-                x = ops.maxpool_nhwc(x, 2, 2, 0)
-                stages.append(x)
-        N2 = x.shape[0]
-        return ops.nhwc_to_nchw(x).view(N2, -1), stages
-
     def features(self, data):
-        """VPHO.py:112-172.  Returns a dict of device tensors (NHWC unless noted)."""
+        """VPHO.py:112-172.  Returns a dict of device tensors (NHWC unless noted): the same keys, shapes and bits from both plans."""
+        grouped = self.grouped and self.conv_terms == 0                  # per call: conv_terms may be set on a live engine
+        self._two_streams = self.feature_streams >= 2 and not grouped
         with ops.conv_split(self.conv_terms):
-            return self._features_grouped(data) if (self.grouped and self.conv_terms == 0) else self._features(data)
+            rgb = data['rgb'].float().contiguous()
+            bs = rgb.shape[0]
+            f32 = lambda k: data[k].float().contiguous()
+            left_u8 = (~data['is_right'].bool()).to(torch.uint8).contiguous()
+            bb_h, bb_o, bb_hr, bb_or = f32('bbox_hand'), f32('bbox_obj'), f32('bbox_hand_rect'), f32('bbox_obj_rect')
+            win_h = win_o = halo_h = halo_o = None
+            if self.roi_window:
+                # the FPN outputs are read only through these RoIAligns (the reference's `of_or` on bbox_obj is never used, VPHO.py:127)
+                fh, fw = rgb.shape[2] // 4, rgb.shape[3] // 4
+                win_h = ops.roi_windows(bb_h, bb_hr, bs, fh, fw, 0.25)
+                win_o = ops.roi_windows(bb_or, None, bs, fh, fw, 0.25)
+                halo_h, halo_o = ops.roi_windows(bb_h, bb_hr, bs, fh, fw, 0.25, dilate=1), ops.roi_windows(bb_or, None, bs, fh, fw, 0.25, dilate=1)
+            grav = f32('gravity').view(bs, 3)
+            twin = self._twin_grouped if grouped else self._twin_per_branch
+            (hand_feat, obj_feat, hf_hr, in_h, in_o, hm_hand, hm_obj, hand_heatmap, obj_heatmap, enc_h, enc_o, st_h, st_o) = twin(
+                rgb, (bb_h, bb_o, bb_hr, bb_or), (win_h, win_o, halo_h, halo_o), left_u8)
+            with self._side():
+                tok_o = self._cross(self.cross['obj'], st_h, st_o, grav, left_u8)
+            hmn = self.head_mano
+            a64 = self.head64                                                                # the regression head with fp64 accumulation (ops.linear)
+            h = ops.linear(ops.linear(enc_h, *hmn['l0'], out_slope=0.01, acc64=a64), *hmn['l2'], out_slope=0.01, acc64=a64)
+            pose = ops.rot6d_to_axis_angle(ops.linear(h, *hmn['pose'], acc64=a64), 16)       # (bs,48)
+            shape = ops.linear(h, *hmn['shape'], acc64=a64)                                  # (bs,10)
+            ctx = self.mano.shape(shape)
+            ho3d = data['is_ho3d'].to(torch.uint8).contiguous() if 'is_ho3d' in data else None
+            reg_vert, reg_joint = self.mano.fk(pose, ctx, 1, True, ho3d)
+            tok_h = self._cross(self.cross['hand'], st_h, st_o, grav, left_u8)
+            self._join()
+            ph = self.phys
+            scale = ops.linear(ops.linear(tok_h, *ph['s0'], out_slope=0.01), *ph['s2'])      # (bs*65,1)
+            logits = ops.linear(ops.linear(tok_o, *ph['w0'], out_slope=0.01), *ph['w2'])     # (bs*65,8)
+            force_local = ops.force_local(scale, logits, ph['anchor'], bs * 32, 32, 65, 0, 32).view(bs, 32, 3)
+            return dict(hand_feat=hand_feat, obj_feat=obj_feat, roi_win_hand=win_h, roi_win_obj=win_o, hf_hr=hf_hr, enc_in_hand=in_h, enc_in_obj=in_o,
+                        hm_hand_nhwc=hm_hand, hm_obj_nhwc=hm_obj, hand_heatmap=hand_heatmap, obj_heatmap=obj_heatmap,
+                        encoding_hand=enc_h, encoding_obj=enc_o, stage_hand=st_h, stage_obj=st_o, mano_pose=pose, mano_shape=shape,
+                        mano_ctx=ctx, reg_hand_vert=reg_vert, reg_hand_joint=reg_joint, tok_hand=tok_h, tok_obj=tok_o, force_local=force_local)
 
-    def _features_grouped(self, data):
-        """_features with the twin branches as grouped launches (one stream; results bit-identical to _features)"""
-        rgb = data['rgb'].float().contiguous()
-        bs = rgb.shape[0]
-        f32 = lambda k: data[k].float().contiguous()
-        is_right = data['is_right'].bool()
-        left_u8 = (~is_right).to(torch.uint8).contiguous()
-        R = cfg.roi_size
-        bb_h, bb_o, bb_hr, bb_or = f32('bbox_hand'), f32('bbox_obj'), f32('bbox_hand_rect'), f32('bbox_obj_rect')
-        win_h = win_o = halo_h = halo_o = None
-        if self.roi_window:
-            fh, fw = rgb.shape[2] // 4, rgb.shape[3] // 4
-            win_h = ops.roi_windows(bb_h, bb_hr, bs, fh, fw, 0.25)
-            win_o = ops.roi_windows(bb_or, None, bs, fh, fw, 0.25)
-            halo_h, halo_o = ops.roi_windows(bb_h, bb_hr, bs, fh, fw, 0.25, dilate=1), ops.roi_windows(bb_or, None, bs, fh, fw, 0.25, dilate=1)
-        grav = f32('gravity').view(bs, 3)
+    # The two plans of the twin branches, from the image to the encodings.  Both take the boxes (hand, object, hand rect, object rect) and
+    # the windows (hand, object, hand halo, object halo; all None for the full maps) and return
+    # (hand_feat, obj_feat, hf_hr, in_h, in_o, hm_hand, hm_obj, hand_heatmap, obj_heatmap, enc_h, enc_o, st_h, st_o), bit for bit the same.
+    def _twin_grouped(self, rgb, bb, win, left_u8):
+        """the twin branches as grouped launches on (2N, ...) tensors, everything on one stream"""
+        (bb_h, bb_o, bb_hr, bb_or), (win_h, win_o, halo_h, halo_o) = bb, win
+        bs, R = rgb.shape[0], cfg.roi_size
         # ---- trunk: shared stem / layer1, the two layer2 / layer3 stacks as groups, shared layer4 on the batch of 2N images (quirk Q6)
-        x = ops.nchw_to_nhwc(rgb, 4)
-        c1 = ops.maxpool_nhwc(ops.conv2d_nhwc(x, *self.stem, kh=7, kw=7, stride=2, pad=3, out_slope=0.01), 3, 2, 1)
-        c2 = self._layer(c1, 'layer1_h')
-        c3 = self._layer_g(c2, 'layer2', x_shared=True)                                       # (2N,32,32,512)
-        c4 = self._layer_g(c3, 'layer3')                                                       # (2N,16,16,1024)
-        c5 = self._layer(c4, 'layer4_h')                                                       # (2N,8,8,2048)
+        c2 = self._stem(rgb)
+        c3 = self._layer(c2, self.g_layers['layer2'], groups=2, x_shared=True)               # (2N,32,32,512)
+        c4 = self._layer(c3, self.g_layers['layer3'], groups=2)                              # (2N,16,16,1024)
+        c5 = self._layer(c4, self.layers['layer4_h'])                                        # (2N,8,8,2048)
         # ---- top-down path: top layer and the two coarse laterals as groups; the stride-4 level per branch (its windows differ)
-        p = ops.conv2d_nhwc(c5, *self.g_fpn['toplayer'], groups=2)
-        if self.fpn_fuse:
-            p = ops.conv2d_nhwc(c4, *self.g_fpn['latlayer1'], groups=2, res_up=p)
-            p = ops.conv2d_nhwc(c3, *self.g_fpn['latlayer2'], groups=2, res_up=p)
-        else:
-            for lat, c in (('latlayer1', c4), ('latlayer2', c3)):
-                q = ops.conv2d_nhwc(c, *self.g_fpn[lat], groups=2)
-                p = ops.resize_bilinear_nhwc(p, q.shape[1], q.shape[2], out=q, accumulate=True)
-        feats = {}
-        for br, pb, halo, win in (('h', p[:bs], halo_h, win_h), ('o', p[bs:], halo_o, win_o)):
-            if self.fpn_fuse:
-                q = ops.conv2d_nhwc(c2, *self.fpn[f'latlayer3_{br}'], rows=halo, rows_scatter=halo is not None, res_up=pb)
-            else:
-                q = ops.conv2d_nhwc(c2, *self.fpn[f'latlayer3_{br}'], rows=halo, rows_scatter=halo is not None)
-                q = ops.resize_bilinear_nhwc(pb, q.shape[1], q.shape[2], out=q, accumulate=True, rows=halo)
-            feats[br] = ops.conv3x3(q, *self.fpn[f'smooth3_{br}'], winograd=self.winograd, rows=win)
-        hand_feat, obj_feat = feats['h'], feats['o']
+        p3 = self._top_down(self.g_fpn, '', c5, c4, c3, groups=2)
+        hand_feat = self._fpn_out('h', c2, p3[:bs], win_h, halo_h)
+        obj_feat = self._fpn_out('o', c2, p3[bs:], win_o, halo_o)
         # ---- RoI crops of both branches in one buffer each: the heads' inputs (2N,32,32,256), the encoders' inputs (2N,32,32,284)
         crop = torch.empty((2 * bs, R, R, 256), device=self.dev)
         enc_in = torch.zeros((2 * bs, R, R, self.g_enc['cin_pad']), device=self.dev)
@@ -398,93 +353,57 @@ class Engine:
             ops.roi_align_dual_nhwc(obj_feat, bb_or, R, 0.25, win_o, in_o, flip_w2=left_u8, out=crop[bs:])
         else:
             ops.roi_align_nhwc(obj_feat, bb_or, R, 0.25, out=crop[bs:])
-            ops.roi_align_nhwc(obj_feat, bb_or, R, 0.25, flip_w=left_u8, out=in_o)                # VPHO.py:138
-        hm_hand, hm_obj = self._hm_head_g(crop)                                              # (bs,64,64,21), (bs,64,64,27)
+            ops.roi_align_nhwc(obj_feat, bb_or, R, 0.25, flip_w=left_u8, out=in_o)           # VPHO.py:138
+        up = self._hm_up(crop, self.g_hm, groups=2)
+        hm_hand = ops.conv2d_nhwc(up[:bs], *self.hm['hand']['final'])                        # (bs,64,64,21)
+        hm_obj = ops.conv2d_nhwc(up[bs:], *self.hm['obj']['final'])                          # (bs,64,64,27)
         ops.resize_bilinear_nhwc(ops.align_heatmap_nhwc(hm_hand, bb_h, bb_hr), R, R, out=in_h, c_off=256)
         ops.resize_bilinear_nhwc(ops.align_heatmap_nhwc(hm_obj, bb_o, bb_or, flip_w=left_u8), R, R, out=in_o, c_off=256)
-        enc, st = self._encoder_g(enc_in)
-        enc_h, enc_o = enc[:bs], enc[bs:]
-        st_h, st_o = [t[:bs] for t in st], [t[bs:] for t in st]
+        enc, st = self._encoder(enc_in, self.g_enc, groups=2)
         hand_heatmap, obj_heatmap = ops.nhwc_to_nchw(hm_hand), ops.nhwc_to_nchw(hm_obj)
-        tok_o = self._cross(self.cross['obj'], st_h[1], st_o[1], grav, left_u8)
-        hmn = self.head_mano
-        a64 = self.head64                                                                    # the regression head with fp64 accumulation (ops.linear)
-        h = ops.linear(ops.linear(enc_h, *hmn['l0'], out_slope=0.01, acc64=a64), *hmn['l2'], out_slope=0.01, acc64=a64)
-        pose = ops.rot6d_to_axis_angle(ops.linear(h, *hmn['pose'], acc64=a64), 16)                      # (bs,48)
-        shape = ops.linear(h, *hmn['shape'], acc64=a64)                                      # (bs,10)
-        ctx = self.mano.shape(shape)
-        ho3d = data['is_ho3d'].to(torch.uint8).contiguous() if 'is_ho3d' in data else None
-        reg_vert, reg_joint = self.mano.fk(pose, ctx, 1, True, ho3d)
-        tok_h = self._cross(self.cross['hand'], st_h[1], st_o[1], grav, left_u8)
-        ph = self.phys
-        scale = ops.linear(ops.linear(tok_h, *ph['s0'], out_slope=0.01), *ph['s2'])          # (bs*65,1)
-        logits = ops.linear(ops.linear(tok_o, *ph['w0'], out_slope=0.01), *ph['w2'])         # (bs*65,8)
-        force_local = ops.force_local(scale, logits, ph['anchor'], bs * 32, 32, 65, 0, 32).view(bs, 32, 3)
-        return dict(hand_feat=hand_feat, obj_feat=obj_feat, roi_win_hand=win_h, roi_win_obj=win_o, hf_hr=hf_hr, enc_in_hand=in_h, enc_in_obj=in_o,
-                    hm_hand_nhwc=hm_hand, hm_obj_nhwc=hm_obj, hand_heatmap=hand_heatmap, obj_heatmap=obj_heatmap,
-                    encoding_hand=enc_h, encoding_obj=enc_o, stage_hand=st_h[1], stage_obj=st_o[1], mano_pose=pose, mano_shape=shape,
-                    mano_ctx=ctx, reg_hand_vert=reg_vert, reg_hand_joint=reg_joint, tok_hand=tok_h, tok_obj=tok_o, force_local=force_local)
+        # the hand's encoder input as the per-branch plan shapes it: its own padded width (280) of the 284 the grouped encoder reads
+        return (hand_feat, obj_feat, hf_hr, in_h[..., :self.enc['hand']['cin_pad']], in_o, hm_hand, hm_obj, hand_heatmap, obj_heatmap,
+                enc[:bs], enc[bs:], st[1][:bs], st[1][bs:])
 
-    def _features(self, data):
-        rgb = data['rgb'].float().contiguous()
-        bs = rgb.shape[0]
-        f32 = lambda k: data[k].float().contiguous()
-        is_right = data['is_right'].bool()
-        left_u8 = (~is_right).to(torch.uint8).contiguous()
-        R, HM = cfg.roi_size, cfg.heatmap_size
-        bb_h, bb_o, bb_hr, bb_or = f32('bbox_hand'), f32('bbox_obj'), f32('bbox_hand_rect'), f32('bbox_obj_rect')
-        win_h = win_o = None
-        if self.roi_window:
-            # the FPN outputs are read only through these RoIAligns (the reference's `of_or` on bbox_obj is never used, VPHO.py:127)
-            fh, fw = rgb.shape[2] // 4, rgb.shape[3] // 4
-            win_h = ops.roi_windows(bb_h, bb_hr, bs, fh, fw, 0.25)
-            win_o = ops.roi_windows(bb_or, None, bs, fh, fw, 0.25)
-            halo = {'h': ops.roi_windows(bb_h, bb_hr, bs, fh, fw, 0.25, dilate=1), 'o': ops.roi_windows(bb_or, None, bs, fh, fw, 0.25, dilate=1)}
-        windows = None if win_h is None else {'h': (win_h, halo['h']), 'o': (win_o, halo['o'])}
+    def _twin_per_branch(self, rgb, bb, win, left_u8):
+        """one launch per branch; with two feature streams the object branch is issued on the side stream"""
+        (bb_h, bb_o, bb_hr, bb_or), (win_h, win_o, halo_h, halo_o) = bb, win
+        bs, R, L = rgb.shape[0], cfg.roi_size, self.layers
         eh, eo = self.enc['hand'], self.enc['obj']
         in_h = torch.zeros((bs, R, R, eh['cin_pad']), device=self.dev)
         in_o = torch.zeros((bs, R, R, eo['cin_pad']), device=self.dev)
-        grav = f32('gravity').view(bs, 3)
-        tr = self._fpn_trunk(rgb)
-        with self._side():                                                               # object branch
-            obj_feat = self._fpn_branch('o', tr, windows)
-            if win_o is not None:                                                        # one pooling pass, two destinations (VPHO.py:126-138)
+        c2 = self._stem(rgb)
+        # shared layer4 (quirk Q6): both branches go through the same weights, so they run as ONE batch of 2N images
+        # (twice the tiles per launch at 8x8 resolution, half the launches); convolutions are per-image, results unchanged.  The two
+        # layer3 stacks write their last block straight into the halves of that batch: no concatenation copy
+        c4 = torch.empty((2 * bs, c2.shape[1] // 4, c2.shape[2] // 4, L['layer3_h'][-1]['c3'][0].shape[0]), device=c2.device)
+        with self._side():
+            c3o = self._layer(c2, L['layer2_o'])
+            c4o = self._layer(c3o, L['layer3_o'], out=c4[bs:])
+        c3h = self._layer(c2, L['layer2_h'])
+        c4h = self._layer(c3h, L['layer3_h'], out=c4[:bs])
+        self._join()
+        c5 = self._layer(c4, L['layer4_h'])
+        with self._side():                                                                   # object branch
+            obj_feat = self._fpn_out('o', c2, self._top_down(self.fpn, '_o', c5[bs:], c4o, c3o), win_o, halo_o)
+            if win_o is not None:                                                            # one pooling pass, two destinations (VPHO.py:126-138)
                 of_or_rect = ops.roi_align_dual_nhwc(obj_feat, bb_or, R, 0.25, win_o, in_o, flip_w2=left_u8)
             else:
                 of_or_rect = ops.roi_align_nhwc(obj_feat, bb_or, R, 0.25)
-                ops.roi_align_nhwc(obj_feat, bb_or, R, 0.25, flip_w=left_u8, out=in_o)           # VPHO.py:138
-            hm_obj = self._hm_head(of_or_rect, self.hm['obj'])                           # (bs,64,64,27)
+                ops.roi_align_nhwc(obj_feat, bb_or, R, 0.25, flip_w=left_u8, out=in_o)       # VPHO.py:138
+            hm_obj = ops.conv2d_nhwc(self._hm_up(of_or_rect, self.hm['obj']), *self.hm['obj']['final'])        # (bs,64,64,27)
             ops.resize_bilinear_nhwc(ops.align_heatmap_nhwc(hm_obj, bb_o, bb_or, flip_w=left_u8), R, R, out=in_o, c_off=256)
             enc_o, st_o = self._encoder(in_o, eo)
             obj_heatmap = ops.nhwc_to_nchw(hm_obj)
-        hand_feat = self._fpn_branch('h', tr, windows)
+        hand_feat = self._fpn_out('h', c2, self._top_down(self.fpn, '_h', c5[:bs], c4h, c3h), win_h, halo_h)
         hf_hr = ops.roi_align_nhwc(hand_feat, bb_h, R, 0.25, win=win_h)
         ops.roi_align_nhwc(hand_feat, bb_hr, R, 0.25, out=in_h, win=win_h)
-        hm_hand = self._hm_head(hf_hr, self.hm['hand'])                                  # (bs,64,64,21)
+        hm_hand = ops.conv2d_nhwc(self._hm_up(hf_hr, self.hm['hand']), *self.hm['hand']['final'])              # (bs,64,64,21)
         ops.resize_bilinear_nhwc(ops.align_heatmap_nhwc(hm_hand, bb_h, bb_hr), R, R, out=in_h, c_off=256)
         enc_h, st_h = self._encoder(in_h, eh)
         hand_heatmap = ops.nhwc_to_nchw(hm_hand)
         self._join()
-        with self._side():
-            tok_o = self._cross(self.cross['obj'], st_h[1], st_o[1], grav, left_u8)
-        hmn = self.head_mano
-        a64 = self.head64                                                                    # the regression head with fp64 accumulation (ops.linear)
-        h = ops.linear(ops.linear(enc_h, *hmn['l0'], out_slope=0.01, acc64=a64), *hmn['l2'], out_slope=0.01, acc64=a64)
-        pose = ops.rot6d_to_axis_angle(ops.linear(h, *hmn['pose'], acc64=a64), 16)                  # (bs,48)
-        shape = ops.linear(h, *hmn['shape'], acc64=a64)                                  # (bs,10)
-        ctx = self.mano.shape(shape)
-        ho3d = data['is_ho3d'].to(torch.uint8).contiguous() if 'is_ho3d' in data else None
-        reg_vert, reg_joint = self.mano.fk(pose, ctx, 1, True, ho3d)
-        tok_h = self._cross(self.cross['hand'], st_h[1], st_o[1], grav, left_u8)
-        self._join()
-        ph = self.phys
-        scale = ops.linear(ops.linear(tok_h, *ph['s0'], out_slope=0.01), *ph['s2'])      # (bs*65,1)
-        logits = ops.linear(ops.linear(tok_o, *ph['w0'], out_slope=0.01), *ph['w2'])     # (bs*65,8)
-        force_local = ops.force_local(scale, logits, ph['anchor'], bs * 32, 32, 65, 0, 32).view(bs, 32, 3)
-        return dict(hand_feat=hand_feat, obj_feat=obj_feat, roi_win_hand=win_h, roi_win_obj=win_o, hf_hr=hf_hr, enc_in_hand=in_h, enc_in_obj=in_o,
-                    hm_hand_nhwc=hm_hand, hm_obj_nhwc=hm_obj, hand_heatmap=hand_heatmap, obj_heatmap=obj_heatmap,
-                    encoding_hand=enc_h, encoding_obj=enc_o, stage_hand=st_h[1], stage_obj=st_o[1], mano_pose=pose, mano_shape=shape,
-                    mano_ctx=ctx, reg_hand_vert=reg_vert, reg_hand_joint=reg_joint, tok_hand=tok_h, tok_obj=tok_o, force_local=force_local)
+        return hand_feat, obj_feat, hf_hr, in_h, in_o, hm_hand, hm_obj, hand_heatmap, obj_heatmap, enc_h, enc_o, st_h[1], st_o[1]
 
     # ------------------------------------------------------------------------------------------------ sampling
     def _prior(self, rows, dim):
