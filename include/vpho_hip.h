@@ -474,6 +474,24 @@ VPHO_API int vpho_obj_metrics_multi_f64(const vpho_obj_metric_tables* t, const d
                                const int* obj_id, int n_img, int n_hyp, int max_verts, double* out, double* best, double* mean,
                                void* workspace, long long workspace_bytes, void* stream);
 
+/* Prediction records of --mode infer (Trainer.infer, lib/engine/train_diff_hand_obj.py:359-444): ONE launch turns the predict outputs of a
+ * batch into fixed-layout per-image records, and ONE hipMemcpyAsync ships them to the host.  Replaces, per batch, the postprocess of
+ * the four hand arrays (__postprocess_hand_vert, :598-602: x negated where !is_right, then + root_joint; one sign flip and one fp32 add
+ * per element), `.astype(np.float16)` of the aggregated vertices (:383; round to nearest even, overflow to inf, subnormals kept),
+ * __postprocess_obj_rt of agg_obj_6d (:593-596; the arithmetic of vpho_obj_9d_to_rt_f64, bit for bit) and to_numpy (:375-376).
+ * Record of one image, vpho_infer_record_bytes(n_joint, n_vert) bytes (a multiple of 8; -1 on a bad argument):
+ *   block A  fp32  reg_joint [n_joint][3] | reg_vert [n_vert][3] | agg_joint [n_joint][3] | agg_vert [n_vert][3]   camera frame
+ *   block B  fp16  agg_vert of block A [n_vert][3], then zero padding to a multiple of 8 bytes
+ *   block C  fp64  pd_obj_rt [3][4] = [R | t + root]
+ * reg_* / agg_* [n_img][n_pts][3] fp32 in the model frame as predict returns them, agg_obj_6d [n_img][9] fp64, root_joint [n_img][3]
+ * fp32, is_right [n_img] (0 / 1); n_vert must be even (block B is written two halves per dword).  records: device, n_img records.
+ * records_host: pinned host memory or NULL; when given, the records are copied to it on `stream` behind the kernel (the caller
+ * waits for the stream or an event on it before reading).  Deterministic; no workspace. */
+VPHO_API long long vpho_infer_record_bytes(int n_joint, int n_vert);
+VPHO_API int vpho_infer_pack_f32(const float* reg_hand_joint, const float* reg_hand_vert, const float* agg_hand_joint, const float* agg_hand_vert,
+                        const double* agg_obj_6d, const float* root_joint, const unsigned char* is_right, int n_img, int n_joint,
+                        int n_vert, void* records, void* records_host, void* stream);
+
 /* Hand-object penetration and contact (--eval_physics).  The object meshes as per-triangle records
  * tri [tri_offset[n_obj]][VPHO_PEN_TRI_STRIDE] fp64, objects concatenated (vpho_amd/physics_eval.py builds them on the host):
  *   fields 0-18 in the object's hash frame (q = scale * p + translate, the mesh bbox mapped onto [0.5, 511.5]^3; corners t1, t2, t3):

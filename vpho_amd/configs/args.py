@@ -11,6 +11,8 @@ import sys
 # lib/configs/args.py:235-245 (the object side offers no `2D_pt_joint`)
 AGGREGATION_MODES_HAND = ('heatmap_cascade', 'heatmap', '2D_pt_pose', '2D_pt_joint', 'average_all', 'random')
 AGGREGATION_MODES_OBJ = ('heatmap_cascade', 'heatmap', '2D_pt_pose', 'average_all', 'random')
+# lib/configs/args.py:151-155: names the data split; --mode infer puts it into the name of its prediction pickle
+CLEAN_DATA_MODES = ('2023_CVPR_HFL', '2022_CVPR_ArtiBoost', '2023_WACV_DMA', 'stable_grasping', '2023_NIPS_DeepSimHO')
 
 
 class Config:
@@ -27,6 +29,7 @@ class Config:
         self.pretrain = ''
         self.remove_pretrained_keys = []
         self.dataset_name = 'dexycb'
+        self.clean_data_mode = '2023_CVPR_HFL'
         self.patch_size = 256
         self.batch_size = 64
         self.eval_batch_size = 32
@@ -80,6 +83,7 @@ def _parser():
     p.add_argument('--pretrain', type=str, default='')
     p.add_argument('--remove_pretrained_keys', nargs='+', default=[])
     p.add_argument('--dataset_name', type=str, default='dexycb', choices=['dexycb', 'ho3d'])
+    p.add_argument('--clean_data_mode', type=str, default='2023_CVPR_HFL', choices=list(CLEAN_DATA_MODES))
     p.add_argument('--patch_size', type=int, default=256)
     p.add_argument('--batch_size', type=int, default=64)
     p.add_argument('--eval_batch_size', type=int, default=32)

@@ -141,12 +141,7 @@ __global__ __launch_bounds__(256) void hand_metrics_kernel(const float* __restri
 __global__ void obj_9d_to_rt_kernel(const double* __restrict__ pose9, const float* __restrict__ root, int n, double* __restrict__ rt) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    double R[9];
-    vpho::rot6d_to_matrix<double>(pose9 + (long long)i * 9, R);
-    for (int r = 0; r < 3; ++r) {
-        for (int c = 0; c < 3; ++c) rt[(long long)i * 12 + r * 4 + c] = R[r * 3 + c];
-        rt[(long long)i * 12 + r * 4 + 3] = (double)root[i * 3 + r] + pose9[(long long)i * 9 + 6 + r];
-    }
+    vpho::obj_9d_to_rt(pose9 + (long long)i * 9, root + (long long)i * 3, rt + (long long)i * 12);
 }
 
 // ------------------------------------------------------------------------------------------------ object metrics

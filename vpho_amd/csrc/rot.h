@@ -33,6 +33,17 @@ __device__ inline void rot6d_to_matrix(const T* d6, T* R) {
     R[8] = b1[0] * b2[1] - b1[1] * b2[0];
 }
 
+// obj_9D_to_mat (lib/utils/transform_fn.py:85-90) + root joint (train_diff_hand_obj.py:593-596): [rot6d | t] -> rt[12] = [R | t + root].
+// The ONE formulation behind vpho_obj_9d_to_rt_f64 and block C of vpho_infer_pack_f32: both give the same bits.
+__device__ inline void obj_9d_to_rt(const double* pose9, const float* root3, double* rt) {
+    double R[9];
+    rot6d_to_matrix<double>(pose9, R);
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) rt[r * 4 + c] = R[r * 3 + c];
+        rt[r * 4 + 3] = (double)root3[r] + pose9[6 + r];
+    }
+}
+
 // matrix_to_quaternion (best-conditioned candidate, then standardize: real part >= 0)
 template <typename T>
 __device__ inline void matrix_to_quaternion(const T* m, T* q) {

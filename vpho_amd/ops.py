@@ -26,6 +26,7 @@ lib.vpho_obj_metrics_multi_workspace_bytes.restype = C.c_longlong
 lib.vpho_bn_workspace_bytes.restype = C.c_longlong
 lib.vpho_conv2d_wgrad_workspace_bytes.restype = C.c_longlong
 lib.vpho_mha_bwd_workspace_bytes.restype = C.c_longlong
+lib.vpho_infer_record_bytes.restype = C.c_longlong
 
 
 class VphoError(RuntimeError):
@@ -1069,6 +1070,72 @@ def obj_9d_to_rt(pose9, root_joint):
     rt = _new((n, 3, 4), pose9, torch.float64)
     _call('vpho_obj_9d_to_rt_f64', _f64(pose9), _f32(root_joint), I(n), _f64(rt))
     return rt
+
+
+def infer_record_dtype(n_joint=21, n_vert=778):
+    """numpy structured dtype of one vpho_infer_pack_f32 record (include/vpho_hip.h): blocks A (fp32), B (fp16), C (fp64)"""
+    import numpy as np
+    size = lib.vpho_infer_record_bytes(I(n_joint), I(n_vert))
+    if size < 0:
+        raise VphoError(f'vpho_infer_record_bytes: n_joint = {n_joint}, n_vert = {n_vert} (both positive, n_vert even)')
+    a = 24 * (n_joint + n_vert)
+    return np.dtype({'names': ['reg_joint', 'reg_vert', 'agg_joint', 'agg_vert', 'agg_vert_f16', 'pd_obj_rt'],
+                     'formats': [('<f4', (n_joint, 3)), ('<f4', (n_vert, 3)), ('<f4', (n_joint, 3)), ('<f4', (n_vert, 3)), ('<f2', (n_vert, 3)),
+                                 ('<f8', (3, 4))],
+                     'offsets': [0, 12 * n_joint, 12 * (n_joint + n_vert), 12 * (2 * n_joint + n_vert), a, size - 96], 'itemsize': size})
+
+
+class InferPacker:
+    """Prediction records of --mode infer (vpho_infer_pack_f32): per slot of the evaluation pipeline a device staging buffer and a PINNED
+    host buffer of ``max_batch`` records.  ``pack`` = one kernel launch + one hipMemcpyAsync on the caller's stream + one event;
+    ``collect`` waits for that event only and returns the records as a numpy view of the pinned buffer (valid until the slot's next
+    ``pack``).  Nothing here synchronises the device."""
+
+    def __init__(self, device, max_batch, slots=3, n_joint=21, n_vert=778):
+        self.device, self.max_batch, self.slots = torch.device(device), int(max_batch), int(slots)
+        self.n_joint, self.n_vert = n_joint, n_vert
+        self.dtype = infer_record_dtype(n_joint, n_vert)
+        self.record_bytes = self.dtype.itemsize
+        self.stage = [torch.empty(self.max_batch * self.record_bytes, dtype=torch.uint8, device=self.device) for _ in range(self.slots)]
+        self.host = [torch.empty(self.max_batch * self.record_bytes, dtype=torch.uint8, pin_memory=True) for _ in range(self.slots)]
+        self.events = [None] * self.slots
+        self.counts = [0] * self.slots
+
+    def pack(self, out, batch, stream=None, slot=0):
+        """out: the predict outputs; batch: its 'root_joint' (n,3) and 'is_right' (n,), on the device.  Enqueued on ``stream`` (default: the
+        current one).  Returns the slot."""
+        n = out['agg_hand_joint'].shape[0]
+        if n > self.max_batch:
+            raise VphoError(f'InferPacker.pack: a batch of {n} images, the packer was built for max_batch = {self.max_batch}')
+        if not 0 <= slot < self.slots:
+            raise VphoError(f'InferPacker.pack: slot {slot} of {self.slots}')
+        stream = torch.cuda.current_stream(self.device) if stream is None else stream
+        c = lambda t: t.float().contiguous()
+        J, V = self.n_joint, self.n_vert
+        rj, rv, aj, av = c(out['reg_hand_joint']), c(out['reg_hand_vert']), c(out['agg_hand_joint']), c(out['agg_hand_vert'])
+        if rj.shape != (n, J, 3) or aj.shape != (n, J, 3) or rv.shape != (n, V, 3) or av.shape != (n, V, 3):
+            raise VphoError(f'InferPacker.pack: hand arrays {tuple(rj.shape)} {tuple(rv.shape)} {tuple(aj.shape)} {tuple(av.shape)}, expected (n,{J},3) / (n,{V},3)')
+        o9 = out['agg_obj_6d'].double().contiguous()
+        root = c(batch['root_joint'])
+        flag = batch['is_right']
+        # a bool tensor on the device is read as it stands (one byte per image, 0 / 1): no conversion launch
+        flag = flag.contiguous().view(torch.uint8) if flag.is_cuda and flag.dtype == torch.bool else flag.to(device=self.device, dtype=torch.uint8).contiguous()
+        if o9.shape != (n, 9) or root.shape != (n, 3) or flag.shape != (n,):
+            raise VphoError(f'InferPacker.pack: agg_obj_6d {tuple(o9.shape)}, root_joint {tuple(root.shape)}, is_right {tuple(flag.shape)} for {n} images')
+        with torch.cuda.stream(stream):
+            _call('vpho_infer_pack_f32', _f32(rj), _f32(rv), _f32(aj), _f32(av), _f64(o9), _f32(root), _u8(flag), I(n), I(J), I(V),
+                  _ptr(self.stage[slot]), C.c_void_p(self.host[slot].data_ptr()))
+            ev = torch.cuda.Event(blocking=True)
+            ev.record(stream)
+        self.events[slot], self.counts[slot] = ev, n
+        return slot
+
+    def collect(self, slot):
+        """the records of the slot's last ``pack`` (numpy, ``self.dtype``, a VIEW of the pinned buffer) once its copy has landed"""
+        if self.events[slot] is None:
+            raise VphoError(f'InferPacker.collect: nothing was packed into slot {slot}')
+        self.events[slot].synchronize()
+        return self.host[slot].numpy()[:self.counts[slot] * self.record_bytes].view(self.dtype)
 
 
 class ObjMetricTables(C.Structure):

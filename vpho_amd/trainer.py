@@ -8,6 +8,7 @@ same RANK/LOCAL_RANK/WORLD_SIZE variables).  There is no dataset in this build: 
 backbone, heat-map heads, encoders, MANO head and score networks are all updated); ``--train_scope score`` trains the two score
 networks on frozen features (``ScoreTrainer.step``: the reference's ``repeat_num`` DSM draws, backward, data-parallel gradient
 average and AdamW per denoiser).
+``infer`` (``--mode infer``): the same batches through the same pipeline, predictions written to files (vpho_amd/infer.py).
 """
 import os
 import time
@@ -174,12 +175,13 @@ class Trainer:
     def _to_device(self, batch):
         return {k: (v.to(self.device) if torch.is_tensor(v) else v) for k, v in batch.items()}
 
-    def _eval_batches(self, loader):
+    def _eval_batches(self, loader, need_gt=True):
         """yields (batch on the device, (gt_joint, gt_vert), index of its first image).  ``loader`` None: ``cfg.num_batches`` synthetic
         batches whose ground truth is batch 0's own regression output (there is no data set in this build).  Otherwise ANY iterable of
         collated Appendix-A batch dicts (lib/dataset/dexycb6.py:471-509; what ``accel.prepare`` hands each rank,
         train_diff_hand_obj.py:211-217): ground truth = ``gt_joint`` / ``gt_hand_vert`` in the camera frame (:237-238), the object's
-        ``gt_obj_rt`` or, like the reference's postprocess of the batch (:578-597), ``gt_obj`` (9-D) + root joint."""
+        ``gt_obj_rt`` or, like the reference's postprocess of the batch (:578-597), ``gt_obj`` (9-D) + root joint.
+        ``need_gt=False`` (``infer``): batches without hand ground truth are taken as they are, their ground truth is None."""
         cfg, bs = self.cfg, self.cfg.eval_batch_size
         if loader is None:
             gt = None
@@ -202,13 +204,13 @@ class Trainer:
                     ids = hidx.clone()            # a shuffled loader / DistributedSampler: the data set's own indices, image by image
             b = self._to_device(b)
             missing = [k for k in ('gt_joint', 'gt_hand_vert') if k not in b]
-            if missing:
+            if missing and need_gt:
                 raise KeyError(f'evaluation batch lacks {missing}: Trainer.eval(loader) needs the ground truth of lib/dataset/dexycb6.py:471-509')
             if 'gt_obj_rt' not in b and 'gt_obj' in b:
                 from . import ops
                 b['gt_obj_rt'] = ops.obj_9d_to_rt(b['gt_obj'].double().contiguous(), b['root_joint'].float().contiguous()).float()
             n = b['rgb'].shape[0]
-            yield b, (b['gt_joint'].float(), b['gt_hand_vert'].float()), (first if first is not None else ids if ids is not None else -(self.rank + self.world * (seen + torch.arange(n))) - 1)
+            yield b, (None if missing else (b['gt_joint'].float(), b['gt_hand_vert'].float())), (first if first is not None else ids if ids is not None else -(self.rank + self.world * (seen + torch.arange(n))) - 1)
             seen += n
 
     @torch.no_grad()
@@ -276,5 +278,136 @@ class Trainer:
             dist.barrier()
         return rows
 
-    def infer(self):
-        return self.eval()
+    @torch.no_grad()
+    def infer(self, loader=None, save_dir=None):
+        """``Trainer.infer`` (train_diff_hand_obj.py:359-444): predictions to files.  ``loader``: see ``_eval_batches`` (hand ground truth is
+        not needed); default ``cfg.num_batches`` synthetic batches.  Per batch ONE kernel turns the predict outputs into per-image records
+        and ONE asynchronous copy lands them in pinned host memory (ops.InferPacker), inside the three-deep pipeline; a host thread takes
+        them out.  Every rank writes a shard, rank 0 merges and writes under ``save_dir`` (default
+        ``<output_dir>/<timestamp>_<mark>_infer_<model>``, base_trainer.py:52-63) ``submit/hand_reg.zip``, ``submit/hand_diff.zip`` and
+        ``my-prediction_align-<clean_data_mode>.pkl`` (vpho_amd/infer.py), prints the object table of the aggregated
+        pose when the batches carry its ground truth, and one ``INFER_JSON`` line.  Returns that line's dict on rank 0, None elsewhere."""
+        import json
+        import queue
+        import threading
+        import numpy as np
+        from . import infer as INF
+        from . import ops
+        from .configs.args import cfg
+        if save_dir is None:
+            names = [os.path.join(cfg.output_dir, f"{time.strftime('%Y%m%d_%H%M%S', time.localtime())}_{cfg.mark}_infer_{cfg.model}")]
+            if self.world > 1:
+                dist.broadcast_object_list(names, src=0)           # one directory for all ranks (base_trainer.py:53)
+            save_dir = names[0]
+        t0 = time.perf_counter()
+        pipe = E.PipelinedPredictor(self.model, depth=3)
+        packer = ops.InferPacker(self.device, max_batch=cfg.eval_batch_size, slots=pipe.depth)
+        free = [threading.Semaphore(1) for _ in range(pipe.depth)]       # a slot's pinned buffer is refilled only after the host took its records
+        todo, recs, objs, errors = queue.Queue(), [], [], []
+
+        def consume():
+            while True:
+                item = todo.get()
+                if item is None:
+                    return
+                fut, slot = item
+                try:
+                    obj = fut.result()
+                    recs.append(packer.collect(slot).copy())
+                    objs.append(obj)
+                except BaseException as e:          # noqa: B036  (kept for the submitting thread; the slot is released either way)
+                    errors.append(e)
+                finally:
+                    free[slot].release()
+
+        host = threading.Thread(target=consume, name='vpho-infer-collect')
+        host.start()
+        ident = []                                   # per batch, decided on the HOST batch: (data-set indices or None, paths or None)
+
+        def tap(batches):
+            for b in batches:
+                idx = b.get('index')
+                idx = (idx.cpu() if idx.is_cuda else idx).reshape(-1).long().numpy().copy() if torch.is_tensor(idx) and idx.numel() else None
+                ident.append((idx, b.get('rgb_path')))
+                yield b
+
+        index, paths, sizes, seen, any_index, skipped_obj = [], [], [], 0, loader is None, 0
+        gen = self._eval_batches(None if loader is None else tap(loader), need_gt=False)
+        try:
+            item = next(gen)
+            while not errors:
+                b, _, first = item
+                n = b['rgb'].shape[0]
+                if n > packer.max_batch:
+                    raise ops.VphoError(f'Trainer.infer: a batch of {n} images with --eval_batch_size {packer.max_batch}: the prediction records '
+                                        f'are staged in buffers of eval_batch_size images')
+                idx, rp = ident[-1] if loader is not None else (np.arange(first, first + n, dtype=np.int64), None)
+                any_index = any_index or idx is not None
+                index.append(np.arange(seen, seen + n, dtype=np.int64) if idx is None else idx)
+                if (idx is None) != (not any_index):
+                    raise KeyError("Trainer.infer: some batches carry 'index' and some do not")
+                paths += [''] * n if rp is None else [str(p) for p in rp]
+                sizes.append(n)
+                seen += n
+                want_obj = all(k in b for k in ('gt_obj_rt', 'cam_intr', 'obj_name'))
+                skipped_obj += 0 if want_obj else 1
+                slot = pipe.n % pipe.depth
+                free[slot].acquire()
+
+                def post(out, batch, eng, slot=slot, want_obj=want_obj):
+                    packer.pack(out, batch, slot=slot)                      # on the slot's stream: kernel + copy + event
+                    return E.object_metric_block(out, batch, self.assets).float() if want_obj else None
+
+                todo.put((pipe.submit(b, post), slot))
+                item = gen.send(None)
+        except StopIteration:
+            pass
+        finally:
+            todo.put(None)
+            host.join()
+            pipe.close()
+        if errors:
+            raise errors[0]
+        t_collected = time.perf_counter() - t0           # every record of this rank is in host memory; no file has been touched yet
+        dt = recs[0].dtype if recs else ops.infer_record_dtype()
+        rec = np.concatenate(recs) if recs else np.zeros(0, dt)
+        mine = dict(index=np.concatenate(index) if index else np.zeros(0, np.int64), path=paths, batch_sizes=sizes, has_index=any_index,
+                    **{k: rec[k] for k in INF.RECORD_FIELDS})
+        # object table of the aggregated pose: (n,16) per batch -> rows of the evaluation layout, one small all-gather (rank order = merge order)
+        rows = torch.zeros((seen, E.ROW), device=self.device, dtype=torch.float32)
+        with_obj = bool(objs) and all(o is not None for o in objs)
+        if with_obj:
+            rows[:, E.OBJ_COL:E.OBJ_COL + 16] = torch.cat(objs, 0)
+        if self.world > 1:
+            INF.write_shard(save_dir, self.rank, mine, mine['index'], paths, sizes, any_index)
+            flags = [None] * self.world
+            dist.all_gather_object(flags, (with_obj, seen))
+            with_obj = all(f[0] or f[1] == 0 for f in flags)
+            rows = E.gather_rows(rows)
+            dist.barrier()                               # every shard is complete on disk
+        res = None
+        if self.rank == 0:
+            shards = [mine] if self.world == 1 else [INF.shard_path(save_dir, r) for r in range(self.world)]
+            rec, idx_all, path_all, size_all, order, gaps = INF.merge_shards(shards)
+            if order.size == 0:
+                raise ValueError('Trainer.infer: the loader yielded no batch on any rank')
+            files = INF.write_outputs(save_dir, cfg.clean_data_mode, rec, idx_all, path_all, size_all, order)
+            t_files = time.perf_counter() - t0
+            N = int(order.size)
+            what = 'synthetic images' if loader is None else 'images'
+            print(f'inferred {N} {what} on {self.world} GPU(s): records collected in {t_collected:.2f} s ({N / t_collected:.1f} images/s), '
+                  f'files written after {t_files:.2f} s ({N / t_files:.1f} images/s)')
+            for k, v in files.items():
+                print(f'  {k}: {v}')
+            table = None
+            if with_obj:
+                table = E.summarize(rows.cpu()[torch.from_numpy(order)])['object']
+                print('Object Evaluation: \nMean Pose: \n' + '  '.join(f'{k} {v:.2f}' for k, v in table.items()))
+            else:
+                print("Object Evaluation: skipped (the batches carry no 'gt_obj_rt' / 'gt_obj', 'cam_intr', 'obj_name')")
+            res = {'images': N, 'world': self.world, 'files': files, 'object': table, 'images_per_s': N / t_collected,
+                   'images_per_s_with_files': N / t_files, 'missing_indices': int(gaps.size), 'save_dir': save_dir}
+            print('INFER_JSON ' + json.dumps(res))
+        if self.world > 1:
+            dist.barrier()
+        return res
