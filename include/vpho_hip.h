@@ -520,6 +520,37 @@ VPHO_API int vpho_hand_obj_penetration_f64(const vpho_obj_mesh_tables* t, const 
                                   const int* obj_id, double contact_thresh, double* sd, unsigned char* inside, double* per_image,
                                   void* stream);
 
+/* The same metric for every sampled hypothesis (--eval_best with --eval_physics), appended within ABI version 13.
+ * vpho_obj_mesh_accel holds two conservative filters over the records of vpho_obj_mesh_tables, built on the host
+ * (vpho_amd/physics_eval.py: mesh_accel), objects concatenated:
+ *   parity: the 512 x 512 hash cells in VPHO_PEN_COLUMNS x VPHO_PEN_COLUMNS columns of 512 / VPHO_PEN_COLUMNS cells a side; column
+ *     (X, Y) of object o lists col_tri[col_offset[o * COLUMNS^2 + Y * COLUMNS + X] .. col_offset[.. + 1]): the triangles (indices into
+ *     tri, ascending) whose cell rectangle (fields 15-18) touches the column.  A point walks the list of its own cell's column and
+ *     applies the cell test and the strict containment of the single-pose kernel to every entry.
+ *   nearest: the triangles in Morton order of their centroids, in clusters of VPHO_PEN_CLUSTER (the last one padded with copies of
+ *     its last triangle); cluster k of object o, k in [clu_offset[o], clu_offset[o + 1]), has a bounding sphere clu_sphere[k] =
+ *     (centre xyz, radius) in the model frame, the radius enlarged on the host by (1 + 2^-30) and by 2^-30 of the mesh's bounding-box
+ *     diagonal, and clu_geo[k][VPHO_PEN_CLUSTER][9], bit copies of fields 19-27 of its triangles.  A cluster is skipped when
+ *     |p - centre| > sqrt(best) (1 + 2^-20) + radius; every other one goes through the exact distance of the single-pose kernel.
+ * vpho_hand_obj_penetration_multi_f64: verts [n][S][V][3] fp32, obj_rt [n][S][3][4] fp64, obj_id [n]: hypothesis s of the hand
+ * against hypothesis s of the object.  per_hyp [n][S][4] = what vpho_hand_obj_penetration_f64 gives per_image for the n*S pairs
+ * (same bits; NaN for an obj_id outside [0, n_obj)); sd [n][S][V] and inside [n][S][V] are optional (NULL: nothing is written per
+ * vertex) and have its bits too.  table [n][12] = one | best | mean over the S hypotheses of an image: the four values of hypothesis
+ * 0; min PD, min n_inside, MAX min-sd (the least penetrating hypothesis), max contact; the four means (sums in ascending s, fp64).
+ * A NaN hypothesis makes best and mean NaN.  n == 0 is a no-op.  Deterministic (max / min / count, no atomics). */
+#define VPHO_PEN_COLUMNS 64
+#define VPHO_PEN_CLUSTER 16
+typedef struct vpho_obj_mesh_accel {
+    const int* col_offset;         /* [n_obj * VPHO_PEN_COLUMNS^2 + 1] */
+    const int* col_tri;            /* [col_offset[n_obj * VPHO_PEN_COLUMNS^2]] */
+    const int* clu_offset;         /* [n_obj + 1] */
+    const double* clu_sphere;      /* [clu_offset[n_obj]][4] */
+    const double* clu_geo;         /* [clu_offset[n_obj]][VPHO_PEN_CLUSTER][9] */
+} vpho_obj_mesh_accel;
+VPHO_API int vpho_hand_obj_penetration_multi_f64(const vpho_obj_mesh_tables* t, const vpho_obj_mesh_accel* acc, const float* verts, int n, int S,
+                                        int V, const double* obj_rt, const int* obj_id, double contact_thresh, double* per_hyp,
+                                        double* sd, unsigned char* inside, double* table, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Pseudo-force label optimisation (force_optim.py / lib/engine/force_optimization.py:110-207).
  * vpho_anchor_frames_f32: ForceAnchor.__call__ (lib/utils/physics_fn.py:224-257) -> pts [n][32][3], frames [n][32][3][3]

@@ -12,17 +12,13 @@
 // are bit-for-bit those of the host test.  Max / min / count reductions: exact, so every result is deterministic.
 #include "common.h"
 #include "../../include/vpho_hip.h"
+#include "penetration_common.h"
 
 namespace {
 
 constexpr int PEN_THREADS = 256;
 constexpr int PEN_TILE = 256;                          // triangles staged per LDS tile: 256 x 28 doubles = 56 KB
 constexpr int TS = VPHO_PEN_TRI_STRIDE;
-static_assert(TS == 28, "record layout below");
-
-// record fields (include/vpho_hip.h)
-enum { R_CX = 0, R_CY, R_A00, R_A01, R_A10, R_A11, R_SDET, R_ADET, R_T1X, R_T1Y, R_N0, R_N1, R_SNZ, R_ANZ, R_D0,
-       R_CX0, R_CX1, R_CY0, R_CY1, R_AX, R_AY, R_AZ, R_ABX, R_ABY, R_ABZ, R_ACX, R_ACY, R_ACZ };
 
 struct PenArgs {
     vpho_obj_mesh_tables t;
@@ -35,48 +31,6 @@ struct PenArgs {
     unsigned char* inside;       // (n, V)
     double* per_image;           // (n, 4)
 };
-
-__device__ inline double dot3(double ax, double ay, double az, double bx, double by, double bz) { return ax * bx + ay * by + az * bz; }
-
-// squared distance from p to the triangle (a, a + ab, a + ac); ap = p - a
-__device__ inline double tri_dist2(const double* r, double px, double py, double pz) {
-    const double abx = r[R_ABX], aby = r[R_ABY], abz = r[R_ABZ], acx = r[R_ACX], acy = r[R_ACY], acz = r[R_ACZ];
-    const double apx = px - r[R_AX], apy = py - r[R_AY], apz = pz - r[R_AZ];
-    const double d1 = dot3(abx, aby, abz, apx, apy, apz), d2 = dot3(acx, acy, acz, apx, apy, apz);
-    if (d1 <= 0.0 && d2 <= 0.0) return dot3(apx, apy, apz, apx, apy, apz);                                   // vertex a
-    const double bpx = apx - abx, bpy = apy - aby, bpz = apz - abz;
-    const double d3 = dot3(abx, aby, abz, bpx, bpy, bpz), d4 = dot3(acx, acy, acz, bpx, bpy, bpz);
-    if (d3 >= 0.0 && d4 <= d3) return dot3(bpx, bpy, bpz, bpx, bpy, bpz);                                     // vertex b
-    const double vc = d1 * d4 - d3 * d2;
-    if (vc <= 0.0 && d1 >= 0.0 && d3 <= 0.0) {                                                                // edge ab
-        const double s = d1 / (d1 - d3);
-        const double ex = apx - s * abx, ey = apy - s * aby, ez = apz - s * abz;
-        return dot3(ex, ey, ez, ex, ey, ez);
-    }
-    const double cpx = apx - acx, cpy = apy - acy, cpz = apz - acz;
-    const double d5 = dot3(abx, aby, abz, cpx, cpy, cpz), d6 = dot3(acx, acy, acz, cpx, cpy, cpz);
-    if (d6 >= 0.0 && d5 <= d6) return dot3(cpx, cpy, cpz, cpx, cpy, cpz);                                     // vertex c
-    const double vb = d5 * d2 - d1 * d6;
-    if (vb <= 0.0 && d2 >= 0.0 && d6 <= 0.0) {                                                                // edge ac
-        const double s = d2 / (d2 - d6);
-        const double ex = apx - s * acx, ey = apy - s * acy, ez = apz - s * acz;
-        return dot3(ex, ey, ez, ex, ey, ez);
-    }
-    const double va = d3 * d6 - d5 * d4;
-    if (va <= 0.0 && (d4 - d3) >= 0.0 && (d5 - d6) >= 0.0) {                                                  // edge bc
-        const double s = (d4 - d3) / ((d4 - d3) + (d5 - d6));
-        const double ex = bpx - s * (acx - abx), ey = bpy - s * (acy - aby), ez = bpz - s * (acz - abz);
-        return dot3(ex, ey, ez, ex, ey, ez);
-    }
-    const double den = va + vb + vc;
-    if (!(den > 0.0)) {                                   // zero-area triangle: nearest of its corners (its edges belong to other faces)
-        const double a2 = dot3(apx, apy, apz, apx, apy, apz), b2 = dot3(bpx, bpy, bpz, bpx, bpy, bpz), c2 = dot3(cpx, cpy, cpz, cpx, cpy, cpz);
-        return fmin(a2, fmin(b2, c2));
-    }
-    const double v = vb / den, w = vc / den;                                                                  // face interior
-    const double ex = apx - v * abx - w * acx, ey = apy - v * aby - w * acy, ez = apz - v * abz - w * acz;
-    return dot3(ex, ey, ez, ex, ey, ez);
-}
 
 __global__ __launch_bounds__(PEN_THREADS) void penetration_kernel(const PenArgs a) {
     __shared__ double tile[PEN_TILE * TS];

@@ -27,10 +27,16 @@ ROW_BEST = ROW + MULTI
 # order of ops_names.PHYSICS_COLUMNS: PD (m), n_inside, min sd (m), contact of (aggregated hand, aggregated object), then of (ground-truth
 # hand, ground-truth object).  The columns before them are the same with and without the flag.
 PHYS = 8
+# with physics_multi (both command-line flags, cfg.eval_best AND cfg.eval_physics; an explicit argument of Trainer.eval / metric_rows
+# otherwise, so that callers who pass the two older flags themselves get the rows they always got) every row carries PHYS_MULTI more
+# columns, last (after the PHYS block), in the order of
+# ops_names.PHYSICS_MULTI_COLUMNS: PD (m), n_inside, min sd (m), contact of (hand hypothesis s, object hypothesis s) reduced per image to
+# hypothesis 0, best-of-S and mean-of-S.  The 96 columns before them are the same with and without the block.
+PHYS_MULTI = 12
 
 
-def row_width(eval_best=False, eval_physics=False):
-    return (ROW_BEST if eval_best else ROW) + (PHYS if eval_physics else 0)
+def row_width(eval_best=False, eval_physics=False, physics_multi=False):
+    return (ROW_BEST if eval_best else ROW) + (PHYS if eval_physics else 0) + (PHYS_MULTI if eval_best and eval_physics and physics_multi else 0)
 
 
 def mje_mm(pd, gt):
@@ -105,14 +111,17 @@ def multi_hypothesis_block(out, data, gt_joint, gt_vert, assets=None):
 _PHYSICS = {}
 
 
-def physics_meter(assets, device):
-    """the HandObjectPenetration of an asset set on a device, built once (object meshes: physics_eval.object_meshes)"""
+def physics_meter(assets, device, multi=False):
+    """the HandObjectPenetration of an asset set on a device, built once (object meshes: physics_eval.object_meshes); its acceleration
+    tables for the multi-hypothesis kernel only with ``multi`` (eval_best and eval_physics together), once as well"""
     key = (id(assets), str(device))
     if key not in _PHYSICS:
         from . import ops
         from .configs.args import cfg
         from .physics_eval import object_meshes
-        _PHYSICS[key] = ops.HandObjectPenetration(object_meshes(assets, cfg.asset_root), device)
+        _PHYSICS[key] = ops.HandObjectPenetration(object_meshes(assets, cfg.asset_root), device, accel=False)
+    if multi:
+        _PHYSICS[key].build_accel()
     return _PHYSICS[key]
 
 
@@ -135,12 +144,39 @@ def physics_block(pp, out, data, gt_vert, meshes):
     return blk
 
 
-def metric_rows(out, data, gt_joint, gt_vert, first_index, assets=None, eval_best=False, eval_physics=False):
+def hypotheses_to_camera(x, root_joint, is_right):
+    """(bs, S, N, 3) model-frame hand candidates -> camera frame: postprocess' un-flip of left hands along x + root joint, per hypothesis"""
+    sgn = torch.where(is_right.bool(), 1.0, -1.0).to(x.dtype)[:, None, None]
+    v = x.clone()
+    v[..., 0] = v[..., 0] * sgn
+    return v + root_joint[:, None, None]
+
+
+def physics_multi_block(out, data, meshes):
+    """(bs, PHYS_MULTI) fp32: penetration and contact of every sampled hypothesis -- hand candidate s
+    (out['diff_final_hand_vert'][:, s], un-flipped + root as the multi-hypothesis hand metrics) against object candidate s
+    (obj_9D_to_mat + root of out['diff_final_obj_6d'][:, s]) -- reduced per image to hypothesis 0 | best-of-S | mean-of-S by ONE
+    HandObjectPenetration.multi launch pair.  ``meshes``: physics_meter(..., multi=True)."""
+    from . import ops
+    from .configs.args import cfg
+    hv = out['diff_final_hand_vert']
+    if not hv.is_cuda:
+        raise RuntimeError('physics_multi_block: the penetration metrics run on the GPU only (no CPU path)')
+    bs, S = hv.shape[:2]
+    root = data['root_joint'].float().contiguous()
+    verts = hypotheses_to_camera(hv.float(), root, data['is_right']).contiguous()
+    pd_rt = ops.obj_9d_to_rt(out['diff_final_obj_6d'].reshape(bs * S, 9).double().contiguous(), root.repeat_interleave(S, 0).contiguous()).view(bs, S, 3, 4)
+    table, _ = meshes.multi(verts, pd_rt, meshes.obj_ids(data['obj_name']), contact_thresh=float(cfg.physics_contact_thresh))
+    return table.float()
+
+
+def metric_rows(out, data, gt_joint, gt_vert, first_index, assets=None, eval_best=False, eval_physics=False, physics_multi=False):
     """(bs, ROW) fp32 on the model's device; (bs, ROW_BEST) with eval_best (multi_hypothesis_block appended); PHYS more columns with
-    eval_physics (physics_block, last)."""
+    eval_physics (physics_block), and with both and ``physics_multi`` PHYS_MULTI more (physics_multi_block, last; without it that block
+    and its launch are left out: the rows of the two flags as they always were)."""
     pp = postprocess(out, data['root_joint'], data['is_right'])
     bs = gt_joint.shape[0]
-    rows = torch.empty((bs, row_width(eval_best, eval_physics)), device=gt_joint.device, dtype=torch.float32)
+    rows = torch.empty((bs, row_width(eval_best, eval_physics, physics_multi)), device=gt_joint.device, dtype=torch.float32)
     if torch.is_tensor(first_index):                 # per-image ids (a loader batch that is not a run of the data set)
         rows[:, 0] = first_index.to(device=rows.device, dtype=torch.float32).reshape(bs)
     else:
@@ -166,14 +202,17 @@ def metric_rows(out, data, gt_joint, gt_vert, first_index, assets=None, eval_bes
     if eval_physics:
         if assets is None:
             raise ValueError('metric_rows: eval_physics needs the asset tables (object meshes)')
-        rows[:, -PHYS:] = physics_block(pp, out, data, gt_vert, physics_meter(assets, gt_joint.device))
+        p0 = ROW_BEST if eval_best else ROW
+        rows[:, p0:p0 + PHYS] = physics_block(pp, out, data, gt_vert, physics_meter(assets, gt_joint.device))
+        if eval_best and physics_multi:
+            rows[:, p0 + PHYS:] = physics_multi_block(out, data, physics_meter(assets, gt_joint.device, multi=True))
     from .configs.args import cfg
     if cfg.aggregation_mode_hand == '2D_pt_joint':
         # that mode fuses joints only; its vertices are the reference's all-zero mesh (aggregation.py:364-366): no vertex metric of it
         rows[:, 4] = float('nan')
         rows[:, 10] = float('nan')
         if eval_physics:
-            rows[:, -PHYS:-PHYS + 4] = float('nan')
+            rows[:, p0:p0 + 4] = float('nan')
     return rows
 
 
@@ -296,8 +335,14 @@ def summarize(rows):
     from .ops_names import OBJ_METRIC_NAMES
     obj = rows[:, OBJ_COL:OBJ_COL + 16].double().mean(0)
     res['object'] = _object_table(obj)
-    if rows.shape[1] in (ROW + PHYS, ROW_BEST + PHYS):
-        res['physics'] = _physics_table(rows[:, -PHYS:])
+    p0 = {ROW + PHYS: ROW, ROW_BEST + PHYS: ROW_BEST, ROW_BEST + PHYS + PHYS_MULTI: ROW_BEST}.get(rows.shape[1])
+    if p0 is not None:
+        from .ops_names import MULTI_TABLES, PHYSICS_SOURCES
+        res['physics'] = _physics_table(rows[:, p0:p0 + PHYS], PHYSICS_SOURCES)
+        if rows.shape[1] > p0 + PHYS:
+            # every hypothesis' penetration reduced per image (physics_multi_block): for mean_of_S an image counts as penetrating when
+            # its mean inside-vertex count is > 0, and its contact is the fraction of its hypotheses in contact
+            res['physics'].update(_physics_table(rows[:, p0 + PHYS:], MULTI_TABLES))
     if rows.shape[1] >= ROW_BEST:
         # multi-hypothesis tables (train_diff_hand_obj.py:466-469,494-496 one_candidate; TesterObject.postprocess best_candidate_pose),
         # over all images: hand in mm, object in the units of the object table
@@ -315,13 +360,13 @@ def _object_table(obj):
             for i, k in enumerate(OBJ_METRIC_NAMES)}
 
 
-def _physics_table(blk):
-    """physics table over all images, per source (pred / gt): mean and largest PD (mm), % of images with a hand vertex inside the object,
-    mean inside-vertex count, % of images in contact (NaN for a source without values, e.g. gt without object ground truth)"""
-    from .ops_names import PHYSICS_SOURCES
+def _physics_table(blk, names):
+    """physics table over all images, per source (pred / gt; one_candidate / best_of_S / mean_of_S): mean and largest PD (mm), % of images
+    with a hand vertex inside the object, mean inside-vertex count, % of images in contact (NaN for a source without values, e.g. gt
+    without object ground truth)"""
     blk = blk.double()
     res = {}
-    for s, name in enumerate(PHYSICS_SOURCES):
+    for s, name in enumerate(names):
         b = blk[:, 4 * s:4 * s + 4]
         res[name] = dict(PD_mm=float(b[:, 0].mean() * 1000.0), PD_max_mm=float(b[:, 0].max() * 1000.0) if b.shape[0] else float('nan'),
                          penetration_rate_pct=float((b[:, 1] > 0).double().mean() * 100.0) if not b[:, 1].isnan().any() else float('nan'),

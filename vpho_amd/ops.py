@@ -1206,12 +1206,18 @@ class ObjMeshTables(C.Structure):
     _fields_ = [('tri', C.c_void_p), ('tri_offset', C.c_void_p), ('scale', C.c_void_p), ('translate', C.c_void_p), ('n_obj', I)]
 
 
+class ObjMeshAccel(C.Structure):
+    _fields_ = [('col_offset', C.c_void_p), ('col_tri', C.c_void_p), ('clu_offset', C.c_void_p), ('clu_sphere', C.c_void_p), ('clu_geo', C.c_void_p)]
+
+
 class HandObjectPenetration:
     """Hand-object penetration and contact (--eval_physics) on the device: per-triangle tables of every object mesh,
     built once (physics_eval.mesh_tables), + thin wrapper of vpho_hand_obj_penetration_f64.  ``meshes``: {name: {'verts', 'faces'}}
-    (physics_eval.object_meshes)."""
+    (physics_eval.object_meshes).  ``multi`` scores every sampled hypothesis (vpho_hand_obj_penetration_multi_f64) through the
+    acceleration tables of physics_eval.mesh_accel, built here once as well (``accel=False`` leaves them out: ``multi`` then raises until
+    ``build_accel()`` is called)."""
 
-    def __init__(self, meshes, device):
+    def __init__(self, meshes, device, accel=True):
         import numpy as np
         from .physics_eval import mesh_tables
         self.names = list(meshes.keys())
@@ -1224,9 +1230,32 @@ class HandObjectPenetration:
         self.scale = d(np.stack([t[1] for t in tabs]))
         self.translate = d(np.stack([t[2] for t in tabs]))
         self.n_tri = counts
+        self.device = device
+        self._tabs, self.acc = tabs, None
+        if accel:
+            self.build_accel()
         self.c = ObjMeshTables(self.tri.data_ptr(), self.tri_offset.data_ptr(), self.scale.data_ptr(), self.translate.data_ptr(),
                                len(self.names))
-        self.device = device
+
+    def build_accel(self):
+        """vpho_obj_mesh_accel of all objects, once: per-object tables concatenated, triangle indices made global"""
+        import numpy as np
+        from .physics_eval import mesh_accel
+        if self.acc is not None:
+            return
+        tabs, counts, device = self._tabs, self.n_tri, self.device
+        acc = [mesh_accel(t[0]) for t in tabs]
+        tri0 = np.concatenate([[0], np.cumsum(counts)])
+        i32 = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.int32)).to(device)
+        f64 = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64)).to(device)
+        ent0 = np.concatenate([[0], np.cumsum([len(a['col_tri']) for a in acc])])
+        self.col_offset = i32(np.concatenate([a['col_offset'][:-1].astype(np.int64) + ent0[i] for i, a in enumerate(acc)] + [ent0[-1:]]))
+        self.col_tri = i32(np.concatenate([a['col_tri'].astype(np.int64) + tri0[i] for i, a in enumerate(acc)]))
+        self.clu_offset = i32(np.concatenate([[0], np.cumsum([len(a['sphere']) for a in acc])]))
+        self.clu_sphere = f64(np.concatenate([a['sphere'] for a in acc]))
+        self.clu_geo = f64(np.concatenate([a['geo'] for a in acc]))
+        self.acc = ObjMeshAccel(self.col_offset.data_ptr(), self.col_tri.data_ptr(), self.clu_offset.data_ptr(), self.clu_sphere.data_ptr(),
+                                self.clu_geo.data_ptr())
 
     def obj_ids(self, names):
         """class indices of a batch as a device tensor (pinned host memory, asynchronous copy on the caller's stream, as
@@ -1255,6 +1284,30 @@ class HandObjectPenetration:
         _call('vpho_hand_obj_penetration_f64', C.byref(self.c), _f32(verts), I(n), I(V), _f64(obj_rt), _i32(obj_id), C.c_double(contact_thresh),
               _f64(sd), _u8(inside), _f64(per))
         return (per, sd, inside) if per_vertex else per
+
+    def multi(self, verts, obj_rt, obj_id, per_vertex=False, contact_thresh=0.005):
+        """Every sampled hypothesis: verts (n,S,V,3) fp32 and obj_rt (n,S,3,4) fp64 in the camera frame, hypothesis s of the hand against
+        hypothesis s of the object; obj_id as in __call__ (one per image).  -> table (n,12) fp64 = one | best | mean over S of
+        (PD, n_inside, min sd, contact): hypothesis 0; min PD, min n_inside, max min-sd, max contact; the four means -- and per_hyp
+        (n,S,4) fp64, the bits __call__ gives for the n*S pairs.  With per_vertex also sd (n,S,V) fp64 and inside (n,S,V) uint8;
+        without it nothing is written per vertex."""
+        if self.acc is None:
+            raise VphoError('HandObjectPenetration.multi: built with accel=False (call build_accel() first)')
+        n, S, V = verts.shape[:3]
+        assert verts.shape == (n, S, V, 3) and obj_rt.shape == (n, S, 3, 4)
+        if not torch.is_tensor(obj_id):
+            ids = [int(i) for i in obj_id]
+            if len(ids) != n or any(i < 0 or i >= len(self.names) for i in ids):
+                raise VphoError(f'HandObjectPenetration: object ids {ids} outside [0, {len(self.names)}) or not one per image')
+            obj_id = _ids_to_device(ids, self.device)
+        assert obj_id.shape == (n,)
+        table = _new((n, 12), obj_rt, torch.float64)
+        per = _new((n, S, 4), obj_rt, torch.float64)
+        sd = _new((n, S, V), obj_rt, torch.float64) if per_vertex else None
+        inside = _new((n, S, V), obj_rt, torch.uint8) if per_vertex else None
+        _call('vpho_hand_obj_penetration_multi_f64', C.byref(self.c), C.byref(self.acc), _f32(verts), I(n), I(S), I(V), _f64(obj_rt), _i32(obj_id),
+              C.c_double(contact_thresh), _f64(per), _f64(sd) if per_vertex else None, _u8(inside) if per_vertex else None, _f64(table))
+        return (table, per, sd, inside) if per_vertex else (table, per)
 
 
 # ----------------------------------------------------------------------------------------------- score-network training

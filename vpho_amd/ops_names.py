@@ -18,3 +18,8 @@ PHYSICS_COLUMNS = tuple(f'physics/{s}/{k}' for s in PHYSICS_SOURCES for k in PHY
 # the summarize / EVAL_JSON table 'physics', per source: mean PD (mm), largest PD (mm), share of images with a vertex inside (%), mean
 # number of inside vertices, share of images in contact (%)
 PHYSICS_TABLE = ('PD_mm', 'PD_max_mm', 'penetration_rate_pct', 'inside_verts', 'contact_rate_pct')
+# the block that evaluate.metric_rows appends last with eval_best AND eval_physics: the same four values for every sampled hypothesis (hand
+# candidate s against object candidate s), per image reduced to hypothesis 0, best-of-S (min PD, min n_inside, MAX min_sd: the least
+# penetrating hypothesis, max contact) and mean-of-S (contact becomes the fraction of hypotheses in contact); the 'physics' table gains
+# the three MULTI_TABLES entries beside 'pred' and 'gt', each with the PHYSICS_TABLE keys
+PHYSICS_MULTI_COLUMNS = tuple(f'physics/{t}/{k}' for t in MULTI_TABLES for k in PHYSICS_METRIC_NAMES)

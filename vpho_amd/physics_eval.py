@@ -16,6 +16,10 @@ from .assets import AssetError
 RESOLUTION = 512              # VPHO_PEN_RESOLUTION
 TRI_STRIDE = 28               # VPHO_PEN_TRI_STRIDE
 BOX_SUBDIV = 16               # synthetic box meshes: 16 x 16 quads per side, 3 072 triangles
+COLUMNS = 64                  # VPHO_PEN_COLUMNS: the 512 x 512 hash cells in 64 x 64 columns of 8 x 8 cells
+CLUSTER = 16                  # VPHO_PEN_CLUSTER: triangles per bounding sphere
+REACH_GROW = 1.0 + 2.0 ** -20  # the kernel's relative slack on sqrt(best) (csrc/penetration_multi.hip)
+RADIUS_GROW = 2.0 ** -30      # the radii's relative slack, and their absolute one in units of the mesh's bounding-box diagonal
 
 
 def box_mesh(bbox3d, sub=BOX_SUBDIV):
@@ -53,6 +57,25 @@ def box_mesh(bbox3d, sub=BOX_SUBDIV):
     return xyz, np.array(faces, np.int64)
 
 
+def torus_mesh(nu, nv, major=1.0, minor=0.4, drop_quad=None):
+    """Closed triangle mesh of a torus about the y axis: nu x nv quads of two triangles (2 nu nv triangles, nu nv vertices), ring radius
+    ``major`` and tube radius ``minor``; non-convex, so a z-ray crosses it 0, 2 or 4 times.  ``drop_quad``: index of a quad to leave out
+    (an open mesh).  No random numbers."""
+    u = np.arange(nu) * (2 * np.pi / nu) + 0.1
+    v = np.arange(nv) * (2 * np.pi / nv) + 0.2
+    uu, vv = np.meshgrid(u, v, indexing='ij')
+    ring = major + minor * np.cos(vv)
+    verts = np.stack([ring * np.cos(uu), minor * np.sin(vv), ring * np.sin(uu)], -1).reshape(-1, 3)
+    faces = []
+    for i in range(nu):
+        for j in range(nv):
+            if drop_quad is not None and i * nv + j == drop_quad:
+                continue
+            a, b, c, d = i * nv + j, ((i + 1) % nu) * nv + j, ((i + 1) % nu) * nv + (j + 1) % nv, i * nv + (j + 1) % nv
+            faces += [(a, b, c), (a, c, d)]
+    return verts, np.array(faces, np.int64)
+
+
 def mesh_tables(verts, faces):
     """(tri (T, TRI_STRIDE) fp64, scale (3,), translate (3,)) of one mesh; field layout of include/vpho_hip.h."""
     triangles = np.asarray(verts, np.float64)[np.asarray(faces, np.int64)].astype(np.float64)
@@ -86,6 +109,108 @@ def mesh_tables(verts, faces):
                           a, ab, ac], axis=1)
     assert tri.shape == (n_tri, TRI_STRIDE)
     return np.ascontiguousarray(tri), scale, translate
+
+
+def mesh_accel(tri):
+    """The two conservative filters of ``vpho_obj_mesh_accel`` (include/vpho_hip.h) over the records ``tri`` (T, TRI_STRIDE) of one mesh,
+    triangle indices local to the mesh; deterministic (stable sorts, no random numbers):
+      col_offset (COLUMNS^2 + 1,), col_tri: per xy column of 512 / COLUMNS hash cells a side (row-major, y first) the triangles whose
+        cell rectangle (fields 15-18) touches it, ascending;
+      order (C * CLUSTER,): the triangles in Morton order of their centroids, the last cluster padded with copies of its last triangle;
+      sphere (C, 4): per cluster of CLUSTER consecutive entries of ``order`` the centre of its corners' bounding box and the largest
+        corner distance from it, enlarged by (1 + RADIUS_GROW) and by RADIUS_GROW bounding-box diagonals (the slack the kernel's skip
+        test relies on, derived in csrc/penetration_multi.hip);
+      geo (C, CLUSTER, 9): bit copies of fields 19-27 in that order."""
+    tri = np.ascontiguousarray(tri, np.float64)
+    n_tri = tri.shape[0]
+    cells = RESOLUTION // COLUMNS
+    x0, x1, y0, y1 = (tri[:, 15 + i].astype(np.int64) // cells for i in range(4))
+    w = x1 - x0 + 1
+    cnt = w * (y1 - y0 + 1)
+    t_idx = np.repeat(np.arange(n_tri), cnt)
+    local = np.arange(int(cnt.sum())) - np.repeat(np.cumsum(cnt) - cnt, cnt)
+    col = (y0[t_idx] + local // w[t_idx]) * COLUMNS + x0[t_idx] + local % w[t_idx]
+    by_col = np.lexsort((t_idx, col))                                   # by column, then ascending triangle index
+    col_offset = np.searchsorted(col[by_col], np.arange(COLUMNS * COLUMNS + 1)).astype(np.int32)
+    col_tri = t_idx[by_col].astype(np.int32)
+    # Morton order of the centroids on a 1024^3 lattice over the corners' bounding box
+    a, ab, ac = tri[:, 19:22], tri[:, 22:25], tri[:, 25:28]
+    corners = np.stack([a, a + ab, a + ac], 1)
+    lo, hi = corners.reshape(-1, 3).min(0), corners.reshape(-1, 3).max(0)
+    ext = np.where(hi > lo, hi - lo, 1.0)
+    g = np.clip(((corners.mean(1) - lo) / ext * 1024.0).astype(np.int64), 0, 1023)
+    code = np.zeros(n_tri, np.int64)
+    for bit in range(10):
+        for k in range(3):
+            code |= ((g[:, k] >> bit) & 1) << (3 * bit + k)
+    order = np.argsort(code, kind='stable')
+    n_clu = (n_tri + CLUSTER - 1) // CLUSTER
+    order = np.concatenate([order, np.full(n_clu * CLUSTER - n_tri, order[-1])])
+    cc = corners[order].reshape(n_clu, 3 * CLUSTER, 3)
+    centre = (cc.min(1) + cc.max(1)) / 2.0
+    r0 = np.sqrt(((cc - centre[:, None]) ** 2).sum(-1)).max(1)
+    radius = r0 * (1.0 + RADIUS_GROW) + RADIUS_GROW * np.sqrt(((hi - lo) ** 2).sum())
+    return dict(col_offset=col_offset, col_tri=col_tri, order=order.astype(np.int32),
+                sphere=np.ascontiguousarray(np.concatenate([centre, radius[:, None]], 1)),
+                geo=np.ascontiguousarray(tri[order, 19:28].reshape(n_clu, CLUSTER, 9)))
+
+
+def parity_candidates(acc, scale, translate, pts):
+    """Host restatement of the kernel's parity walk: (P, T) bool, the triangles of the column list of every point's own hash cell
+    (none for a point outside [0, 512]^3 or on its far faces: no cell).  ``pts`` (P, 3) in the model frame."""
+    q = scale * np.asarray(pts, np.float64) + translate
+    n_tri = int(acc['order'].max()) + 1
+    out = np.zeros((len(q), n_tri), bool)
+    ok = np.all((0 <= q) & (q <= RESOLUTION), axis=1)
+    cells = RESOLUTION // COLUMNS
+    for i in np.nonzero(ok)[0]:
+        cx, cy = int(q[i, 0]), int(q[i, 1])
+        if cx < RESOLUTION and cy < RESOLUTION:
+            col = (cy // cells) * COLUMNS + cx // cells
+            out[i, acc['col_tri'][acc['col_offset'][col]:acc['col_offset'][col + 1]]] = True
+    return out
+
+
+def _tri_dist2(p, g):
+    """squared distances of points p (P, 1, 3) to the triangles g (1, M, 9) = (a, b - a, c - a): closest point by Voronoi regions
+    (Ericson 5.1.5), the first matching region in the kernel's order wins"""
+    a, ab, ac = g[..., 0:3], g[..., 3:6], g[..., 6:9]
+    dot = lambda x, y: (x * y).sum(-1)
+    ap = p - a
+    bp, cp = ap - ab, ap - ac
+    d1, d2, d3, d4, d5, d6 = dot(ab, ap), dot(ac, ap), dot(ab, bp), dot(ac, bp), dot(ab, cp), dot(ac, cp)
+    vc, vb, va = d1 * d4 - d3 * d2, d5 * d2 - d1 * d6, d3 * d6 - d5 * d4
+    sq = lambda e: dot(e, e)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        den = va + vb + vc
+        res = np.where(den > 0, sq(ap - (vb / den)[..., None] * ab - (vc / den)[..., None] * ac), np.minimum(sq(ap), np.minimum(sq(bp), sq(cp))))
+        res = np.where((va <= 0) & (d4 - d3 >= 0) & (d5 - d6 >= 0), sq(bp - ((d4 - d3) / ((d4 - d3) + (d5 - d6)))[..., None] * (ac - ab)), res)
+        res = np.where((vb <= 0) & (d2 >= 0) & (d6 <= 0), sq(ap - (d2 / (d2 - d6))[..., None] * ac), res)
+        res = np.where((d6 >= 0) & (d5 <= d6), sq(cp), res)
+        res = np.where((vc <= 0) & (d1 >= 0) & (d3 <= 0), sq(ap - (d1 / (d1 - d3))[..., None] * ab), res)
+        res = np.where((d3 >= 0) & (d4 <= d3), sq(bp), res)
+    return np.where((d1 <= 0) & (d2 <= 0), sq(ap), res)
+
+
+def nearest_candidates(acc, pts):
+    """Host restatement of the kernel's nearest-triangle walk: the cluster with the nearest centre first, then the clusters in order,
+    skipping those with |p - centre| > sqrt(best) REACH_GROW + radius.  -> (visited (P, T) bool, best (P,) squared distance).
+    ``pts`` (P, 3) in the model frame."""
+    p = np.asarray(pts, np.float64)
+    sphere, geo = acc['sphere'], acc['geo']
+    order = acc['order'].reshape(len(sphere), CLUSTER)
+    visited = np.zeros((len(p), int(acc['order'].max()) + 1), bool)
+    D2 = ((p[:, None, :] - sphere[None, :, :3]) ** 2).sum(-1)
+    seed = D2.argmin(1)                                                  # the first minimum, as the kernel's strict compare
+    best = _tri_dist2(p[:, None, :], geo[seed]).min(1)
+    visited[np.arange(len(p))[:, None], order[seed]] = True
+    for k in range(len(sphere)):
+        lim = np.sqrt(best) * REACH_GROW + sphere[k, 3]
+        go = np.nonzero((seed != k) & ~(D2[:, k] > lim * lim))[0]
+        if len(go):
+            best[go] = np.minimum(best[go], _tri_dist2(p[go, None, :], geo[k][None]).min(1))
+            visited[go[:, None], order[k][None, :]] = True
+    return visited, best
 
 
 def object_meshes(assets, asset_root='asset'):

@@ -214,16 +214,22 @@ class Trainer:
             seen += n
 
     @torch.no_grad()
-    def eval(self, loader=None, eval_best=None, eval_physics=None):
+    def eval(self, loader=None, eval_best=None, eval_physics=None, physics_multi=None):
         """``evaluate(testing_dataloader)`` (train_diff_hand_obj.py:202-357).  ``loader``: see ``_eval_batches``; default synthetic.
         ``eval_best`` (default: cfg.eval_best, the reference's is_eval_best): also score every sampled hypothesis and report the
         one_candidate, best_of_S and mean_of_S tables (rows of evaluate.ROW_BEST columns).  ``eval_physics`` (default:
-        cfg.eval_physics): also report hand-object penetration and contact, the ``physics`` table (evaluate.PHYS more columns, last)."""
+        cfg.eval_physics): also report hand-object penetration and contact, the ``physics`` table (evaluate.PHYS more columns, last);
+        ``physics_multi`` (default: cfg.eval_best and cfg.eval_physics, i.e. both command-line flags; it needs both of the above):
+        every sampled hypothesis' penetration as well (evaluate.PHYS_MULTI more columns, last; the ``physics`` table gains
+        one_candidate, best_of_S and mean_of_S).  A caller that passes eval_best / eval_physics itself gets the rows it always got
+        unless it asks for the new block too."""
         from .configs.args import cfg
         eval_best = bool(cfg.eval_best if eval_best is None else eval_best)
         eval_physics = bool(cfg.eval_physics if eval_physics is None else eval_physics)
+        physics_multi = bool((cfg.eval_best and cfg.eval_physics) if physics_multi is None else physics_multi) and eval_best and eval_physics
         if eval_physics:
-            E.physics_meter(self.assets, self.device)          # object meshes and their tables, once, before the timed loop
+            # object meshes and their tables (with eval_best also the multi-hypothesis kernel's), once, before the timed loop
+            E.physics_meter(self.assets, self.device, multi=physics_multi)
         rows = []
         t0 = time.perf_counter()
         # three batches in flight (independent images; see evaluate.PipelinedPredictor)
@@ -238,10 +244,10 @@ class Trainer:
                     # synthetic run: batch 0 provides the ground truth (its own regression output), so it is evaluated first
                     out0 = pipe.submit(b).result()
                     gt = (out0['reg_hand_joint'] + b['root_joint'][:, None], out0['reg_hand_vert'] + b['root_joint'][:, None])
-                    rows.append(E.metric_rows(out0, b, gt[0], gt[1], first, self.assets, eval_best, eval_physics))
+                    rows.append(E.metric_rows(out0, b, gt[0], gt[1], first, self.assets, eval_best, eval_physics, physics_multi))
                 else:
                     futs.append(pipe.submit(b, lambda out, batch, eng, first=first, gt=gt: E.metric_rows(out, batch, gt[0], gt[1], first, self.assets,
-                                                                                                    eval_best, eval_physics)))
+                                                                                                    eval_best, eval_physics, physics_multi)))
                 item = gen.send(gt)
         except StopIteration:
             pass
@@ -249,7 +255,7 @@ class Trainer:
         pipe.close()
         # a rank whose shard is empty still takes part in the collective (with zero rows: the ragged gather carries the counts first);
         # raising here would leave the other ranks blocked in their all-gather.  Only an evaluation without ANY image is an error
-        mine = torch.cat(rows, 0) if rows else torch.zeros((0, E.row_width(eval_best, eval_physics)), device=self.device, dtype=torch.float32)
+        mine = torch.cat(rows, 0) if rows else torch.zeros((0, E.row_width(eval_best, eval_physics, physics_multi)), device=self.device, dtype=torch.float32)
         rows = E.gather_rows(mine)
         if rows.shape[0] == 0:
             raise ValueError('Trainer.eval: the loader yielded no batch on any rank')
