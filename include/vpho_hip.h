@@ -551,6 +551,31 @@ VPHO_API int vpho_hand_obj_penetration_multi_f64(const vpho_obj_mesh_tables* t, 
                                         int V, const double* obj_rt, const int* obj_id, double contact_thresh, double* per_hyp,
                                         double* sd, unsigned char* inside, double* table, void* stream);
 
+/* Hand-object intersection volume (--eval_volume), appended within ABI version 13.  Per (hand, object pose) pair, in
+ * the object's model frame: the hand mesh is the posed vertices q_v = R^T (v - t) (fp64, the arithmetic of vpho_hand_obj_penetration_f64)
+ * with `faces`, ONE closed triangle list shared by all pairs ([F][3] vertex indices in [0, V); vpho_amd/physics_eval.py: hand_faces);
+ * the object is a SOLID point set: the centres of the cells of a lattice of pitch h over the object's mesh bbox that lie inside the object
+ * (fp32, objects concatenated; physics_eval.solid_lattice + the single-pose kernel at identity pose).  inside_hand(c) is the z-ray
+ * parity rule above applied to the posed hand mesh in ITS OWN hash frame (bbox of the q_v by min / max, scale = 511 / (max - min),
+ * translate = 0.5 - scale * min, the 19 parity fields per face in the order of operations of physics_eval.mesh_tables).
+ * out [n][2] = n_cells (the number of solid centres of the pair's object inside the hand, an integer) | IV = ((h * h) * h) * n_cells, one
+ * fp64 product (m^3).  flags (optional, NULL: nothing is written per centre) [n][solids->max_pts] = 0 / 1 per centre of the pair's object
+ * (0 behind its last centre).  An obj_id outside [0, n_obj), which cannot be refused without a host sync, or a hand vertex that is not a
+ * finite number gives NaN in both columns and flags = 0.  workspace: vpho_hand_obj_intersection_workspace_bytes(n, F) bytes (-1 on a bad
+ * argument): [n][F][VPHO_VOL_TRI_STRIDE] fp64 records + [n][6] fp64 scale | translate + [n][2] int (count | bad mesh).  V, F and n are free;
+ * F == 0, pitch <= 0 or a face index outside [0, V) (checked on the device: NaN rows) are errors; n == 0 is a no-op.  Deterministic
+ * (min / max and integer adds only). */
+#define VPHO_VOL_TRI_STRIDE 19
+typedef struct vpho_obj_solids {
+    const float* pts;              /* [pt_offset[n_obj]][3] */
+    const int* pt_offset;          /* [n_obj + 1] */
+    int n_obj, max_pts;            /* max_pts = the largest per-object number of centres */
+} vpho_obj_solids;
+VPHO_API long long vpho_hand_obj_intersection_workspace_bytes(int n, int F);
+VPHO_API int vpho_hand_obj_intersection_f64(const vpho_obj_mesh_tables* t, const vpho_obj_solids* solids, const int* faces, int F, const float* verts,
+                                   int n, int V, const double* obj_rt, const int* obj_id, double pitch, double* out, unsigned char* flags,
+                                   void* workspace, long long workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Pseudo-force label optimisation (force_optim.py / lib/engine/force_optimization.py:110-207).
  * vpho_anchor_frames_f32: ForceAnchor.__call__ (lib/utils/physics_fn.py:224-257) -> pts [n][32][3], frames [n][32][3][3]

@@ -38,8 +38,25 @@ def _unit(v):
     return v / (np.linalg.norm(v, axis=-1, keepdims=True) + 1e-12)
 
 
+def hull_faces(points):
+    """(F, 3) int64: the convex hull of a point cloud as a closed, outward-oriented triangle list, rows sorted lexicographically (each
+    row rotated so that its smallest index comes first: the winding is kept).  The synthetic MANO is a scattered cloud without a surface;
+    its hull is a closed surface of plausible size for benchmarks -- a mitten, not a hand."""
+    from scipy.spatial import ConvexHull                       # only the synthetic table needs it
+    pts = np.asarray(points, np.float64)
+    hull = ConvexHull(pts)
+    f = hull.simplices.astype(np.int64)
+    tri = pts[f]
+    # outward: the normal (b - a) x (c - a) points along the facet's outward equation normal
+    flip = (np.cross(tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0]) * hull.equations[:, :3]).sum(1) < 0
+    f[flip] = f[flip][:, [0, 2, 1]]
+    k = f.argmin(1)
+    f = np.stack([f[np.arange(len(f)), (k + i) % 3] for i in range(3)], 1)
+    return np.ascontiguousarray(f[np.lexsort((f[:, 2], f[:, 1], f[:, 0]))])
+
+
 def synthetic_mano(rng):
-    """Hand-like MANO tables: 16-joint skeleton, 778 vertices scattered around the bones."""
+    """Hand-like MANO tables: 16-joint skeleton, 778 vertices scattered around the bones; ``faces``: their convex hull (hull_faces)."""
     # finger base positions / directions in MANO order (index, middle, pinky, ring, thumb), metres
     base = np.array([[0.095, 0.005, 0.025], [0.095, 0.003, 0.003], [0.080, -0.002, -0.038],
                      [0.090, 0.000, -0.018], [0.025, -0.010, 0.035]])
@@ -95,7 +112,7 @@ def synthetic_mano(rng):
     posedirs = rng.normal(0, 0.0008, size=(nv, 3, 135))
     return dict(v_template=v.astype(np.float32), shapedirs=shapedirs.astype(np.float32),
                 posedirs=posedirs.astype(np.float32), J_regressor=Jr.astype(np.float32),
-                weights=W.astype(np.float32))
+                weights=W.astype(np.float32), faces=hull_faces(v.astype(np.float32)))
 
 
 def synthetic_ycb(rng):
@@ -193,7 +210,8 @@ def load_assets(asset_root='asset', seed=0):
     """The three static tables of the model in the reference's on-disk formats, relative to ``asset_root`` (the reference opens them
     relative to the CWD at import time, quirk Q9):
 
-    * ``mano_v1_2/models/MANO_RIGHT.pkl`` (manopth's ManoLayer, head_mano.py:48-55; unpickling the licensed file needs ``chumpy``)
+    * ``mano_v1_2/models/MANO_RIGHT.pkl`` (manopth's ManoLayer, head_mano.py:48-55; unpickling the licensed file needs ``chumpy``);
+      besides the five arrays its faces ``f`` -> ``assets['mano']['faces']`` (F, 3) int64 (--eval_volume, physics_eval.hand_faces)
     * ``2021_CVPR_CPF/anchor/{face_vertex_idx.txt, anchor_weight.txt}`` + ``ours/vert2joint.pkl`` (physics_fn.py:224-257,
       hand_fn.py:427-450)
     * ``ours/object_mesh_info.pkl`` (dataset/base.py:204-258: the cache the reference writes itself)
@@ -241,7 +259,14 @@ def load_assets(asset_root='asset', seed=0):
                              f'install it or re-save the five arrays as plain numpy') from e
         jr = m['J_regressor']
         jr = jr.toarray() if hasattr(jr, 'toarray') else jr
-        return dict(v_template=_shape('mano', 'v_template', np.asarray(m['v_template'], np.float32), (778, 3)),
+        if 'f' not in m:
+            raise AssetError("mano: MANO_RIGHT.pkl lacks the key 'f' (the faces of the hand mesh)")
+        faces = np.asarray(m['f']).astype(np.int64)
+        if faces.ndim != 2 or faces.shape[1] != 3 or faces.shape[0] == 0:
+            raise AssetError(f"mano: f has shape {tuple(faces.shape)}, expected (F, 3)")
+        if faces.min() < 0 or faces.max() >= 778:
+            raise AssetError('mano: f indexes outside the 778 MANO vertices')
+        return dict(faces=faces, v_template=_shape('mano', 'v_template', np.asarray(m['v_template'], np.float32), (778, 3)),
                     shapedirs=_shape('mano', 'shapedirs', np.asarray(m['shapedirs'], np.float32), (778, 3, 10)),
                     posedirs=_shape('mano', 'posedirs', np.asarray(m['posedirs'], np.float32), (778, 3, 135)),
                     J_regressor=_shape('mano', 'J_regressor', np.asarray(jr, np.float32), (16, 778)),
@@ -256,7 +281,8 @@ def load_assets(asset_root='asset', seed=0):
         if got is None:
             src[table] = 'synthetic'
             _report(f'{table}: no file under {os.path.abspath(asset_root)!r} ({", ".join(os.path.relpath(p, asset_root) for p in paths)}) -> '
-                    f'seeded SYNTHETIC table (seed {seed}); results are not those of the real assets')
+                    f'seeded SYNTHETIC table (seed {seed}); results are not those of the real assets'
+                    + ('; its faces are the convex hull of v_template (a mitten, not a hand)' if table == 'mano' else ''))
         else:
             a[table] = got
             src[table] = paths[0] if len(paths) == 1 else os.path.dirname(paths[0])

@@ -69,7 +69,6 @@ __global__ __launch_bounds__(PM_THREADS) void penetration_multi_kernel(const Pen
     const double* tr = a.t.translate + 3 * o;
     const int kb = a.acc.clu_offset[o], ke = a.acc.clu_offset[o + 1];
     const int* coff = a.acc.col_offset + (long long)o * (COLS * COLS);
-    const double res = (double)VPHO_PEN_RESOLUTION;
     double pd = 0.0, mn = INFINITY;
     int cnt = 0;
     bool nan = false;
@@ -80,14 +79,8 @@ __global__ __launch_bounds__(PM_THREADS) void penetration_multi_kernel(const Pen
         // p = R^T (v - t) in the model frame; q = scale * p + translate in the hash frame (the expressions of penetration.hip)
         double px = 0.0, py = 0.0, pz = 0.0, qx = 0.0, qy = 0.0, qz = 0.0;
         if (live) {
-            const float* v = a.verts + (hyp * a.V + vi) * 3;
-            const double d0 = (double)v[0] - R[3], d1 = (double)v[1] - R[7], d2 = (double)v[2] - R[11];
-            px = R[0] * d0 + R[4] * d1 + R[8] * d2;
-            py = R[1] * d0 + R[5] * d1 + R[9] * d2;
-            pz = R[2] * d0 + R[6] * d1 + R[10] * d2;
-            qx = sc[0] * px + tr[0];
-            qy = sc[1] * py + tr[1];
-            qz = sc[2] * pz + tr[2];
+            pen_model_frame(R, a.verts + (hyp * a.V + vi) * 3, px, py, pz);
+            pen_hash_frame(sc, tr, px, py, pz, qx, qy, qz);
         }
         // ---- nearest triangle: the cluster with the nearest centre first, then every cluster the bound cannot reject
         int seed = kb;
@@ -119,32 +112,15 @@ __global__ __launch_bounds__(PM_THREADS) void penetration_multi_kernel(const Pen
             }
         }
         // ---- z-ray parity over the triangles of the vertex' own column
-        const bool in_box = 0.0 <= qx && qx <= res && 0.0 <= qy && qy <= res && 0.0 <= qz && qz <= res;
-        // the point's own hash cell (q >= 0 here: truncation == floor); a point on the far faces (q == 512) has no cell and no triangle
-        const double cx = in_box ? (double)(int)qx : -1.0, cy = in_box ? (double)(int)qy : -1.0;
-        const bool has_cell = live && in_box && cx < res && cy < res;
+        double cx, cy;
+        const bool has_cell = pen_cell(qx, qy, qz, cx, cy) && live;
         unsigned par0 = 0, par1 = 0;
         if (has_cell) {
             const int col = ((int)cy / CELLS) * COLS + (int)cx / CELLS;
             const int le = coff[col + 1];
             for (int i = coff[col]; i < le; ++i) {
                 const double* r = a.t.tri + (long long)a.acc.col_tri[i] * TS;
-                if (r[R_CX0] <= cx && cx <= r[R_CX1] && r[R_CY0] <= cy && cy <= r[R_CY1]) {
-                    // strict 2-D containment (check_triangles): y = q - t3, (u, v) by the adjugate, scaled by sign(det A)
-                    const double y0 = qx - r[R_CX], y1 = qy - r[R_CY];
-                    const double sdet = r[R_SDET], adet = r[R_ADET];
-                    const double u = (r[R_A11] * y0 - r[R_A01] * y1) * sdet;
-                    const double w = (-r[R_A10] * y0 + r[R_A00] * y1) * sdet;
-                    const double suv = u + w;
-                    if (0.0 < u && u < adet && 0.0 < w && w < adet && 0.0 < suv && suv < adet) {
-                        // plane depth against q_z |n_z| (compute_intersection_depth); D0 = t1_z |n_z|, NaN where n_z == 0
-                        const double alpha = r[R_N0] * (r[R_T1X] - qx) + r[R_N1] * (r[R_T1Y] - qy);
-                        const double depth = r[R_D0] + alpha * r[R_SNZ];
-                        const double zz = qz * r[R_ANZ];
-                        par0 ^= (depth >= zz) ? 1u : 0u;
-                        par1 ^= (depth < zz) ? 1u : 0u;
-                    }
-                }
+                pen_parity_step(r, qx, qy, qz, cx, cy, par0, par1);
             }
         }
         if (live) {

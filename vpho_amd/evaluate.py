@@ -33,10 +33,15 @@ PHYS = 8
 # ops_names.PHYSICS_MULTI_COLUMNS: PD (m), n_inside, min sd (m), contact of (hand hypothesis s, object hypothesis s) reduced per image to
 # hypothesis 0, best-of-S and mean-of-S.  The 96 columns before them are the same with and without the block.
 PHYS_MULTI = 12
+# with eval_volume (cfg.eval_volume; independent of the flags above) every row carries VOL more columns, last of all, in the order of
+# ops_names.VOLUME_COLUMNS: IV (m^3) and the solid-cell count of (aggregated hand, aggregated object), then of the ground-truth pair.
+# Every column before them is the same with and without the flag.
+VOL = 4
 
 
-def row_width(eval_best=False, eval_physics=False, physics_multi=False):
-    return (ROW_BEST if eval_best else ROW) + (PHYS if eval_physics else 0) + (PHYS_MULTI if eval_best and eval_physics and physics_multi else 0)
+def row_width(eval_best=False, eval_physics=False, physics_multi=False, eval_volume=False):
+    return (ROW_BEST if eval_best else ROW) + (PHYS if eval_physics else 0) + (PHYS_MULTI if eval_best and eval_physics and physics_multi else 0) + \
+        (VOL if eval_volume else 0)
 
 
 def mje_mm(pd, gt):
@@ -111,9 +116,10 @@ def multi_hypothesis_block(out, data, gt_joint, gt_vert, assets=None):
 _PHYSICS = {}
 
 
-def physics_meter(assets, device, multi=False):
+def physics_meter(assets, device, multi=False, volume=False):
     """the HandObjectPenetration of an asset set on a device, built once (object meshes: physics_eval.object_meshes); its acceleration
-    tables for the multi-hypothesis kernel only with ``multi`` (eval_best and eval_physics together), once as well"""
+    tables for the multi-hypothesis kernel only with ``multi`` (eval_best and eval_physics together), once as well; with ``volume``
+    (eval_volume) the closed hand mesh (physics_eval.hand_faces) and the objects' solids at cfg.physics_voxel_pitch, once per pitch"""
     key = (id(assets), str(device))
     if key not in _PHYSICS:
         from . import ops
@@ -122,6 +128,12 @@ def physics_meter(assets, device, multi=False):
         _PHYSICS[key] = ops.HandObjectPenetration(object_meshes(assets, cfg.asset_root), device, accel=False)
     if multi:
         _PHYSICS[key].build_accel()
+    if volume:
+        from .configs.args import cfg
+        if _PHYSICS[key].hand_faces is None:
+            from .physics_eval import hand_faces
+            _PHYSICS[key].set_hand_faces(hand_faces(assets))
+        _PHYSICS[key].build_solids(float(cfg.physics_voxel_pitch))
     return _PHYSICS[key]
 
 
@@ -141,6 +153,25 @@ def physics_block(pp, out, data, gt_vert, meshes):
     blk[:, 0:4] = meshes(pp['agg_hand_vert'].float().contiguous(), pd_rt, ids, th).float()
     if 'gt_obj_rt' in data:
         blk[:, 4:8] = meshes(gt_vert.float().contiguous(), data['gt_obj_rt'].double().contiguous(), ids, th).float()
+    return blk
+
+
+def volume_block(pp, out, data, gt_vert, meshes):
+    """(bs, VOL) fp32: the hand-object intersection volume of the pairs of physics_block -- the aggregated hand
+    vertices (pp['agg_hand_vert'], camera frame) with the aggregated object pose, then the ground-truth vertices with data['gt_obj_rt']
+    (NaN without it) -- as IV (m^3) | solid-cell count each.  ``meshes``: physics_meter(..., volume=True)."""
+    from . import ops
+    from .configs.args import cfg
+    if not gt_vert.is_cuda:
+        raise RuntimeError('volume_block: the intersection volume runs on the GPU only (no CPU path)')
+    bs = gt_vert.shape[0]
+    blk = torch.full((bs, VOL), float('nan'), device=gt_vert.device, dtype=torch.float32)
+    ids = meshes.obj_ids(data['obj_name'])
+    h = float(cfg.physics_voxel_pitch)
+    pd_rt = ops.obj_9d_to_rt(out['agg_obj_6d'].double().contiguous(), data['root_joint'].float().contiguous())
+    blk[:, 0:2] = meshes.volume(pp['agg_hand_vert'].float().contiguous(), pd_rt, ids, h).flip(1).float()
+    if 'gt_obj_rt' in data:
+        blk[:, 2:4] = meshes.volume(gt_vert.float().contiguous(), data['gt_obj_rt'].double().contiguous(), ids, h).flip(1).float()
     return blk
 
 
@@ -170,13 +201,14 @@ def physics_multi_block(out, data, meshes):
     return table.float()
 
 
-def metric_rows(out, data, gt_joint, gt_vert, first_index, assets=None, eval_best=False, eval_physics=False, physics_multi=False):
+def metric_rows(out, data, gt_joint, gt_vert, first_index, assets=None, eval_best=False, eval_physics=False, physics_multi=False, eval_volume=False):
     """(bs, ROW) fp32 on the model's device; (bs, ROW_BEST) with eval_best (multi_hypothesis_block appended); PHYS more columns with
-    eval_physics (physics_block), and with both and ``physics_multi`` PHYS_MULTI more (physics_multi_block, last; without it that block
-    and its launch are left out: the rows of the two flags as they always were)."""
+    eval_physics (physics_block), and with both and ``physics_multi`` PHYS_MULTI more (physics_multi_block; without it that block
+    and its launch are left out: the rows of the two flags as they always were); VOL more with ``eval_volume`` (volume_block), last of
+    all, whatever the other flags are."""
     pp = postprocess(out, data['root_joint'], data['is_right'])
     bs = gt_joint.shape[0]
-    rows = torch.empty((bs, row_width(eval_best, eval_physics, physics_multi)), device=gt_joint.device, dtype=torch.float32)
+    rows = torch.empty((bs, row_width(eval_best, eval_physics, physics_multi, eval_volume)), device=gt_joint.device, dtype=torch.float32)
     if torch.is_tensor(first_index):                 # per-image ids (a loader batch that is not a run of the data set)
         rows[:, 0] = first_index.to(device=rows.device, dtype=torch.float32).reshape(bs)
     else:
@@ -205,7 +237,12 @@ def metric_rows(out, data, gt_joint, gt_vert, first_index, assets=None, eval_bes
         p0 = ROW_BEST if eval_best else ROW
         rows[:, p0:p0 + PHYS] = physics_block(pp, out, data, gt_vert, physics_meter(assets, gt_joint.device))
         if eval_best and physics_multi:
-            rows[:, p0 + PHYS:] = physics_multi_block(out, data, physics_meter(assets, gt_joint.device, multi=True))
+            rows[:, p0 + PHYS:p0 + PHYS + PHYS_MULTI] = physics_multi_block(out, data, physics_meter(assets, gt_joint.device, multi=True))
+    if eval_volume:
+        if assets is None:
+            raise ValueError('metric_rows: eval_volume needs the asset tables (object meshes, hand faces)')
+        v0 = rows.shape[1] - VOL
+        rows[:, v0:] = volume_block(pp, out, data, gt_vert, physics_meter(assets, gt_joint.device, volume=True))
     from .configs.args import cfg
     if cfg.aggregation_mode_hand == '2D_pt_joint':
         # that mode fuses joints only; its vertices are the reference's all-zero mesh (aggregation.py:364-366): no vertex metric of it
@@ -213,6 +250,8 @@ def metric_rows(out, data, gt_joint, gt_vert, first_index, assets=None, eval_bes
         rows[:, 10] = float('nan')
         if eval_physics:
             rows[:, p0:p0 + 4] = float('nan')
+        if eval_volume:
+            rows[:, v0:v0 + 2] = float('nan')
     return rows
 
 
@@ -335,6 +374,10 @@ def summarize(rows):
     from .ops_names import OBJ_METRIC_NAMES
     obj = rows[:, OBJ_COL:OBJ_COL + 16].double().mean(0)
     res['object'] = _object_table(obj)
+    # the widths without the volume block are 28, 88, 36, 96 and 108; with it each is 4 wider: no two layouts share a width
+    if rows.shape[1] in tuple(w + VOL for w in (ROW, ROW_BEST, ROW + PHYS, ROW_BEST + PHYS, ROW_BEST + PHYS + PHYS_MULTI)):
+        res['volume'] = _volume_table(rows[:, -VOL:])
+        rows = rows[:, :-VOL]
     p0 = {ROW + PHYS: ROW, ROW_BEST + PHYS: ROW_BEST, ROW_BEST + PHYS + PHYS_MULTI: ROW_BEST}.get(rows.shape[1])
     if p0 is not None:
         from .ops_names import MULTI_TABLES, PHYSICS_SOURCES
@@ -358,6 +401,19 @@ def _object_table(obj):
     from .ops_names import OBJ_METRIC_NAMES
     return {k: float(obj[i] * (1000.0 if k in ('MCE', 'OCE', 'MCE2', 'ADD', 'ADDS', 'CD') else (1.0 if k == 'REP' else 100.0)))
             for i, k in enumerate(OBJ_METRIC_NAMES)}
+
+
+def _volume_table(blk):
+    """volume table over all images, per source (pred / gt): mean and largest intersection volume (cm^3) and the share of images with
+    at least one solid cell of the object inside the hand (%); NaN for a source without values"""
+    from .ops_names import PHYSICS_SOURCES
+    blk = blk.double()
+    res = {}
+    for s, name in enumerate(PHYSICS_SOURCES):
+        iv, cells = blk[:, 2 * s], blk[:, 2 * s + 1]
+        res[name] = dict(IV_cm3=float(iv.mean() * 1e6), IV_max_cm3=float(iv.max() * 1e6) if iv.shape[0] else float('nan'),
+                         intersecting_pct=float((cells > 0).double().mean() * 100.0) if not cells.isnan().any() else float('nan'))
+    return res
 
 
 def _physics_table(blk, names):

@@ -27,6 +27,7 @@ lib.vpho_bn_workspace_bytes.restype = C.c_longlong
 lib.vpho_conv2d_wgrad_workspace_bytes.restype = C.c_longlong
 lib.vpho_mha_bwd_workspace_bytes.restype = C.c_longlong
 lib.vpho_infer_record_bytes.restype = C.c_longlong
+lib.vpho_hand_obj_intersection_workspace_bytes.restype = C.c_longlong
 
 
 class VphoError(RuntimeError):
@@ -1210,14 +1211,20 @@ class ObjMeshAccel(C.Structure):
     _fields_ = [('col_offset', C.c_void_p), ('col_tri', C.c_void_p), ('clu_offset', C.c_void_p), ('clu_sphere', C.c_void_p), ('clu_geo', C.c_void_p)]
 
 
+class ObjSolids(C.Structure):
+    _fields_ = [('pts', C.c_void_p), ('pt_offset', C.c_void_p), ('n_obj', I), ('max_pts', I)]
+
+
 class HandObjectPenetration:
     """Hand-object penetration and contact (--eval_physics) on the device: per-triangle tables of every object mesh,
     built once (physics_eval.mesh_tables), + thin wrapper of vpho_hand_obj_penetration_f64.  ``meshes``: {name: {'verts', 'faces'}}
     (physics_eval.object_meshes).  ``multi`` scores every sampled hypothesis (vpho_hand_obj_penetration_multi_f64) through the
     acceleration tables of physics_eval.mesh_accel, built here once as well (``accel=False`` leaves them out: ``multi`` then raises until
-    ``build_accel()`` is called)."""
+    ``build_accel()`` is called).  ``volume`` is the hand-object intersection volume (--eval_volume, vpho_hand_obj_intersection_f64) of a
+    hand mesh (``hand_faces``: one closed (F, 3) face list, physics_eval.hand_faces) with the objects' solid point sets, which
+    ``build_solids(pitch)`` makes once per pitch."""
 
-    def __init__(self, meshes, device, accel=True):
+    def __init__(self, meshes, device, accel=True, hand_faces=None):
         import numpy as np
         from .physics_eval import mesh_tables
         self.names = list(meshes.keys())
@@ -1232,6 +1239,9 @@ class HandObjectPenetration:
         self.n_tri = counts
         self.device = device
         self._tabs, self.acc = tabs, None
+        self._meshes, self._solids, self.hand_faces = meshes, {}, None
+        if hand_faces is not None:
+            self.set_hand_faces(hand_faces)
         if accel:
             self.build_accel()
         self.c = ObjMeshTables(self.tri.data_ptr(), self.tri_offset.data_ptr(), self.scale.data_ptr(), self.translate.data_ptr(),
@@ -1256,6 +1266,82 @@ class HandObjectPenetration:
         self.clu_geo = f64(np.concatenate([a['geo'] for a in acc]))
         self.acc = ObjMeshAccel(self.col_offset.data_ptr(), self.col_tri.data_ptr(), self.clu_offset.data_ptr(), self.clu_sphere.data_ptr(),
                                 self.clu_geo.data_ptr())
+
+    def set_hand_faces(self, faces):
+        """the closed face list of the hand mesh for ``volume``: (F, 3) integers, kept on the device as int32"""
+        import numpy as np
+        f = np.ascontiguousarray(np.asarray(faces).reshape(-1, 3), dtype=np.int64)
+        if f.shape[0] == 0 or f.min() < 0 or f.max() > 0x7fffffff:
+            raise VphoError(f'HandObjectPenetration: a hand mesh of {f.shape[0]} faces (indices {f.min() if f.size else None} .. {f.max() if f.size else None})')
+        self.hand_faces = torch.as_tensor(f.astype(np.int32)).to(self.device)
+        self.hand_faces_max = int(f.max())
+
+    def build_solids(self, pitch):
+        """The objects' solid point sets at one voxel pitch (m), once per pitch: per object the cell centres of
+        physics_eval.solid_lattice that the single-pose kernel finds inside the object at identity pose (p = v exactly), concatenated,
+        plus offsets.  -> dict(pts (P, 3) fp32 and pt_offset (n_obj + 1,) int32 on the device, counts, dims, max_pts, c = ObjSolids)."""
+        import numpy as np
+        from .physics_eval import solid_lattice
+        key = float(pitch)
+        if not key > 0.0:
+            raise VphoError(f'HandObjectPenetration.build_solids: the voxel pitch must be positive ({pitch})')
+        if key in self._solids:
+            return self._solids[key]
+        eye = torch.zeros((1, 3, 4), dtype=torch.float64, device=self.device)
+        eye[0, :, :3] = torch.eye(3, dtype=torch.float64)
+        pts, counts, dims = [], [], []
+        for o, n in enumerate(self.names):
+            c, d = solid_lattice(self._meshes[n]['verts'], self._meshes[n]['faces'], key)
+            c = torch.from_numpy(c).to(self.device)
+            _, _, inside = self(c[None], eye, [o], per_vertex=True)
+            keep = c[inside[0].bool()]
+            pts.append(keep)
+            counts.append(int(keep.shape[0]))
+            dims.append(tuple(int(x) for x in d))
+        allp = torch.cat(pts, 0).contiguous() if sum(counts) else torch.zeros((1, 3), dtype=torch.float32, device=self.device)
+        off = torch.as_tensor(np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)).to(self.device)
+        sol = dict(pts=allp, pt_offset=off, counts=counts, dims=dims, max_pts=max(counts), pitch=key)
+        sol['c'] = ObjSolids(allp.data_ptr(), off.data_ptr(), len(self.names), sol['max_pts'])
+        torch.cuda.current_stream(allp.device).synchronize()          # built on this stream, read by kernels of any stream afterwards
+        self._solids[key] = sol
+        return sol
+
+    def volume(self, verts, obj_rt, obj_id, pitch=None, flags=False):
+        """Hand-object intersection volume per (hand, object pose) pair: verts (n,V,3) fp32 hand vertices and obj_rt (n,3,4) fp64 object
+        poses in the camera frame, obj_id as in __call__; ``pitch`` (m; default cfg.physics_voxel_pitch).  -> (n,2) fp64 = n_cells (solid
+        cell centres of the object inside the posed hand mesh) | IV = n_cells * pitch^3 (m^3); with ``flags`` also (n, max_pts) uint8,
+        one flag per solid centre of the pair's object in the order of build_solids(pitch) (0 behind its last centre)."""
+        if pitch is None:
+            from .configs.args import cfg
+            pitch = cfg.physics_voxel_pitch
+        pitch = float(pitch)
+        if not pitch > 0.0:
+            raise VphoError(f'HandObjectPenetration.volume: the voxel pitch must be positive ({pitch})')
+        if self.hand_faces is None:
+            raise VphoError('HandObjectPenetration.volume: no hand mesh (pass hand_faces= or call set_hand_faces)')
+        n, V = verts.shape[:2]
+        assert verts.shape == (n, V, 3) and obj_rt.shape == (n, 3, 4)
+        if self.hand_faces_max >= V:
+            raise VphoError(f'HandObjectPenetration.volume: the hand faces index vertex {self.hand_faces_max}, the hands have {V}')
+        if not torch.is_tensor(obj_id):
+            ids = [int(i) for i in obj_id]
+            if len(ids) != n or any(i < 0 or i >= len(self.names) for i in ids):
+                raise VphoError(f'HandObjectPenetration: object ids {ids} outside [0, {len(self.names)}) or not one per image')
+            obj_id = _ids_to_device(ids, self.device)
+        assert obj_id.shape == (n,)
+        sol = self.build_solids(pitch)
+        F_ = int(self.hand_faces.shape[0])
+        out = _new((n, 2), obj_rt, torch.float64)
+        fl = _new((n, sol['max_pts']), obj_rt, torch.uint8) if flags else None
+        if n == 0:
+            return (out, fl) if flags else out
+        need = lib.vpho_hand_obj_intersection_workspace_bytes(I(n), I(F_))
+        if need < 0:
+            raise VphoError('vpho_hand_obj_intersection_workspace_bytes: bad argument')
+        ws = torch.empty(need, dtype=torch.uint8, device=self.device)          # per call: one object serves streams that run concurrently
+        _call('vpho_hand_obj_intersection_f64', C.byref(self.c), C.byref(sol['c']), _i32(self.hand_faces), I(F_), _f32(verts), I(n), I(V),
+              _f64(obj_rt), _i32(obj_id), C.c_double(pitch), _f64(out), _u8(fl), _ptr(ws), LL(ws.numel()))
+        return (out, fl) if flags else out
 
     def obj_ids(self, names):
         """class indices of a batch as a device tensor (pinned host memory, asynchronous copy on the caller's stream, as

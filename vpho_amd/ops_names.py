@@ -23,3 +23,9 @@ PHYSICS_TABLE = ('PD_mm', 'PD_max_mm', 'penetration_rate_pct', 'inside_verts', '
 # penetrating hypothesis, max contact) and mean-of-S (contact becomes the fraction of hypotheses in contact); the 'physics' table gains
 # the three MULTI_TABLES entries beside 'pred' and 'gt', each with the PHYSICS_TABLE keys
 PHYSICS_MULTI_COLUMNS = tuple(f'physics/{t}/{k}' for t in MULTI_TABLES for k in PHYSICS_METRIC_NAMES)
+# the block that evaluate.metric_rows appends last of all with eval_volume: the hand-object intersection volume of the
+# aggregated hand mesh with the aggregated object pose ('pred'), then of the ground-truth pair ('gt', NaN without object ground truth);
+# per image IV (m^3) and the number of solid cells of the object inside the hand (IV = cells * cfg.physics_voxel_pitch^3)
+VOLUME_COLUMNS = ('pred_IV_m3', 'pred_cells', 'gt_IV_m3', 'gt_cells')
+# the summarize / EVAL_JSON table 'volume', per source: mean IV (cm^3), largest IV (cm^3), share of images with a cell inside (%)
+VOLUME_TABLE = ('IV_cm3', 'IV_max_cm3', 'intersecting_pct')

@@ -238,3 +238,67 @@ def object_meshes(assets, asset_root='asset'):
             raise AssetError(f"ycb: {path} entry {n!r}: 'faces' index outside its {v.shape[0]} vertices")
         out[n] = dict(verts=v, faces=f)
     return out
+
+
+# ------------------------------------------------------------------------------------------------ intersection volume (--eval_volume)
+def close_mesh(faces):
+    """Closes an open triangle mesh: the boundary edges (used by exactly one face) are chained into loops and every loop is
+    fan-triangulated from its lowest vertex index, wound so that every edge of the result appears once in each direction.  Deterministic
+    (loops in ascending order of their lowest vertex); a closed mesh comes back unchanged.  An edge used more than once in the same
+    direction, or a boundary vertex where two loops touch, is non-manifold: AssetError.  (F, 3) int64 -> (F', 3) int64."""
+    f = np.asarray(faces, np.int64).reshape(-1, 3)
+    edges = np.concatenate([f[:, [0, 1]], f[:, [1, 2]], f[:, [2, 0]]])
+    seen = {}
+    for a, b in edges.tolist():
+        if a == b or (a, b) in seen:
+            raise AssetError(f'close_mesh: non-manifold edge ({a}, {b}): used more than once in the same direction')
+        seen[(a, b)] = True
+    # a boundary edge (a, b) has no twin (b, a); the closing faces run along it backwards: b -> a
+    nxt = {}
+    for a, b in seen:
+        if (b, a) not in seen:
+            if b in nxt:
+                raise AssetError(f'close_mesh: non-manifold boundary at vertex {b}: two boundary loops touch')
+            nxt[b] = a
+    if not nxt:
+        return f.copy()
+    if sorted(nxt) != sorted(nxt.values()):
+        raise AssetError('close_mesh: the boundary edges do not chain into loops')
+    extra, left = [], set(nxt)
+    while left:
+        start = min(left)
+        loop, v = [], start
+        while v in left:
+            left.discard(v)
+            loop.append(v)
+            v = nxt[v]
+        if v != start or len(loop) < 3:
+            raise AssetError(f'close_mesh: the boundary through vertex {start} does not close into a loop of three or more edges')
+        extra += [(loop[0], loop[i], loop[i + 1]) for i in range(1, len(loop) - 1)]
+    return np.concatenate([f, np.array(extra, np.int64).reshape(-1, 3)])
+
+
+def hand_faces(assets):
+    """the closed face list of the hand mesh, (F, 3) int64: ``assets['mano']['faces']`` (MANO_RIGHT.pkl's ``f``: 1 538 faces, the wrist
+    hole is one boundary loop -> 1 552; the synthetic table: the convex hull of v_template, closed already) through close_mesh"""
+    mano = assets['mano']
+    if 'faces' not in mano:
+        raise AssetError("mano: the table carries no 'faces' (--eval_volume needs the hand mesh's triangles)")
+    return close_mesh(mano['faces'])
+
+
+def solid_lattice(verts, faces, pitch):
+    """The cell centres of the lattice of pitch h over a mesh's bbox [lo, hi]: n_a = ceil((hi_a - lo_a) / h) cells per axis, centres
+    c = lo + (i + 1/2, j + 1/2, k + 1/2) h computed in fp64 and rounded ONCE to fp32 (the fp32 values are the points: they go through the
+    fp32-vertex interface of the kernels unchanged), k fastest.  Which centres are inside the mesh -- the solid -- is the caller's business
+    (ops: the single-pose penetration kernel at identity pose).  -> (centres (P, 3) fp32, dims (3,) int64).
+    Not a surface voxelisation: trimesh's default ``voxelized()`` marks the cells the surface passes through."""
+    h = float(pitch)
+    if not h > 0.0:
+        raise AssetError(f'solid_lattice: the pitch must be positive ({pitch})')
+    tri = np.asarray(verts, np.float64)[np.asarray(faces, np.int64)].reshape(-1, 3)
+    lo, hi = tri.min(0), tri.max(0)
+    dims = np.maximum(np.ceil((hi - lo) / h), 1).astype(np.int64)
+    ax = [lo[a] + (np.arange(dims[a], dtype=np.float64) + 0.5) * h for a in range(3)]
+    c = np.stack(np.meshgrid(*ax, indexing='ij'), -1).reshape(-1, 3)
+    return np.ascontiguousarray(c.astype(np.float32)), dims

@@ -214,7 +214,7 @@ class Trainer:
             seen += n
 
     @torch.no_grad()
-    def eval(self, loader=None, eval_best=None, eval_physics=None, physics_multi=None):
+    def eval(self, loader=None, eval_best=None, eval_physics=None, physics_multi=None, eval_volume=None):
         """``evaluate(testing_dataloader)`` (train_diff_hand_obj.py:202-357).  ``loader``: see ``_eval_batches``; default synthetic.
         ``eval_best`` (default: cfg.eval_best, the reference's is_eval_best): also score every sampled hypothesis and report the
         one_candidate, best_of_S and mean_of_S tables (rows of evaluate.ROW_BEST columns).  ``eval_physics`` (default:
@@ -222,14 +222,21 @@ class Trainer:
         ``physics_multi`` (default: cfg.eval_best and cfg.eval_physics, i.e. both command-line flags; it needs both of the above):
         every sampled hypothesis' penetration as well (evaluate.PHYS_MULTI more columns, last; the ``physics`` table gains
         one_candidate, best_of_S and mean_of_S).  A caller that passes eval_best / eval_physics itself gets the rows it always got
-        unless it asks for the new block too."""
+        unless it asks for the new block too.  ``eval_volume`` (default: cfg.eval_volume; independent of the others): also report the
+        hand-object intersection volume at cfg.physics_voxel_pitch, the ``volume`` table (evaluate.VOL more columns, last of all)."""
         from .configs.args import cfg
+        eval_volume = bool(cfg.eval_volume if eval_volume is None else eval_volume)
+        # the keyword travels to metric_rows only when it is set: without it the call is the one it always was
+        vol = dict(eval_volume=True) if eval_volume else {}
         eval_best = bool(cfg.eval_best if eval_best is None else eval_best)
         eval_physics = bool(cfg.eval_physics if eval_physics is None else eval_physics)
         physics_multi = bool((cfg.eval_best and cfg.eval_physics) if physics_multi is None else physics_multi) and eval_best and eval_physics
         if eval_physics:
             # object meshes and their tables (with eval_best also the multi-hypothesis kernel's), once, before the timed loop
             E.physics_meter(self.assets, self.device, multi=physics_multi)
+        if eval_volume:
+            # the closed hand mesh and the objects' solids at the configured pitch, once, before the timed loop
+            E.physics_meter(self.assets, self.device, volume=True)
         rows = []
         t0 = time.perf_counter()
         # three batches in flight (independent images; see evaluate.PipelinedPredictor)
@@ -244,10 +251,10 @@ class Trainer:
                     # synthetic run: batch 0 provides the ground truth (its own regression output), so it is evaluated first
                     out0 = pipe.submit(b).result()
                     gt = (out0['reg_hand_joint'] + b['root_joint'][:, None], out0['reg_hand_vert'] + b['root_joint'][:, None])
-                    rows.append(E.metric_rows(out0, b, gt[0], gt[1], first, self.assets, eval_best, eval_physics, physics_multi))
+                    rows.append(E.metric_rows(out0, b, gt[0], gt[1], first, self.assets, eval_best, eval_physics, physics_multi, **vol))
                 else:
                     futs.append(pipe.submit(b, lambda out, batch, eng, first=first, gt=gt: E.metric_rows(out, batch, gt[0], gt[1], first, self.assets,
-                                                                                                    eval_best, eval_physics, physics_multi)))
+                                                                                                    eval_best, eval_physics, physics_multi, **vol)))
                 item = gen.send(gt)
         except StopIteration:
             pass
@@ -255,7 +262,7 @@ class Trainer:
         pipe.close()
         # a rank whose shard is empty still takes part in the collective (with zero rows: the ragged gather carries the counts first);
         # raising here would leave the other ranks blocked in their all-gather.  Only an evaluation without ANY image is an error
-        mine = torch.cat(rows, 0) if rows else torch.zeros((0, E.row_width(eval_best, eval_physics, physics_multi)), device=self.device, dtype=torch.float32)
+        mine = torch.cat(rows, 0) if rows else torch.zeros((0, E.row_width(eval_best, eval_physics, physics_multi, eval_volume)), device=self.device, dtype=torch.float32)
         rows = E.gather_rows(mine)
         if rows.shape[0] == 0:
             raise ValueError('Trainer.eval: the loader yielded no batch on any rank')
@@ -267,7 +274,7 @@ class Trainer:
             print(f'aggregation_mode_hand {cfg.aggregation_mode_hand}  aggregation_mode_obj {cfg.aggregation_mode_obj}')
             table = E.summarize(rows.cpu())
             for name, r in table.items():
-                if name not in ('object', 'physics') + E.MULTI_TABLES:
+                if name not in ('object', 'physics', 'volume') + E.MULTI_TABLES:
                     print(f'{name:>5s}: n={r["n"]:5d}  MJE reg {r["MJE_reg"]:.2f}  first {r["MJE_first"]:.2f}  agg {r["MJE_agg"]:.2f}  MVE agg {r["MVE_agg"]:.2f}  (mm)')
             print('object (aggregated pose): ' + '  '.join(f'{k} {v:.2f}' for k, v in table['object'].items()))
             for name in E.MULTI_TABLES:
@@ -277,6 +284,9 @@ class Trainer:
             if 'physics' in table:
                 for src, r in table['physics'].items():
                     print(f'physics {src}: ' + '  '.join(f'{k} {v:.2f}' for k, v in r.items()))
+            if 'volume' in table:
+                for src, r in table['volume'].items():
+                    print(f'volume {src} (pitch {cfg.physics_voxel_pitch * 1000.0:g} mm): ' + '  '.join(f'{k} {v:.3f}' for k, v in r.items()))
             import json
             print('EVAL_JSON ' + json.dumps({'images': int(rows.shape[0]), 'world': self.world, 'aggregation_mode_hand': cfg.aggregation_mode_hand,
                                              'aggregation_mode_obj': cfg.aggregation_mode_obj, 'table': table}))
