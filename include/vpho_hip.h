@@ -377,7 +377,8 @@ VPHO_API int vpho_hand_fuse_level_f32(const float* hv, int n_obs, float* pose, i
 /* generic wavefront top-k: element c of row (o,f) at scores[(o*n + c)*F + f]; val/idx [o][f][k] */
 VPHO_API int vpho_topk_f32(const float* scores, int rows_outer, int n, int F, int k, float* val, int* idx, void* stream);
 VPHO_API int vpho_topk_weights_f32(const float* val, int rows, int k, float* w, void* stream);
-/* select_topk_object_by_heatmap score (aggregation.py:742-776); pose (bs,n,9) fp64 */
+/* select_topk_object_by_heatmap score (aggregation.py:742-776); pose (bs,n,9) fp64.  vpho_obj_heat_score, vpho_obj_physics_score and
+ * vpho_obj_verts_f32: an obj_id outside [0, n_obj) gives NaN for that image's outputs (no table row is read), as vpho_obj_pt2d_score */
 VPHO_API int vpho_obj_heat_score(const double* pose, int n, const double* transl_override, const float* root, const vpho_obj_tables* t,
                         const int* obj_id, const unsigned char* is_right, const float* Kmat, const float* bbox,
                         const float* heatmap, int bs, int H, int W, float* score, void* stream);

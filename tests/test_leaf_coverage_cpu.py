@@ -10,22 +10,8 @@ import re
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # entry points with no wrapper named in a GPU test file, each with the reason it is acceptable.  The test fails on an entry that is no
-# longer needed, and none of the kernels of the leaf-test issue may ever be listed here (LEAF_KERNELS below).
-CASCADE = ('an aggregation-cascade stage reached only through the engine: pinned stage by stage in test_gpu_predict / test_gpu_aggmodes / test_gpu_referee, no direct leaf test yet')
+# longer needed, and none of the kernels of the leaf-test issues may ever be listed here (LEAF_KERNELS, CASCADE_KERNELS below).
 EXCEPTIONS = {
-    'vpho_force_anchor_f32': CASCADE,
-    'vpho_hand_candidates_f32': CASCADE,
-    'vpho_hand_heat_f32': CASCADE,
-    'vpho_hand_joint_gather_mean_f32': CASCADE,
-    'vpho_hand_phys_candidates_f32': CASCADE,
-    'vpho_hand_pose_fuse_f32': CASCADE,
-    'vpho_hand_pt2d_score_f32': CASCADE,
-    'vpho_obj_cross_candidates': CASCADE,
-    'vpho_obj_heat_score': CASCADE,
-    'vpho_obj_physics_score': CASCADE,
-    'vpho_obj_pt2d_score': CASCADE,
-    'vpho_obj_verts_f32': CASCADE,
-    'vpho_topk_weights_f32': CASCADE,
     'vpho_conv3x3_winograd_gate_nhwc_f32': 'gated Winograd input gradient of the training blocks: compared through the bottleneck / FPN / encoder training goldens only',
     'vpho_maxpool_bwd_nhwc_f32': 'one-pass form without an ops wrapper: test_gpu_conv_backward.py calls it through ops._call against the workspace form',
     'vpho_mha_f32': 'alias of vpho_mha_dropout_f32 without a mask (no wrapper): that entry point is tested directly in test_gpu_train_physics.py',
@@ -44,6 +30,19 @@ LEAF_WRAPPERS = {
     'nchw_to_nhwc', 'nhwc_to_nchw', 'maxpool_nhwc', 'align_heatmap_nhwc', 'nerf_embed', 'cross_tokens', 'add_layernorm', 'force_local',
     'append_betas', 'dsm_prepare', 'plinear2_fwd', 'plinear2_bwd', 'dsm_loss', 'mse_loss', 'relu_bwd', 'sum_repeats', 'transpose', 'im2col_t',
     'add_lrelu', 'adamw_', 'AdamWList', 'AdamWList.step', 'cross_tokens_bwd', 'layernorm_bwd', 'physics_loss', 'resize_bilinear_nhwc', 'lrelu_bwd'}
+
+# the aggregation-cascade kernels that tests/test_gpu_cascade_leaves.py covers one by one
+CASCADE_KERNELS = {
+    'vpho_hand_candidates_f32', 'vpho_hand_heat_f32', 'vpho_topk_weights_f32', 'vpho_obj_heat_score', 'vpho_obj_cross_candidates',
+    'vpho_obj_physics_score', 'vpho_obj_verts_f32', 'vpho_force_anchor_f32', 'vpho_hand_phys_candidates_f32', 'vpho_hand_pt2d_score_f32',
+    'vpho_obj_pt2d_score', 'vpho_hand_pose_fuse_f32', 'vpho_hand_joint_gather_mean_f32', 'vpho_obj_fuse_f64', 'vpho_hand_phys_score_f32',
+    'vpho_hand_phys_fuse_f32'}
+CASCADE_WRAPPERS = {'Aggregation.' + m for m in (
+    'hand_candidates', 'hand_heat', 'topk_weights', 'obj_heat_score', 'obj_cross', 'obj_physics_score', 'obj_verts', 'force_anchor',
+    'hand_phys_candidates', 'hand_pt2d_score', 'obj_pt2d_score', 'hand_pose_fuse', 'hand_joint_gather_mean', 'obj_fuse', 'hand_phys_score',
+    'hand_phys_fuse')}
+# of these, the three that other GPU test files also call by name (weakly: equality with the engine, an error message, finiteness)
+CASCADE_CALLED_ELSEWHERE = {'vpho_obj_fuse_f64', 'vpho_hand_phys_score_f32', 'vpho_hand_phys_fuse_f32'}
 
 
 def _declared():
@@ -266,6 +265,27 @@ def test_without_the_leaf_files_the_gap_of_the_issue_is_back():
     are called elsewhere as helpers of other comparisons."""
     back = set(uncovered(skip=('test_gpu_leaf_forward.py', 'test_gpu_leaf_train.py'))) - set(EXCEPTIONS)
     assert back == LEAF_KERNELS - {'vpho_resize_bilinear_nhwc_f32', 'vpho_resize_bilinear_rows_nhwc_f32', 'vpho_lrelu_bwd_f32'}, sorted(back ^ LEAF_KERNELS)
+
+
+def test_the_cascade_kernels_are_never_an_exception_and_each_wrapper_is_called_directly():
+    assert not (set(EXCEPTIONS) & CASCADE_KERNELS) and len(CASCADE_KERNELS) == len(CASCADE_WRAPPERS) == 16
+    declared = set(_declared())
+    assert CASCADE_KERNELS <= declared, sorted(CASCADE_KERNELS - declared)
+    W = wrappers()
+    assert CASCADE_WRAPPERS <= set(W), sorted(CASCADE_WRAPPERS - set(W))
+    assert all(len(W[w]) == 1 for w in CASCADE_WRAPPERS)                                                # one wrapper, one entry point
+    reached = set().union(*(W[w] for w in CASCADE_WRAPPERS))
+    assert reached == CASCADE_KERNELS, sorted(reached ^ CASCADE_KERNELS)
+    src = open(os.path.join(ROOT, 'tests', 'test_gpu_cascade_leaves.py')).read()
+    calls = ops_calls_in(src, ops_classes(), ops_factories(), package_attributes())
+    assert CASCADE_WRAPPERS <= calls, sorted(CASCADE_WRAPPERS - calls)
+
+
+def test_without_the_cascade_file_the_gap_of_the_issue_is_back():
+    """the other GPU test files reach the cascade stages through the engine only: with tests/test_gpu_cascade_leaves.py left out, exactly
+    the thirteen kernels that had no direct call come back as uncovered (the other three are called by name elsewhere)"""
+    back = set(uncovered(skip=('test_gpu_cascade_leaves.py',))) - set(EXCEPTIONS)
+    assert back == CASCADE_KERNELS - CASCADE_CALLED_ELSEWHERE, sorted(back ^ (CASCADE_KERNELS - CASCADE_CALLED_ELSEWHERE))
 
 
 _SAMPLE = '''

@@ -122,17 +122,19 @@ __global__ void hand_heat_kernel(const float* __restrict__ joints, const float* 
 // pose: (bs, n, 9) fp64; optional per-image translation override (bs,3) fp64 (aggregation.py:1219-1220)
 // F64: the poses are fp64 already (quirk Q5: the sampler returns float64 object poses, the reference casts them with .float(), :753):
 // rotation from the 6-D columns, key-point transform, translation + root, flip, projection, look-up and the sum over the key-points all
-// in double, one rounding at the end
+// in double; each key-point's look-up is rounded to float (bicubic_zero_d's return value), their double sum once more at the end
 template <bool F64>
 __global__ void obj_heat_kernel(const double* __restrict__ pose, const double* __restrict__ transl_override, const float* __restrict__ root,
                                 const float* __restrict__ kpt_tab, const int* __restrict__ obj_id, const unsigned char* __restrict__ is_right,
                                 const float* __restrict__ Kmat, const float* __restrict__ bbox, const float* __restrict__ heatmap,
-                                int bs, int n, int J, int H, int W, float* __restrict__ out) {
+                                int bs, int n, int J, int n_obj, int H, int W, float* __restrict__ out) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (long long)bs * n) return;
     const int b = (int)(i / n);
+    const int oid = obj_id[b];
+    if (oid < 0 || oid >= n_obj) { out[i] = NAN; return; }            // an unknown class: no table row to read (as obj_pt2d_kernel)
     const double* pp = pose + i * 9;
-    const float* kp = kpt_tab + (long long)obj_id[b] * J * 3;
+    const float* kp = kpt_tab + (long long)oid * J * 3;
     if (F64) {
         double R[9], t[3];
         vpho::rot6d_to_matrix<double>(pp, R);
@@ -475,14 +477,16 @@ __global__ __launch_bounds__(256) void anchor_kernel(const AnchorArgs a) {
 // ---------------------------------------------------------------------------------------- object point clouds
 // verts_cam[b][v] = flip(R(pose_b) v + t_b + root_b)     (head_object.py:36-67, aggregation.py:1281-1284)
 __global__ void obj_verts_kernel(const double* __restrict__ pose, const float* __restrict__ root, const float* __restrict__ vert_tab,
-                                 const int* __restrict__ obj_id, const unsigned char* __restrict__ is_right, int bs, int nv, float* __restrict__ out) {
+                                 const int* __restrict__ obj_id, const unsigned char* __restrict__ is_right, int bs, int nv, int n_obj, float* __restrict__ out) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (long long)bs * nv) return;
     const int b = (int)(i / nv), v = (int)(i % nv);
+    const int oid = obj_id[b];
+    if (oid < 0 || oid >= n_obj) { out[i * 3 + 0] = NAN; out[i * 3 + 1] = NAN; out[i * 3 + 2] = NAN; return; }   // an unknown class: no table row to read
     float p6[6], R[9];
     for (int k = 0; k < 6; ++k) p6[k] = (float)pose[b * 9 + k];
     vpho::rot6d_to_matrix(p6, R);
-    const float* p = vert_tab + ((long long)obj_id[b] * nv + v) * 3;
+    const float* p = vert_tab + ((long long)oid * nv + v) * 3;
     for (int r = 0; r < 3; ++r) {
         float val = (p[0] * R[r * 3 + 0] + p[1] * R[r * 3 + 1] + p[2] * R[r * 3 + 2]) + ((float)pose[b * 9 + 6 + r] + root[b * 3 + r]);
         if (r == 0 && !is_right[b]) val = val * -1.f;
@@ -498,7 +502,7 @@ __global__ void obj_verts_kernel(const double* __restrict__ pose, const float* _
 // round to the same root are told apart here and not there).
 struct ObjPhysArgs {
     const double* cand; int n;                       // (bs, n, 9)
-    const float* root; const float* vert_tab; const float* com_tab; const int* obj_id; const unsigned char* is_right; int nv;
+    const float* root; const float* vert_tab; const float* com_tab; const int* obj_id; const unsigned char* is_right; int nv, n_obj;
     const float* force_point; const float* force_global;   // (bs,32,3)
     float* score;                                     // (bs, n)
 };
@@ -506,13 +510,18 @@ __global__ __launch_bounds__(256) void obj_physics_kernel(const ObjPhysArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];               // nv x (x, y, z, -) transformed vertices
     __shared__ float s_d[32], s_r[32][3];
     const int b = blockIdx.x / a.n;
+    const int oid = a.obj_id[b];
+    if (oid < 0 || oid >= a.n_obj) {                                          // an unknown class: no table row to read; the whole block leaves
+        if (threadIdx.x == 0) a.score[blockIdx.x] = NAN;
+        return;
+    }
     const double* pp = a.cand + (long long)blockIdx.x * 9;
     float p6[6], R[9], t[3];
     for (int k = 0; k < 6; ++k) p6[k] = (float)pp[k];
     for (int k = 0; k < 3; ++k) t[k] = (float)pp[6 + k] + a.root[b * 3 + k];
     vpho::rot6d_to_matrix(p6, R);
     const float sgn = a.is_right[b] ? 1.f : -1.f;
-    const float* tab = a.vert_tab + (long long)a.obj_id[b] * a.nv * 3;
+    const float* tab = a.vert_tab + (long long)oid * a.nv * 3;
     for (int v = threadIdx.x; v < a.nv; v += blockDim.x) {
         float o[3];
         for (int r = 0; r < 3; ++r) {
@@ -540,7 +549,7 @@ __global__ __launch_bounds__(256) void obj_physics_kernel(const ObjPhysArgs a) {
     best = sqrtf(best);
     if (sub == 0) {
         // CoM of the candidate: R com + t, flipped
-        const float* cm = a.com_tab + (long long)a.obj_id[b] * 3;
+        const float* cm = a.com_tab + (long long)oid * 3;
         float com[3];
         for (int r = 0; r < 3; ++r) com[r] = (cm[0] * R[r * 3 + 0] + cm[1] * R[r * 3 + 1] + cm[2] * R[r * 3 + 2]) + t[r];
         com[0] *= sgn;
@@ -801,8 +810,8 @@ extern "C" int vpho_obj_heat_score(const double* pose, int n, const double* tran
                                    const int* obj_id, const unsigned char* is_right, const float* Kmat, const float* bbox,
                                    const float* heatmap, int bs, int H, int W, float* score, void* stream) {
     VPHO_REQUIRE(pose && root && t && t->kpt && obj_id && is_right && Kmat && bbox && heatmap && score && bs > 0 && n > 0, "vpho_obj_heat_score: bad argument");
-    if (score_fp32()) LAUNCH1D(obj_heat_kernel<false>, (long long)bs * n, stream, pose, transl_override, root, t->kpt, obj_id, is_right, Kmat, bbox, heatmap, bs, n, t->n_kpt, H, W, score);
-    else LAUNCH1D(obj_heat_kernel<true>, (long long)bs * n, stream, pose, transl_override, root, t->kpt, obj_id, is_right, Kmat, bbox, heatmap, bs, n, t->n_kpt, H, W, score);
+    if (score_fp32()) LAUNCH1D(obj_heat_kernel<false>, (long long)bs * n, stream, pose, transl_override, root, t->kpt, obj_id, is_right, Kmat, bbox, heatmap, bs, n, t->n_kpt, t->n_obj, H, W, score);
+    else LAUNCH1D(obj_heat_kernel<true>, (long long)bs * n, stream, pose, transl_override, root, t->kpt, obj_id, is_right, Kmat, bbox, heatmap, bs, n, t->n_kpt, t->n_obj, H, W, score);
     return vpho::check_launch("obj_heat_kernel");
 }
 
@@ -818,7 +827,7 @@ extern "C" int vpho_obj_physics_score(const double* cand, int n, const float* ro
     VPHO_REQUIRE(cand && root && t && t->vert && t->com && obj_id && is_right && force_point && force_global && score && bs > 0 && n > 0, "vpho_obj_physics_score: bad argument");
     VPHO_REQUIRE(t->n_vert > 0 && (size_t)t->n_vert * 16 <= 64 * 1024, "vpho_obj_physics_score: object point cloud of %d vertices does not fit LDS", t->n_vert);
     ObjPhysArgs a;
-    a.cand = cand; a.n = n; a.root = root; a.vert_tab = t->vert; a.com_tab = t->com; a.obj_id = obj_id; a.is_right = is_right; a.nv = t->n_vert;
+    a.cand = cand; a.n = n; a.root = root; a.vert_tab = t->vert; a.com_tab = t->com; a.obj_id = obj_id; a.is_right = is_right; a.nv = t->n_vert; a.n_obj = t->n_obj;
     a.force_point = force_point; a.force_global = force_global; a.score = score;
     // algorithmic bytes: the object's vertex table and the 32 force points / forces once per image, 72-byte pose + score per candidate
     vpho::ProfScope prof(vpho::PROF_OBJ_PHYSICS, (hipStream_t)stream, 0.0,
@@ -840,7 +849,7 @@ extern "C" int vpho_obj_fuse_f64(const double* pose, int n, const int* idx_a, co
 extern "C" int vpho_obj_verts_f32(const double* pose, const float* root, const vpho_obj_tables* t, const int* obj_id,
                                   const unsigned char* is_right, int bs, float* out, void* stream) {
     VPHO_REQUIRE(pose && root && t && t->vert && obj_id && is_right && out && bs > 0, "vpho_obj_verts_f32: bad argument");
-    LAUNCH1D(obj_verts_kernel, (long long)bs * t->n_vert, stream, pose, root, t->vert, obj_id, is_right, bs, t->n_vert, out);
+    LAUNCH1D(obj_verts_kernel, (long long)bs * t->n_vert, stream, pose, root, t->vert, obj_id, is_right, bs, t->n_vert, t->n_obj, out);
     return vpho::check_launch("obj_verts_kernel");
 }
 
