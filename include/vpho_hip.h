@@ -576,6 +576,28 @@ VPHO_API long long vpho_hand_obj_intersection_workspace_bytes(int n, int F);
 VPHO_API int vpho_hand_obj_intersection_f64(const vpho_obj_mesh_tables* t, const vpho_obj_solids* solids, const int* faces, int F, const float* verts,
                                    int n, int V, const double* obj_rt, const int* obj_id, double pitch, double* out, unsigned char* flags,
                                    void* workspace, long long workspace_bytes, void* stream);
+/* The intersection volume of EVERY sampled hypothesis (--eval_best with --eval_volume), appended within ABI version 13: verts
+ * [n][S][V][3] fp32, obj_rt [n][S][3][4] fp64, obj_id [n]: hypothesis s of the hand against hypothesis s of the object.
+ * per_hyp [n][S][2] = n_cells | IV, the bits vpho_hand_obj_intersection_f64 gives in `out` for the n*S pairs (NaN for an obj_id outside
+ * [0, n_obj), for the whole image, and for a hypothesis with a non-finite hand vertex or a face index outside [0, V)); flags (optional)
+ * [n][S][solids->max_pts] has its bits too.  table [n][6] = one_IV, one_cells (hypothesis 0) | best_IV, best_cells (the minima over S) |
+ * mean_IV, mean_cells: mean_cells = (the exact integer sum of the cell counts) / S, mean_IV = ((h * h) * h) * mean_cells; a NaN
+ * hypothesis makes best and mean NaN.  The kernel walks lattice COLUMNS: vpho_obj_solid_columns names the runs of solids->pts that share
+ * x and y (the solid keeps lattice order, z fastest; vpho_amd/physics_eval.py: solid_columns); the part of the parity rule that depends
+ * on (x, y) and the face only runs once per column.  One workgroup per pair on grid.x: n * S <= 2147483647; V, F and the solids are
+ * free.  The face records are built in LDS per workgroup: vpho_hand_obj_intersection_multi_workspace_bytes is 0 (-1 on a bad argument)
+ * and workspace may be NULL.  S < 1, F <= 0 and pitch <= 0 are errors; n == 0 is a no-op.  Deterministic (min / max and integer adds). */
+typedef struct vpho_obj_solid_columns {
+    const int* col_start;    /* [col_offset[n_obj] + 1]: index into vpho_obj_solids.pts of each non-empty lattice column's first centre,
+                                columns in lattice order (i, then j), objects concatenated; a column ends where the next starts */
+    const int* col_offset;   /* [n_obj + 1] */
+    int n_obj, max_cols;
+} vpho_obj_solid_columns;
+VPHO_API long long vpho_hand_obj_intersection_multi_workspace_bytes(int n, int S, int F);
+VPHO_API int vpho_hand_obj_intersection_multi_f64(const vpho_obj_mesh_tables* t, const vpho_obj_solids* solids, const vpho_obj_solid_columns* cols,
+        const int* faces, int F, const float* verts /* [n][S][V][3] */, int n, int S, int V, const double* obj_rt /* [n][S][3][4] */,
+        const int* obj_id /* [n] */, double pitch, double* per_hyp /* [n][S][2] */, double* table /* [n][6] */,
+        unsigned char* flags /* NULL or [n][S][max_pts] */, void* workspace, long long workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Pseudo-force label optimisation (force_optim.py / lib/engine/force_optimization.py:110-207).

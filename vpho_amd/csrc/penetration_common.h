@@ -61,6 +61,32 @@ __device__ inline void pen_parity_step(const double* r, double qx, double qy, do
     }
 }
 
+// pen_parity_step split at the point where q_z first enters, for callers whose points share q_x, q_y and the cell (the centres of one
+// lattice column, intersection_volume_multi.hip): the same operations on the same operands in the same order, so
+//   if (pen_parity_xy(r, qx, qy, cx, cy, depth)) pen_parity_z(r, depth, qz, par0, par1);
+// leaves in par0, par1 the bits pen_parity_step(r, qx, qy, qz, cx, cy, par0, par1) leaves.  -> the triangle's projection holds (qx, qy)
+__device__ inline bool pen_parity_xy(const double* r, double qx, double qy, double cx, double cy, double& depth) {
+    if (r[R_CX0] <= cx && cx <= r[R_CX1] && r[R_CY0] <= cy && cy <= r[R_CY1]) {
+        const double y0 = qx - r[R_CX], y1 = qy - r[R_CY];
+        const double sdet = r[R_SDET], adet = r[R_ADET];
+        const double u = (r[R_A11] * y0 - r[R_A01] * y1) * sdet;
+        const double w = (-r[R_A10] * y0 + r[R_A00] * y1) * sdet;
+        const double suv = u + w;
+        if (0.0 < u && u < adet && 0.0 < w && w < adet && 0.0 < suv && suv < adet) {
+            const double alpha = r[R_N0] * (r[R_T1X] - qx) + r[R_N1] * (r[R_T1Y] - qy);
+            depth = r[R_D0] + alpha * r[R_SNZ];
+            return true;
+        }
+    }
+    return false;
+}
+
+__device__ inline void pen_parity_z(const double* r, double depth, double qz, unsigned& par0, unsigned& par1) {
+    const double zz = qz * r[R_ANZ];
+    par0 ^= (depth >= zz) ? 1u : 0u;
+    par1 ^= (depth < zz) ? 1u : 0u;
+}
+
 // squared distance from p to the triangle (a, a + ab, a + ac), g = fields R_AX .. R_ACZ of its record; ap = p - a
 __device__ inline double tri_dist2_geo(const double* g, double px, double py, double pz) {
     const double abx = g[3], aby = g[4], abz = g[5], acx = g[6], acy = g[7], acz = g[8];

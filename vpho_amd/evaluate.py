@@ -37,11 +37,16 @@ PHYS_MULTI = 12
 # ops_names.VOLUME_COLUMNS: IV (m^3) and the solid-cell count of (aggregated hand, aggregated object), then of the ground-truth pair.
 # Every column before them is the same with and without the flag.
 VOL = 4
+# with volume_multi (both command-line flags, cfg.eval_best AND cfg.eval_volume; an explicit argument of Trainer.eval / metric_rows
+# otherwise, as physics_multi) every row carries VOL_MULTI more columns IMMEDIATELY BEFORE the VOL block -- rows[:, -VOL:] is the volume
+# block in every layout --, in the order of ops_names.VOLUME_MULTI_COLUMNS: IV (m^3) and the solid-cell count of (hand hypothesis s,
+# object hypothesis s) reduced per image to hypothesis 0, best-of-S and mean-of-S.  Widths 98, 106 and 118: no other layout has them.
+VOL_MULTI = 6
 
 
-def row_width(eval_best=False, eval_physics=False, physics_multi=False, eval_volume=False):
+def row_width(eval_best=False, eval_physics=False, physics_multi=False, volume_multi=False, eval_volume=False):
     return (ROW_BEST if eval_best else ROW) + (PHYS if eval_physics else 0) + (PHYS_MULTI if eval_best and eval_physics and physics_multi else 0) + \
-        (VOL if eval_volume else 0)
+        (VOL_MULTI if eval_best and eval_volume and volume_multi else 0) + (VOL if eval_volume else 0)
 
 
 def mje_mm(pd, gt):
@@ -116,10 +121,11 @@ def multi_hypothesis_block(out, data, gt_joint, gt_vert, assets=None):
 _PHYSICS = {}
 
 
-def physics_meter(assets, device, multi=False, volume=False):
+def physics_meter(assets, device, multi=False, volume=False, volume_multi=False):
     """the HandObjectPenetration of an asset set on a device, built once (object meshes: physics_eval.object_meshes); its acceleration
     tables for the multi-hypothesis kernel only with ``multi`` (eval_best and eval_physics together), once as well; with ``volume``
-    (eval_volume) the closed hand mesh (physics_eval.hand_faces) and the objects' solids at cfg.physics_voxel_pitch, once per pitch"""
+    (eval_volume) the closed hand mesh (physics_eval.hand_faces) and the objects' solids at cfg.physics_voxel_pitch, once per pitch;
+    with ``volume_multi`` (eval_best and eval_volume together) also the solids' lattice columns, once per pitch"""
     key = (id(assets), str(device))
     if key not in _PHYSICS:
         from . import ops
@@ -128,12 +134,14 @@ def physics_meter(assets, device, multi=False, volume=False):
         _PHYSICS[key] = ops.HandObjectPenetration(object_meshes(assets, cfg.asset_root), device, accel=False)
     if multi:
         _PHYSICS[key].build_accel()
-    if volume:
+    if volume or volume_multi:
         from .configs.args import cfg
         if _PHYSICS[key].hand_faces is None:
             from .physics_eval import hand_faces
             _PHYSICS[key].set_hand_faces(hand_faces(assets))
         _PHYSICS[key].build_solids(float(cfg.physics_voxel_pitch))
+        if volume_multi:
+            _PHYSICS[key].build_solid_columns(float(cfg.physics_voxel_pitch))
     return _PHYSICS[key]
 
 
@@ -201,14 +209,34 @@ def physics_multi_block(out, data, meshes):
     return table.float()
 
 
-def metric_rows(out, data, gt_joint, gt_vert, first_index, assets=None, eval_best=False, eval_physics=False, physics_multi=False, eval_volume=False):
+def volume_multi_block(out, data, meshes):
+    """(bs, VOL_MULTI) fp32: the intersection volume of every sampled hypothesis, the pairing of
+    physics_multi_block -- hand candidate s (out['diff_final_hand_vert'][:, s], un-flipped + root) against object candidate s
+    (obj_9D_to_mat + root of out['diff_final_obj_6d'][:, s]) -- reduced per image to hypothesis 0 | best-of-S | mean-of-S by ONE
+    HandObjectPenetration.volume_multi launch pair.  ``meshes``: physics_meter(..., volume_multi=True)."""
+    from . import ops
+    from .configs.args import cfg
+    hv = out['diff_final_hand_vert']
+    if not hv.is_cuda:
+        raise RuntimeError('volume_multi_block: the intersection volume runs on the GPU only (no CPU path)')
+    bs, S = hv.shape[:2]
+    root = data['root_joint'].float().contiguous()
+    verts = hypotheses_to_camera(hv.float(), root, data['is_right']).contiguous()
+    pd_rt = ops.obj_9d_to_rt(out['diff_final_obj_6d'].reshape(bs * S, 9).double().contiguous(), root.repeat_interleave(S, 0).contiguous()).view(bs, S, 3, 4)
+    table, _ = meshes.volume_multi(verts, pd_rt, meshes.obj_ids(data['obj_name']), float(cfg.physics_voxel_pitch))
+    return table.float()
+
+
+def metric_rows(out, data, gt_joint, gt_vert, first_index, assets=None, eval_best=False, eval_physics=False, physics_multi=False, volume_multi=False,
+                eval_volume=False):
     """(bs, ROW) fp32 on the model's device; (bs, ROW_BEST) with eval_best (multi_hypothesis_block appended); PHYS more columns with
     eval_physics (physics_block), and with both and ``physics_multi`` PHYS_MULTI more (physics_multi_block; without it that block
     and its launch are left out: the rows of the two flags as they always were); VOL more with ``eval_volume`` (volume_block), last of
-    all, whatever the other flags are."""
+    all, whatever the other flags are; with eval_best, eval_volume and ``volume_multi`` VOL_MULTI more immediately before them
+    (volume_multi_block; without it that block and its launches are left out)."""
     pp = postprocess(out, data['root_joint'], data['is_right'])
     bs = gt_joint.shape[0]
-    rows = torch.empty((bs, row_width(eval_best, eval_physics, physics_multi, eval_volume)), device=gt_joint.device, dtype=torch.float32)
+    rows = torch.empty((bs, row_width(eval_best, eval_physics, physics_multi, volume_multi, eval_volume)), device=gt_joint.device, dtype=torch.float32)
     if torch.is_tensor(first_index):                 # per-image ids (a loader batch that is not a run of the data set)
         rows[:, 0] = first_index.to(device=rows.device, dtype=torch.float32).reshape(bs)
     else:
@@ -243,6 +271,8 @@ def metric_rows(out, data, gt_joint, gt_vert, first_index, assets=None, eval_bes
             raise ValueError('metric_rows: eval_volume needs the asset tables (object meshes, hand faces)')
         v0 = rows.shape[1] - VOL
         rows[:, v0:] = volume_block(pp, out, data, gt_vert, physics_meter(assets, gt_joint.device, volume=True))
+        if eval_best and volume_multi:
+            rows[:, v0 - VOL_MULTI:v0] = volume_multi_block(out, data, physics_meter(assets, gt_joint.device, volume_multi=True))
     from .configs.args import cfg
     if cfg.aggregation_mode_hand == '2D_pt_joint':
         # that mode fuses joints only; its vertices are the reference's all-zero mesh (aggregation.py:364-366): no vertex metric of it
@@ -374,8 +404,16 @@ def summarize(rows):
     from .ops_names import OBJ_METRIC_NAMES
     obj = rows[:, OBJ_COL:OBJ_COL + 16].double().mean(0)
     res['object'] = _object_table(obj)
-    # the widths without the volume block are 28, 88, 36, 96 and 108; with it each is 4 wider: no two layouts share a width
-    if rows.shape[1] in tuple(w + VOL for w in (ROW, ROW_BEST, ROW + PHYS, ROW_BEST + PHYS, ROW_BEST + PHYS + PHYS_MULTI)):
+    # the widths without the volume block are 28, 88, 36, 96 and 108; with it each is 4 wider, and the three with the eval_best block
+    # another 6 wider with the volume_multi block (98, 106, 118): no two layouts share a width
+    if rows.shape[1] in tuple(w + VOL_MULTI + VOL for w in (ROW_BEST, ROW_BEST + PHYS, ROW_BEST + PHYS + PHYS_MULTI)):
+        from .ops_names import MULTI_TABLES
+        res['volume'] = _volume_table(rows[:, -VOL:])
+        # every hypothesis' volume reduced per image (volume_multi_block): for mean_of_S an image counts as intersecting when its mean
+        # cell count is > 0
+        res['volume'].update(_volume_table(rows[:, -VOL - VOL_MULTI:-VOL], MULTI_TABLES))
+        rows = rows[:, :-VOL - VOL_MULTI]
+    elif rows.shape[1] in tuple(w + VOL for w in (ROW, ROW_BEST, ROW + PHYS, ROW_BEST + PHYS, ROW_BEST + PHYS + PHYS_MULTI)):
         res['volume'] = _volume_table(rows[:, -VOL:])
         rows = rows[:, :-VOL]
     p0 = {ROW + PHYS: ROW, ROW_BEST + PHYS: ROW_BEST, ROW_BEST + PHYS + PHYS_MULTI: ROW_BEST}.get(rows.shape[1])
@@ -403,13 +441,13 @@ def _object_table(obj):
             for i, k in enumerate(OBJ_METRIC_NAMES)}
 
 
-def _volume_table(blk):
-    """volume table over all images, per source (pred / gt): mean and largest intersection volume (cm^3) and the share of images with
-    at least one solid cell of the object inside the hand (%); NaN for a source without values"""
+def _volume_table(blk, names=None):
+    """volume table over all images, per source (pred / gt; one_candidate / best_of_S / mean_of_S): mean and largest intersection volume
+    (cm^3) and the share of images with at least one solid cell of the object inside the hand (%); NaN for a source without values"""
     from .ops_names import PHYSICS_SOURCES
     blk = blk.double()
     res = {}
-    for s, name in enumerate(PHYSICS_SOURCES):
+    for s, name in enumerate(PHYSICS_SOURCES if names is None else names):
         iv, cells = blk[:, 2 * s], blk[:, 2 * s + 1]
         res[name] = dict(IV_cm3=float(iv.mean() * 1e6), IV_max_cm3=float(iv.max() * 1e6) if iv.shape[0] else float('nan'),
                          intersecting_pct=float((cells > 0).double().mean() * 100.0) if not cells.isnan().any() else float('nan'))

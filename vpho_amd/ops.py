@@ -28,6 +28,7 @@ lib.vpho_conv2d_wgrad_workspace_bytes.restype = C.c_longlong
 lib.vpho_mha_bwd_workspace_bytes.restype = C.c_longlong
 lib.vpho_infer_record_bytes.restype = C.c_longlong
 lib.vpho_hand_obj_intersection_workspace_bytes.restype = C.c_longlong
+lib.vpho_hand_obj_intersection_multi_workspace_bytes.restype = C.c_longlong
 
 
 class VphoError(RuntimeError):
@@ -1215,6 +1216,13 @@ class ObjSolids(C.Structure):
     _fields_ = [('pts', C.c_void_p), ('pt_offset', C.c_void_p), ('n_obj', I), ('max_pts', I)]
 
 
+class ObjSolidColumns(C.Structure):
+    _fields_ = [('col_start', C.c_void_p), ('col_offset', C.c_void_p), ('n_obj', I), ('max_cols', I)]
+
+
+VOLUME_MULTI_MAX_PAIRS = 0x7fffffff      # vpho_hand_obj_intersection_multi_f64: one workgroup per (image, hypothesis) on grid.x
+
+
 class HandObjectPenetration:
     """Hand-object penetration and contact (--eval_physics) on the device: per-triangle tables of every object mesh,
     built once (physics_eval.mesh_tables), + thin wrapper of vpho_hand_obj_penetration_f64.  ``meshes``: {name: {'verts', 'faces'}}
@@ -1222,7 +1230,8 @@ class HandObjectPenetration:
     acceleration tables of physics_eval.mesh_accel, built here once as well (``accel=False`` leaves them out: ``multi`` then raises until
     ``build_accel()`` is called).  ``volume`` is the hand-object intersection volume (--eval_volume, vpho_hand_obj_intersection_f64) of a
     hand mesh (``hand_faces``: one closed (F, 3) face list, physics_eval.hand_faces) with the objects' solid point sets, which
-    ``build_solids(pitch)`` makes once per pitch."""
+    ``build_solids(pitch)`` makes once per pitch.  ``volume_multi`` is that volume for every sampled hypothesis
+    (vpho_hand_obj_intersection_multi_f64), a walk of the solids' lattice columns (``build_solid_columns(pitch)``, once per pitch)."""
 
     def __init__(self, meshes, device, accel=True, hand_faces=None):
         import numpy as np
@@ -1239,7 +1248,7 @@ class HandObjectPenetration:
         self.n_tri = counts
         self.device = device
         self._tabs, self.acc = tabs, None
-        self._meshes, self._solids, self.hand_faces = meshes, {}, None
+        self._meshes, self._solids, self._columns, self.hand_faces = meshes, {}, {}, None
         if hand_faces is not None:
             self.set_hand_faces(hand_faces)
         if accel:
@@ -1342,6 +1351,75 @@ class HandObjectPenetration:
         _call('vpho_hand_obj_intersection_f64', C.byref(self.c), C.byref(sol['c']), _i32(self.hand_faces), I(F_), _f32(verts), I(n), I(V),
               _f64(obj_rt), _i32(obj_id), C.c_double(pitch), _f64(out), _u8(fl), _ptr(ws), LL(ws.numel()))
         return (out, fl) if flags else out
+
+    def build_solid_columns(self, pitch):
+        """The lattice columns of the objects' solids at one voxel pitch, once per pitch: physics_eval.solid_columns of every object's
+        part of build_solids(pitch)['pts'] (which is built first if need be, and stays as it is), run starts made global and concatenated.
+        -> dict(col_start (C + 1,) and col_offset (n_obj + 1,) int32 on the device, counts, max_cols, c = ObjSolidColumns)."""
+        import numpy as np
+        from .physics_eval import solid_columns
+        sol = self.build_solids(pitch)
+        key = sol['pitch']
+        if key in self._columns:
+            return self._columns[key]
+        pts = sol['pts'].cpu().numpy()
+        off = np.concatenate([[0], np.cumsum(sol['counts'])]).astype(np.int64)
+        starts, counts = [], []
+        for o in range(len(self.names)):
+            cs = solid_columns(pts[off[o]:off[o + 1]])
+            starts.append(cs[:-1].astype(np.int64) + off[o])
+            counts.append(len(cs) - 1)
+        col_start = torch.as_tensor(np.concatenate(starts + [off[-1:]]).astype(np.int32)).to(self.device)
+        col_offset = torch.as_tensor(np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)).to(self.device)
+        cols = dict(col_start=col_start, col_offset=col_offset, counts=counts, max_cols=max(counts), pitch=key)
+        cols['c'] = ObjSolidColumns(col_start.data_ptr(), col_offset.data_ptr(), len(self.names), cols['max_cols'])
+        torch.cuda.current_stream(col_start.device).synchronize()     # built on this stream, read by kernels of any stream afterwards
+        self._columns[key] = cols
+        return cols
+
+    def volume_multi(self, verts, obj_rt, obj_id, pitch=None, flags=False):
+        """The intersection volume of every sampled hypothesis: verts (n,S,V,3) fp32 and obj_rt (n,S,3,4) fp64 in the camera frame,
+        hypothesis s of the hand against hypothesis s of the object; obj_id as in __call__ (one per image); ``pitch`` as in ``volume``.
+        -> table (n,6) fp64 in the order of ops_names.VOLUME_MULTI_COLUMNS (hypothesis 0 | the minima over S | mean_cells = integer sum /
+        S and mean_IV = pitch^3 * mean_cells; a NaN hypothesis makes best and mean NaN) and per_hyp (n,S,2) fp64 = n_cells | IV, the bits
+        ``volume`` gives for the n*S pairs; with ``flags`` also (n,S,max_pts) uint8 with its bits.  n * S <= VOLUME_MULTI_MAX_PAIRS."""
+        if pitch is None:
+            from .configs.args import cfg
+            pitch = cfg.physics_voxel_pitch
+        pitch = float(pitch)
+        if not pitch > 0.0:
+            raise VphoError(f'HandObjectPenetration.volume_multi: the voxel pitch must be positive ({pitch})')
+        if self.hand_faces is None:
+            raise VphoError('HandObjectPenetration.volume_multi: no hand mesh (pass hand_faces= or call set_hand_faces)')
+        n, S, V = verts.shape[:3]
+        assert verts.shape == (n, S, V, 3) and obj_rt.shape == (n, S, 3, 4)
+        if S < 1:
+            raise VphoError(f'HandObjectPenetration.volume_multi: no hypotheses (S={S})')
+        if n * S > VOLUME_MULTI_MAX_PAIRS:
+            raise VphoError(f'HandObjectPenetration.volume_multi: {n} x {S} pairs, at most {VOLUME_MULTI_MAX_PAIRS} in one call')
+        if self.hand_faces_max >= V:
+            raise VphoError(f'HandObjectPenetration.volume_multi: the hand faces index vertex {self.hand_faces_max}, the hands have {V}')
+        if not torch.is_tensor(obj_id):
+            ids = [int(i) for i in obj_id]
+            if len(ids) != n or any(i < 0 or i >= len(self.names) for i in ids):
+                raise VphoError(f'HandObjectPenetration: object ids {ids} outside [0, {len(self.names)}) or not one per image')
+            obj_id = _ids_to_device(ids, self.device)
+        assert obj_id.shape == (n,)
+        sol = self.build_solids(pitch)
+        cols = self.build_solid_columns(pitch)
+        F_ = int(self.hand_faces.shape[0])
+        table = _new((n, 6), obj_rt, torch.float64)
+        per = _new((n, S, 2), obj_rt, torch.float64)
+        fl = _new((n, S, sol['max_pts']), obj_rt, torch.uint8) if flags else None
+        if n == 0:
+            return (table, per, fl) if flags else (table, per)
+        need = lib.vpho_hand_obj_intersection_multi_workspace_bytes(I(n), I(S), I(F_))
+        if need < 0:
+            raise VphoError('vpho_hand_obj_intersection_multi_workspace_bytes: bad argument')
+        ws = torch.empty(need, dtype=torch.uint8, device=self.device) if need else None       # per call, as in volume
+        _call('vpho_hand_obj_intersection_multi_f64', C.byref(self.c), C.byref(sol['c']), C.byref(cols['c']), _i32(self.hand_faces), I(F_),
+              _f32(verts), I(n), I(S), I(V), _f64(obj_rt), _i32(obj_id), C.c_double(pitch), _f64(per), _f64(table), _u8(fl), _ptr(ws), LL(need))
+        return (table, per, fl) if flags else (table, per)
 
     def obj_ids(self, names):
         """class indices of a batch as a device tensor (pinned host memory, asynchronous copy on the caller's stream, as

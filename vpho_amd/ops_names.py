@@ -29,3 +29,8 @@ PHYSICS_MULTI_COLUMNS = tuple(f'physics/{t}/{k}' for t in MULTI_TABLES for k in 
 VOLUME_COLUMNS = ('pred_IV_m3', 'pred_cells', 'gt_IV_m3', 'gt_cells')
 # the summarize / EVAL_JSON table 'volume', per source: mean IV (cm^3), largest IV (cm^3), share of images with a cell inside (%)
 VOLUME_TABLE = ('IV_cm3', 'IV_max_cm3', 'intersecting_pct')
+# the block that evaluate.metric_rows puts immediately before the VOLUME_COLUMNS with eval_best AND eval_volume (and volume_multi): the
+# intersection volume of every sampled hypothesis (hand candidate s against object candidate s), per image reduced to hypothesis 0,
+# best-of-S (the minima) and mean-of-S (mean_cells = integer sum / S, mean_IV = pitch^3 * mean_cells); the 'volume' table gains the three
+# MULTI_TABLES entries beside 'pred' and 'gt', each with the VOLUME_TABLE keys
+VOLUME_MULTI_COLUMNS = ('one_IV_m3', 'one_cells', 'best_IV_m3', 'best_cells', 'mean_IV_m3', 'mean_cells')

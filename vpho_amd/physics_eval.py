@@ -302,3 +302,17 @@ def solid_lattice(verts, faces, pitch):
     ax = [lo[a] + (np.arange(dims[a], dtype=np.float64) + 0.5) * h for a in range(3)]
     c = np.stack(np.meshgrid(*ax, indexing='ij'), -1).reshape(-1, 3)
     return np.ascontiguousarray(c.astype(np.float32)), dims
+
+
+def solid_columns(pts):
+    """Run starts of equal (x, y) in a lattice-ordered (P, 3) fp32 point set (the kept centres of ``solid_lattice``: k fastest, so the
+    centres of one lattice column (i, j) are one contiguous run with the same fp32 x and y, whatever gaps the solid leaves along k; an
+    empty column has no run).  -> col_start (C + 1,) int32: the index of every run's first point, then P.  The runs are what
+    ``vpho_obj_solid_columns`` (include/vpho_hip.h) hands to the column-walk kernel; x, y are compared as bits of the fp32 values."""
+    p = np.ascontiguousarray(np.asarray(pts, np.float32).reshape(-1, 3))
+    n = p.shape[0]
+    if n == 0:
+        return np.zeros(1, np.int32)
+    xy = p[:, :2].copy().view(np.uint32)
+    new = np.concatenate([[True], (xy[1:] != xy[:-1]).any(1)])
+    return np.concatenate([np.nonzero(new)[0], [n]]).astype(np.int32)

@@ -214,7 +214,7 @@ class Trainer:
             seen += n
 
     @torch.no_grad()
-    def eval(self, loader=None, eval_best=None, eval_physics=None, physics_multi=None, eval_volume=None):
+    def eval(self, loader=None, eval_best=None, eval_physics=None, physics_multi=None, eval_volume=None, volume_multi=None):
         """``evaluate(testing_dataloader)`` (train_diff_hand_obj.py:202-357).  ``loader``: see ``_eval_batches``; default synthetic.
         ``eval_best`` (default: cfg.eval_best, the reference's is_eval_best): also score every sampled hypothesis and report the
         one_candidate, best_of_S and mean_of_S tables (rows of evaluate.ROW_BEST columns).  ``eval_physics`` (default:
@@ -223,12 +223,19 @@ class Trainer:
         every sampled hypothesis' penetration as well (evaluate.PHYS_MULTI more columns, last; the ``physics`` table gains
         one_candidate, best_of_S and mean_of_S).  A caller that passes eval_best / eval_physics itself gets the rows it always got
         unless it asks for the new block too.  ``eval_volume`` (default: cfg.eval_volume; independent of the others): also report the
-        hand-object intersection volume at cfg.physics_voxel_pitch, the ``volume`` table (evaluate.VOL more columns, last of all)."""
+        hand-object intersection volume at cfg.physics_voxel_pitch, the ``volume`` table (evaluate.VOL more columns, last of all).
+        ``volume_multi`` (default: cfg.eval_best and cfg.eval_volume, i.e. both command-line flags; it needs eval_best and eval_volume):
+        every sampled hypothesis' intersection volume as well (evaluate.VOL_MULTI more columns immediately before the VOL block; the
+        ``volume`` table gains one_candidate, best_of_S and mean_of_S).  As with physics_multi, a caller that passes eval_best /
+        eval_volume itself gets the rows it always got unless it asks for the new block too."""
         from .configs.args import cfg
         eval_volume = bool(cfg.eval_volume if eval_volume is None else eval_volume)
         # the keyword travels to metric_rows only when it is set: without it the call is the one it always was
         vol = dict(eval_volume=True) if eval_volume else {}
         eval_best = bool(cfg.eval_best if eval_best is None else eval_best)
+        volume_multi = bool((cfg.eval_best and cfg.eval_volume) if volume_multi is None else volume_multi) and eval_best and eval_volume
+        if volume_multi:
+            vol['volume_multi'] = True
         eval_physics = bool(cfg.eval_physics if eval_physics is None else eval_physics)
         physics_multi = bool((cfg.eval_best and cfg.eval_physics) if physics_multi is None else physics_multi) and eval_best and eval_physics
         if eval_physics:
@@ -236,7 +243,7 @@ class Trainer:
             E.physics_meter(self.assets, self.device, multi=physics_multi)
         if eval_volume:
             # the closed hand mesh and the objects' solids at the configured pitch, once, before the timed loop
-            E.physics_meter(self.assets, self.device, volume=True)
+            E.physics_meter(self.assets, self.device, volume=True, volume_multi=volume_multi)
         rows = []
         t0 = time.perf_counter()
         # three batches in flight (independent images; see evaluate.PipelinedPredictor)
@@ -262,7 +269,7 @@ class Trainer:
         pipe.close()
         # a rank whose shard is empty still takes part in the collective (with zero rows: the ragged gather carries the counts first);
         # raising here would leave the other ranks blocked in their all-gather.  Only an evaluation without ANY image is an error
-        mine = torch.cat(rows, 0) if rows else torch.zeros((0, E.row_width(eval_best, eval_physics, physics_multi, eval_volume)), device=self.device, dtype=torch.float32)
+        mine = torch.cat(rows, 0) if rows else torch.zeros((0, E.row_width(eval_best, eval_physics, physics_multi, volume_multi, eval_volume)), device=self.device, dtype=torch.float32)
         rows = E.gather_rows(mine)
         if rows.shape[0] == 0:
             raise ValueError('Trainer.eval: the loader yielded no batch on any rank')
