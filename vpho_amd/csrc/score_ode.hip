@@ -507,7 +507,24 @@ struct HeadArgs {
 // 256 of them add ~20 us to a 232-us launch.  A four-stage prefetch ring for them -- fills three stages ahead, 80 KB of LDS -- changed
 // nothing (233-235 us): the stage time is the 24 KB of weights a tail workgroup streams for 32 rows, ~70 GB/s per CU from L2, not a
 // latency.  Dropped.)
-template <int TI, bool CB>
+//
+// EPI selects how the epilogue's operands are laid out in LDS and when they are requested (same arithmetic in the same order either way:
+// bit-identical scores, tests/test_gpu_head_epilogue.py):
+//   EPI = 0  the table is [256][4] records {ct, w2_0, w2_1, w2_2}, the per-image copy has slot stride 257, every element reads its record
+//            (ds_read_b128) and its cimg (ds_read_b32) right in front of its arithmetic -- two reads per element, 26 lgkmcnt(0) waits per
+//            128-row tile, and the (w2_0, w2_1) pair on an odd register (188 v_mov per tile to re-pair packed operands).  Kept as the
+//            reference kernel score_head_epi0_kernel (VPHO_HEAD_EPI=0).
+//   EPI = 1  a lane's 16 elements of an accumulator tile are four runs of four consecutive hidden units j (e & 3), so the table is
+//            [64 groups of 4 j][16]: {w2_0, w2_1} x 4 | w2_2 x 4 | ct x 4 -- four ds_read_b128 serve four elements and the pair that is
+//            multiplied and added together sits on an even register pair; the per-image copy has slot stride 260 (a multiple of 4 floats:
+//            one ds_read_b128 per four elements; the at most two images of a 16-lane read group sit 4 banks apart).  5 reads per four
+//            elements instead of 8.  The reads of a run are requested together, EPI_AHEAD runs ahead of the arithmetic (the first ones
+//            in front of the main loop's closing barrier, where the fragment registers are free), pinned by sched_barrier.  One run of
+//            20 registers ahead is what the budget holds: 64 accumulators + two runs + addresses = 118 of the 128 registers of two
+//            workgroups per CU (half an accumulator tile per batch, one batch ahead, would be 80 registers of operands).  Measured:
+//            profiles/head_epilogue_ab.txt, docs/LOG.md.
+constexpr int EPI_AHEAD = 1;
+template <int TI, bool CB, int EPI>
 __device__ __forceinline__ void head_tile(const HeadArgs& a, float* smem, const int n, const int r0) {
     constexpr int ROWS = TI == 4 ? 128 : 32, PARTS = 8;              // partial sums per row: one per 32 hidden units, whatever the tile kind
     constexpr int STAGE = (256 + 128) * HB_K;
@@ -526,12 +543,12 @@ __device__ __forceinline__ void head_tile(const HeadArgs& a, float* smem, const 
 
     // Per-image terms of the epilogue (cimg: the encoding's share of the first layer, one 256-vector per image and head).  A tile's rows
     // span a few images (128 rows of sample_num 100: at most 3): their vectors are staged in LDS next to the epilogue table, slot stride
-    // 257 floats so that the lanes of a half-wave -- same hidden unit, neighbouring images -- hit different banks.  Round 4 read them
+    // 257 floats (EPI = 1: 260) so that the lanes of a half-wave -- same hidden unit, neighbouring images -- hit different banks.  Round 4 read them
     // with 64 global loads per lane in the epilogue: 16 waves x 64 dword loads through the CU's one texture-address path = ~7 us of a
     // 62-us tile life with the matrix pipe idle (profiles/r05_inkernel_clock.txt: epilogue 13.6 us median).  Same values, same order of
     // additions: bit-identical.  CB = sample_num >= 64 (chosen by the host: a 128-row tile then spans at most 3 images); smaller
     // sample_num (a 128-row tile of sample_num 4 spans 33 images -- and is a tiny launch) keeps the global loads.
-    constexpr int CB_LD = 257;
+    constexpr int CB_LD = EPI ? 260 : 257;
     float* Cb = Eb + 256 * 4;                                       // [3][CB_LD] <= the 1024 floats behind the table
     const int img0 = r0 / a.S;
     const int img_last = (min(r0 + ROWS, a.R) - 1) / a.S;
@@ -539,8 +556,14 @@ __device__ __forceinline__ void head_tile(const HeadArgs& a, float* smem, const 
         f32x4 e;
         e[0] = a.ct[n * 256 + tid];
         const f32x4 w2 = *reinterpret_cast<const f32x4*>(a.w2 + (long long)(n * 256 + tid) * 4);
-        e[1] = w2[0]; e[2] = w2[1]; e[3] = w2[2];
-        *reinterpret_cast<f32x4*>(Eb + tid * 4) = e;
+        if (EPI) {
+            float* g = Eb + (tid >> 2) * 16;
+            const int c = tid & 3;
+            g[2 * c] = w2[0]; g[2 * c + 1] = w2[1]; g[8 + c] = w2[2]; g[12 + c] = e[0];
+        } else {
+            e[1] = w2[0]; e[2] = w2[1]; e[3] = w2[2];
+            *reinterpret_cast<f32x4*>(Eb + tid * 4) = e;
+        }
     } else if (CB) {
         const int j = tid - 256;
         for (int sl = 0; sl <= img_last - img0; ++sl) Cb[sl * CB_LD + j] = a.cimg[(long long)(img0 + sl) * a.NH + n * 256 + j];
@@ -625,17 +648,35 @@ __device__ __forceinline__ void head_tile(const HeadArgs& a, float* smem, const 
         if (kt + 2 < NK && !(HEAD_ABLATE & 1)) fill(buf, kt + 2);
         mfmas();
     }
-    __syncthreads();
-    VPHO_PRIO_REST();
-    VPHO_STAMP_AT(3);
-    if ((HEAD_ABLATE & 8) && acc[0][0] != 1.2345e-30f) return;       // timing: no epilogue
-
     // epilogue: hidden unit j = 32*TI*hh + 32*i + (e&3) + 8*(e>>2) + 4*lh on the register, hypothesis on the lane
     const int lrow_out = rg * 32 + li;
     const int row = r0 + lrow_out;
     const bool live = row < a.R;
     const float* cim = a.cimg + (long long)(live ? row / a.S : 0) * a.NH + n * 256;
     const float* cbl = Cb + (live ? row / a.S - img0 : 0) * CB_LD;  // this lane's image in the LDS copy (CB)
+    // EPI = 1: the operands of run g = 4 i + q (elements e = 4 q .. 4 q + 3 of accumulator tile i), five 16-byte reads requested together
+    struct EpiRun { f32x4 w01a, w01b, w2, ct, ci; };
+    constexpr int NRUN = 4 * TI, NRING = EPI_AHEAD + 1;
+    EpiRun ring[NRING];
+    auto request = [&](const int g) {
+        const int j = 32 * TI * hh + 32 * (g >> 2) + 8 * (g & 3) + 4 * lh;
+        const float* t = Eb + j * 4;                                // group j / 4, 16 floats each
+        EpiRun& r = ring[g % NRING];
+        r.w01a = *reinterpret_cast<const f32x4*>(t);     r.w01b = *reinterpret_cast<const f32x4*>(t + 4);
+        r.w2   = *reinterpret_cast<const f32x4*>(t + 8); r.ct   = *reinterpret_cast<const f32x4*>(t + 12);
+        r.ci   = *reinterpret_cast<const f32x4*>((CB ? cbl : cim) + j);
+    };
+    if (EPI) {   // the table and the per-image copy lie behind the stages and were complete before the first stage barrier
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int g = 0; g < EPI_AHEAD; ++g) request(g);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    __syncthreads();
+    VPHO_PRIO_REST();
+    VPHO_STAMP_AT(3);
+    if ((HEAD_ABLATE & 8) && acc[0][0] != 1.2345e-30f) return;       // timing: no epilogue
+
     // The 256 hidden units of a row are summed as EIGHT partial sums of 32 (hidden 32 p .. 32 p + 31 = one 32 x 32 accumulator tile: two
     // 16-term lane sums added), combined in ascending p -- in an ordinary 128-row tile (a wave holds four of the eight) exactly as in a
     // 32-row tail tile (a wave holds one).  Round 3 let an ordinary tile sum 2 x 128: which rows of a launch fall into tail tiles
@@ -645,6 +686,31 @@ __device__ __forceinline__ void head_tile(const HeadArgs& a, float* smem, const 
 #pragma unroll
     for (int i = 0; i < TI; ++i) {
         float o0 = 0.f, o1 = 0.f, o2 = 0.f;
+        if (EPI) {
+            // the same operations per element as below, written on register pairs so that they issue as packed instructions: the two
+            // additions and the w2_2 product for two neighbouring elements at once, the (w2_0, w2_1) products and sums for one element
+            typedef float f32x2 __attribute__((ext_vector_type(2)));
+            f32x2 o01 = {0.f, 0.f};
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int g = 4 * i + q;
+                if (g + EPI_AHEAD < NRUN) request(g + EPI_AHEAD);   // the next run(s) in flight under this run's arithmetic
+                __builtin_amdgcn_sched_barrier(0);
+                const EpiRun& r = ring[g % NRING];
+#pragma unroll
+                for (int c = 0; c < 4; c += 2) {
+                    f32x2 h = f32x2{acc[i][4 * q + c], acc[i][4 * q + c + 1]} + f32x2{r.ci[c], r.ci[c + 1]};
+                    h = h + f32x2{r.ct[c], r.ct[c + 1]};
+                    h[0] = h[0] > 0.f ? h[0] : 0.f; h[1] = h[1] > 0.f ? h[1] : 0.f;
+                    const f32x4& w01 = c < 2 ? r.w01a : r.w01b;
+                    const f32x2 t2 = h * f32x2{r.w2[c], r.w2[c + 1]};
+                    o01 = o01 + f32x2{h[0], h[0]} * f32x2{w01[0], w01[1]}; o2 += t2[0];
+                    o01 = o01 + f32x2{h[1], h[1]} * f32x2{w01[2], w01[3]}; o2 += t2[1];
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            o0 = o01[0]; o1 = o01[1];
+        } else {
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
             const int j = 32 * TI * hh + 32 * i + (e & 3) + 8 * (e >> 2) + 4 * lh;
@@ -653,7 +719,18 @@ __device__ __forceinline__ void head_tile(const HeadArgs& a, float* smem, const 
             h = h > 0.f ? h : 0.f;
             o0 += h * t[1]; o1 += h * t[2]; o2 += h * t[3];
         }
-        o0 += __shfl_xor(o0, 32); o1 += __shfl_xor(o1, 32); o2 += __shfl_xor(o2, 32);
+        }
+        if (EPI) {
+            // own sum + the other half-wave's, as below, by one half exchange in the vector unit instead of a trip through the LDS queue
+            // (behind the reads already requested for the next run); only the lower half's result is used
+            auto cross = [](const float v) {
+                const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+                return __uint_as_float(r[0]) + __uint_as_float(r[1]);        // lanes 0-31: v + v of lane + 32
+            };
+            o0 = cross(o0); o1 = cross(o1); o2 = cross(o2);
+        } else {
+            o0 += __shfl_xor(o0, 32); o1 += __shfl_xor(o1, 32); o2 += __shfl_xor(o2, 32);
+        }
         if (lh == 0) {
             float* ob = Ob + ((hh * TI + i) * ROWS + lrow_out) * 4;
             ob[0] = o0; ob[1] = o1; ob[2] = o2;
@@ -693,11 +770,12 @@ __device__ __forceinline__ void head_tile(const HeadArgs& a, float* smem, const 
     VPHO_STAMP_WRITE(head, blockIdx.x);
 }
 
-template <bool CB>
-__global__ __launch_bounds__(512, 4) void score_head_kernel(const HeadArgs a) {
+template <bool CB, int EPI>
+__device__ __forceinline__ void score_head_body(const HeadArgs& a) {
     extern __shared__ __attribute__((aligned(1024))) float smem[];
     // [2] stages x ([256][HB_K] weights | [128][HB_K] activations), unpadded rows filled by global_load_lds with the 16-B chunk
-    // index XOR-swizzled (see conv_igemm_glds_kernel); then [256][4] {ct, w2_0, w2_1, w2_2}; the [8][ROWS][4] partial outputs of the epilogue reuse the stages
+    // index XOR-swizzled (see conv_igemm_glds_kernel); then the 1024-float epilogue table (layout: head_tile, EPI) and the per-image copy; the
+    // [8][ROWS][4] partial outputs of the epilogue reuse the stages
     if (ctl_skip(a.ctl, a.ctl_mode)) return;
     // (measured no better, round 5: 64-row tiles for launches with fewer 128-row tiles than CUs -- the object head, 3 heads x 50 tiles = 150
     // workgroups -> 300: 39.4-39.5 us against 39.8-40.2, step unchanged.  A tile alone on its CU is a chain of 16 barrier-separated k stages,
@@ -706,12 +784,17 @@ __global__ __launch_bounds__(512, 4) void score_head_kernel(const HeadArgs a) {
     // tail tiles, 231 us -- a tail tile is bound by its chain of 16 barrier-separated weight stages, not by where the weights are)
     const int b = blockIdx.x, n_full = a.nheads * a.full_tiles;
     if (b < n_full) {
-        head_tile<4, CB>(a, smem, b / a.full_tiles, (b % a.full_tiles) * 128);
+        head_tile<4, CB, EPI>(a, smem, b / a.full_tiles, (b % a.full_tiles) * 128);
     } else {
         const int q = b - n_full;
-        head_tile<1, CB>(a, smem, q / a.tail_tiles, a.full_tiles * 128 + (q % a.tail_tiles) * 32);
+        head_tile<1, CB, EPI>(a, smem, q / a.tail_tiles, a.full_tiles * 128 + (q % a.tail_tiles) * 32);
     }
 }
+template <bool CB>
+__global__ __launch_bounds__(512, 4) void score_head_kernel(const HeadArgs a) { score_head_body<CB, 1>(a); }
+// the epilogue as it was before the run layout (VPHO_HEAD_EPI=0): the reference of tests/test_gpu_head_epilogue.py and of the A/B in docs/LOG.md
+template <bool CB>
+__global__ __launch_bounds__(512, 4) void score_head_epi0_kernel(const HeadArgs a) { score_head_body<CB, 0>(a); }
 
 // --------------------------------------------------------------------------------------------- persistent score head (round 5 experiment, opt-in: VPHO_HEAD_PERS=1)
 // The in-kernel stamps of profiles/r05_inkernel_clock.txt: a 128-row tile lives 62 us -- entry 0.7, first fill wait 1.0, main loop 45,
@@ -1576,6 +1659,8 @@ int eval_net(Ctx& c, const float* X, float t, int rhs_mode, float coef, float* o
     if (getenv("VPHO_HEAD_LDS")) lds = (size_t)atoi(getenv("VPHO_HEAD_LDS"));   // tuning aid: force 1 block/CU
     VPHO_DYN_LDS(score_head_kernel<true>, lds);
     VPHO_DYN_LDS(score_head_kernel<false>, lds);
+    VPHO_DYN_LDS(score_head_epi0_kernel<true>, lds);
+    VPHO_DYN_LDS(score_head_epi0_kernel<false>, lds);
     // Tile plan: 128-row tiles; when the last round of the launch would be less than half full, the rows beyond the last full round
     // become 32-row tail tiles (see head_tile).  VPHO_HEAD_TAIL=0: ordinary tiles only.
     static const int tail_on = getenv("VPHO_HEAD_TAIL") ? atoi(getenv("VPHO_HEAD_TAIL")) : 1;
@@ -1626,8 +1711,13 @@ int eval_net(Ctx& c, const float* X, float t, int rhs_mode, float coef, float* o
             hipLaunchKernelGGL(score_head_pers_kernel<true>, pgrid, dim3(512), plds, c.s, a);       // sample_num >= 64 (the LDS copy of the per-image terms); smaller: the one-tile kernel
             return vpho::check_launch("score_head_pers_kernel");
         }
-        if (cb) hipLaunchKernelGGL(score_head_kernel<true>, grid, dim3(512), lds, c.s, a);
-        else    hipLaunchKernelGGL(score_head_kernel<false>, grid, dim3(512), lds, c.s, a);
+        // VPHO_HEAD_EPI=0: the reference epilogue (read per call; same bits)
+        const char* epi_s = getenv("VPHO_HEAD_EPI");
+        if (epi_s && atoi(epi_s) == 0) {
+            if (cb) hipLaunchKernelGGL(score_head_epi0_kernel<true>, grid, dim3(512), lds, c.s, a);
+            else    hipLaunchKernelGGL(score_head_epi0_kernel<false>, grid, dim3(512), lds, c.s, a);
+        } else if (cb) hipLaunchKernelGGL(score_head_kernel<true>, grid, dim3(512), lds, c.s, a);
+        else           hipLaunchKernelGGL(score_head_kernel<false>, grid, dim3(512), lds, c.s, a);
     }
     return vpho::check_launch("score_head_kernel");
 }
