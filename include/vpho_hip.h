@@ -475,6 +475,27 @@ VPHO_API int vpho_obj_metrics_multi_f64(const vpho_obj_metric_tables* t, const d
                                const int* obj_id, int n_img, int n_hyp, int max_verts, double* out, double* best, double* mean,
                                void* workspace, long long workspace_bytes, void* stream);
 
+/* Hand benchmark metrics for every sampled hypothesis (--eval_hand_bench), appended within ABI version 13.  They
+ * replace nothing in the reference: the definitions are those of the FreiHAND / HO3D leaderboards' eval.py (F-score at two distances,
+ * AUC of the PCK curve), the alignment is rigid_align_AtoB (lib/utils/transform_fn.py:43-66) as in vpho_hand_metrics_multi_f32.
+ * vpho_hand_bench_multi_f32: pd, gt, root_joint, is_right as in vpho_hand_metrics_multi_f32 (postprocess applied on load); A = the
+ *   postprocessed hypothesis, B = the ground truth, A^ = the aligned A (fp64).  Per-point errors e = |X - B| in fp64 for X = A, A^.
+ *   auc_thresh [n_thresh] ascending fp64 thresholds (metres), auc_g [n_thresh + 1]: auc_g[c] = the normalised trapezoid integral of the
+ *   step 1[e <= t] for a point with c = #{j : e <= auc_thresh[j]}; AUC = (sum_p auc_g[c_p]) / n_pts.  With with_fscore != 0 also, for
+ *   th in (f_thresh_lo, f_thresh_hi): precision = #{d1 < th} / n_pts, recall = #{d2 < th} / n_pts (d1: B's points to their nearest point of
+ *   X, d2: X's points to their nearest point of B; fp32 brute force on points centred on B's centroid), F = 2 p r / (p + r), 0 when
+ *   p + r = 0.  values [n_img][n_hyp][6] = AUC, PA AUC, F@lo, F@hi, PA F@lo, PA F@hi (the four F entries NaN when with_fscore == 0).
+ *   counts (may be NULL) [n_img][n_hyp][10] int32 = #{d1 < lo}, #{d1 < hi}, #{d2 < lo}, #{d2 < hi} raw, the same four aligned (0 when
+ *   with_fscore == 0), sum_p c_p raw, sum_p c_p aligned.  A pair with a non-finite coordinate gives NaN values (counts 0).
+ *   3 <= n_pts <= 1024, 2 <= n_thresh <= 256, n_img * n_hyp <= 2^31 - 1: anything else is an error before any launch.
+ * vpho_hand_bench_table_f64: per [n_img][n_hyp][8] -> one [n_img][8] (hypothesis 0), best [n_img][8] (per-value MAXIMUM over the
+ *   hypotheses), mean [n_img][8] (fp64 sum in ascending hypothesis order / n_hyp); a NaN hypothesis makes best and mean NaN.
+ * Deterministic: fixed reduction orders, integer counts, no atomics. */
+VPHO_API int vpho_hand_bench_multi_f32(const float* pd, const float* gt, const float* root_joint, const unsigned char* is_right, int n_img,
+                              int n_hyp, int n_pts, double f_thresh_lo, double f_thresh_hi, const double* auc_thresh, const double* auc_g,
+                              int n_thresh, int with_fscore, double* values, int* counts, void* stream);
+VPHO_API int vpho_hand_bench_table_f64(const double* per, int n_img, int n_hyp, double* one, double* best, double* mean, void* stream);
+
 /* Prediction records of --mode infer (Trainer.infer, lib/engine/train_diff_hand_obj.py:359-444): ONE launch turns the predict outputs of a
  * batch into fixed-layout per-image records, and ONE hipMemcpyAsync ships them to the host.  Replaces, per batch, the postprocess of
  * the four hand arrays (__postprocess_hand_vert, :598-602: x negated where !is_right, then + root_joint; one sign flip and one fp32 add

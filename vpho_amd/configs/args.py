@@ -24,6 +24,7 @@ class Config:
         self.physics_contact_thresh = 0.005   # contact distance (m): the reference's contact_vertical_distance_thresh
         self.eval_volume = False      # also report the hand-object intersection volume; independent of eval_physics
         self.physics_voxel_pitch = 0.005      # its voxel pitch (m): the 0.5 cm of the ObMan / GraspTTA evaluations
+        self.eval_hand_bench = False  # also report the hand F@5 / F@15 and PCK AUC of the HO3D / FreiHAND leaderboards
         self.mark = ''
         self.random_seed = 0
         self.output_dir = 'output'
@@ -80,6 +81,7 @@ def _parser():
     p.add_argument('--physics_contact_thresh', type=float, default=0.005)
     p.add_argument('--eval_volume', action='store_true')
     p.add_argument('--physics_voxel_pitch', type=float, default=0.005)
+    p.add_argument('--eval_hand_bench', action='store_true')
     p.add_argument('--mark', type=str, default='')
     p.add_argument('--random_seed', type=int, default=0)
     p.add_argument('--output_dir', type=str, default='output')

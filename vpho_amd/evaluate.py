@@ -42,6 +42,14 @@ VOL = 4
 # block in every layout --, in the order of ops_names.VOLUME_MULTI_COLUMNS: IV (m^3) and the solid-cell count of (hand hypothesis s,
 # object hypothesis s) reduced per image to hypothesis 0, best-of-S and mean-of-S.  Widths 98, 106 and 118: no other layout has them.
 VOL_MULTI = 6
+# with eval_hand_bench (cfg.eval_hand_bench; Trainer.eval, not metric_rows: its signature and summarize's width table are frozen) the
+# pipeline callback appends HAND_BENCH more columns AFTER everything metric_rows returns, in the order of ops_names.HAND_BENCH_COLUMNS:
+# the eight leaderboard values of the aggregated hand, then of the regression hand; with hand_bench_multi (both
+# command-line flags, cfg.eval_best AND cfg.eval_hand_bench; an explicit argument of Trainer.eval otherwise) HAND_BENCH_MULTI more after
+# those (ops_names.HAND_BENCH_MULTI_COLUMNS).  summarize never sees them: Trainer.eval cuts them off and tabulates them by
+# hand_bench_table.  In these layouts rows[:, -VOL:] is NOT the volume block.
+HAND_BENCH = 16
+HAND_BENCH_MULTI = 24
 
 
 def row_width(eval_best=False, eval_physics=False, physics_multi=False, volume_multi=False, eval_volume=False):
@@ -225,6 +233,61 @@ def volume_multi_block(out, data, meshes):
     pd_rt = ops.obj_9d_to_rt(out['diff_final_obj_6d'].reshape(bs * S, 9).double().contiguous(), root.repeat_interleave(S, 0).contiguous()).view(bs, S, 3, 4)
     table, _ = meshes.volume_multi(verts, pd_rt, meshes.obj_ids(data['obj_name']), float(cfg.physics_voxel_pitch))
     return table.float()
+
+
+def hand_bench_width(multi=False):
+    """columns that Trainer.eval appends after metric_rows' with eval_hand_bench: 16, or 40 with the multi-hypothesis block"""
+    return HAND_BENCH + (HAND_BENCH_MULTI if multi else 0)
+
+
+def _hand_bench_pair(pd_joint, pd_vert, data, gt_joint, gt_vert):
+    """(bs, S, 8) fp64 in the order of ops_names.HAND_BENCH_NAMES from model-frame candidates (bs, S, 21 | V, 3): one joint call (AUC
+    only) and one vertex call of ops.hand_bench_multi"""
+    from . import ops
+    root = data['root_joint'].float().contiguous()
+    c = lambda t: t.float().contiguous()
+    j = ops.hand_bench_multi(c(pd_joint), c(gt_joint), root, data['is_right'], with_fscore=False)
+    v = ops.hand_bench_multi(c(pd_vert), c(gt_vert), root, data['is_right'])
+    return torch.cat([j[..., :2], v], -1)
+
+
+def hand_bench_block(out, data, gt_joint, gt_vert):
+    """(bs, HAND_BENCH) fp32 in the order of ops_names.HAND_BENCH_COLUMNS: AUC_J, PA_AUC_J, AUC_V, PA_AUC_V, F@5, F@15, PA_F@5, PA_F@15
+     of the aggregated hand, then of the regression hand, each as one hypothesis (S = 1) of the multi-hypothesis
+    kernel: the model-frame outputs go in, the postprocess happens on load.  In hand mode 2D_pt_joint the six vertex values of the
+    aggregated hand are NaN, as MVE is there."""
+    if not gt_joint.is_cuda:
+        raise RuntimeError('hand_bench_block: the hand benchmark metrics run on the GPU only (no CPU path)')
+    agg = _hand_bench_pair(out['agg_hand_joint'][:, None], out['agg_hand_vert'][:, None], data, gt_joint, gt_vert)[:, 0]
+    reg = _hand_bench_pair(out['reg_hand_joint'][:, None], out['reg_hand_vert'][:, None], data, gt_joint, gt_vert)[:, 0]
+    blk = torch.cat([agg, reg], 1).float()
+    from .configs.args import cfg
+    if cfg.aggregation_mode_hand == '2D_pt_joint':
+        blk[:, 2:8] = float('nan')
+    return blk
+
+
+def hand_bench_multi_block(out, data, gt_joint, gt_vert):
+    """(bs, HAND_BENCH_MULTI) fp32 in the order of ops_names.HAND_BENCH_MULTI_COLUMNS: the eight values of every sampled hypothesis
+    (out['diff_final_hand_joint'] / _vert, model frame) reduced per image to hypothesis 0 | best-of-S (each value's maximum on its
+    own) | mean-of-S by ops.hand_bench_table"""
+    from . import ops
+    if not gt_joint.is_cuda:
+        raise RuntimeError('hand_bench_multi_block: the hand benchmark metrics run on the GPU only (no CPU path)')
+    per = _hand_bench_pair(out['diff_final_hand_joint'], out['diff_final_hand_vert'], data, gt_joint, gt_vert).contiguous()
+    return torch.cat(ops.hand_bench_table(per), 1).float()
+
+
+def hand_bench_table(block):
+    """the table 'hand_bench' of Trainer.eval / EVAL_JSON from the (n, 16 | 40) columns hand_bench_block [+ hand_bench_multi_block] made:
+    {'agg': {...}, 'reg': {...}[, 'one_candidate': ..., 'best_of_S': ..., 'mean_of_S': ...]}, each the ops_names.HAND_BENCH_TABLE keys as
+    fp64 means over the images, in [0, 1] (NaN where a column holds one)"""
+    from .ops_names import HAND_BENCH_SOURCES, HAND_BENCH_TABLE, MULTI_TABLES
+    if block.shape[1] not in (HAND_BENCH, HAND_BENCH + HAND_BENCH_MULTI):
+        raise ValueError(f'hand_bench_table: {block.shape[1]} columns, expected {HAND_BENCH} or {HAND_BENCH + HAND_BENCH_MULTI}')
+    mean = block.double().mean(0)
+    names = HAND_BENCH_SOURCES + (MULTI_TABLES if block.shape[1] > HAND_BENCH else ())
+    return {src: {k: float(mean[8 * s + i]) for i, k in enumerate(HAND_BENCH_TABLE)} for s, src in enumerate(names)}
 
 
 def metric_rows(out, data, gt_joint, gt_vert, first_index, assets=None, eval_best=False, eval_physics=False, physics_multi=False, volume_multi=False,

@@ -1066,6 +1066,64 @@ def hand_metrics_multi(pd, gt, root_joint, is_right):
     return me, pa
 
 
+HAND_BENCH_MAX_POINTS = 1024            # csrc/hand_bench.hip: three point sets of a pair in LDS
+_HAND_BENCH_TABLES = {}
+
+
+def hand_bench_tables(device):
+    """the AUC threshold table t = np.linspace(*HAND_BENCH_AUC) (n_t,) fp64 and G (n_t + 1,) fp64 on ``device``, built once per device:
+    G[c] = the trapezoid integral over the table of the step 1[e <= t] of a point with c = #{j : e <= t_j}, divided by t[-1] - t[0];
+    with j0 = n_t - c: ((t[-1] - t[j0]) + (t[j0] - t[j0 - 1]) / 2 if j0 >= 1) / (t[-1] - t[0]), G[0] = 0"""
+    key = str(torch.device(device))
+    if key not in _HAND_BENCH_TABLES:
+        import numpy as np
+        from .ops_names import HAND_BENCH_AUC
+        t = np.linspace(HAND_BENCH_AUC[0], HAND_BENCH_AUC[1], HAND_BENCH_AUC[2])
+        n_t = t.shape[0]
+        g = np.zeros(n_t + 1)
+        for c in range(1, n_t + 1):
+            j0 = n_t - c
+            g[c] = ((t[-1] - t[j0]) + ((t[j0] - t[j0 - 1]) / 2 if j0 >= 1 else 0.0)) / (t[-1] - t[0])
+        _HAND_BENCH_TABLES[key] = (torch.from_numpy(t).to(device), torch.from_numpy(g).to(device))
+    return _HAND_BENCH_TABLES[key]
+
+
+def hand_bench_multi(pd, gt, root_joint, is_right, with_fscore=True, counts=False):
+    """The hand leaderboard values of every sampled hypothesis (FreiHAND / HO3D eval.py).  pd (n,S,P,3) fp32 in the
+    model frame as predict returns it (the postprocess happens on load, as in hand_metrics_multi), gt (n,P,3), root_joint (n,3),
+    is_right (n,) -> values (n,S,6) fp64 = AUC, PA AUC of the PCK curve over ops_names.HAND_BENCH_AUC, then F, F, PA F, PA F at the two
+    ops_names.HAND_BENCH_F_THRESH (NaN without ``with_fscore``: the joint call); with ``counts`` also (n,S,10) int32: the eight
+    nearest-neighbour counts {raw, PA} x {d1, d2} x {lo, hi}, then the sums of the AUC counts raw and aligned.  A pair with a
+    non-finite coordinate is NaN.  S = 1 serves a single hand per image: ``out['agg_hand_vert'][:, None]``."""
+    from .ops_names import HAND_BENCH_F_THRESH
+    n, S, P, _ = pd.shape
+    assert pd.shape == (n, S, P, 3) and gt.shape == (n, P, 3) and root_joint.shape == (n, 3) and is_right.shape == (n,)
+    if P > HAND_BENCH_MAX_POINTS or P < 3:
+        raise VphoError(f'hand_bench_multi: {P} points per hand, the kernel takes 3 .. {HAND_BENCH_MAX_POINTS}')
+    if n * S > 0x7fffffff:
+        raise VphoError(f'hand_bench_multi: {n} x {S} pairs, at most 2^31 - 1 in one call')
+    values = _new((n, S, 6), pd, torch.float64)
+    cnt = _new((n, S, 10), pd, torch.int32) if counts else None
+    if n * S > 0:
+        t, g = hand_bench_tables(pd.device)
+        flag = is_right.to(device=pd.device, dtype=torch.uint8).contiguous()
+        _call('vpho_hand_bench_multi_f32', _f32(pd), _f32(gt), _f32(root_joint), _u8(flag), I(n), I(S), I(P), C.c_double(HAND_BENCH_F_THRESH[0]),
+              C.c_double(HAND_BENCH_F_THRESH[1]), _f64(t), _f64(g), I(t.shape[0]), I(1 if with_fscore else 0), _f64(values),
+              _i32(cnt) if counts else None)
+    return (values, cnt) if counts else values
+
+
+def hand_bench_table(per):
+    """per (n,S,8) fp64 in the order of ops_names.HAND_BENCH_NAMES -> one, best, mean, each (n,8) fp64: hypothesis 0, the per-value
+    MAXIMUM over the S hypotheses, the mean (fp64 sum in ascending s); a NaN hypothesis makes best and mean NaN"""
+    n, S, k = per.shape
+    assert k == 8 and S > 0
+    one, best, mean = (_new((n, 8), per, torch.float64) for _ in range(3))
+    if n > 0:
+        _call('vpho_hand_bench_table_f64', _f64(per), I(n), I(S), _f64(one), _f64(best), _f64(mean))
+    return one, best, mean
+
+
 def obj_9d_to_rt(pose9, root_joint):
     """(n,9) fp64 [rot6d | t], (n,3) fp32 root -> (n,3,4) fp64 [R | t + root]  (transform_fn.py:85-90, train_diff_hand_obj.py:594-597)"""
     n = pose9.shape[0]

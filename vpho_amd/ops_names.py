@@ -34,3 +34,17 @@ VOLUME_TABLE = ('IV_cm3', 'IV_max_cm3', 'intersecting_pct')
 # best-of-S (the minima) and mean-of-S (mean_cells = integer sum / S, mean_IV = pitch^3 * mean_cells); the 'volume' table gains the three
 # MULTI_TABLES entries beside 'pred' and 'gt', each with the VOLUME_TABLE keys
 VOLUME_MULTI_COLUMNS = ('one_IV_m3', 'one_cells', 'best_IV_m3', 'best_cells', 'mean_IV_m3', 'mean_cells')
+# the hand benchmark block (--eval_hand_bench): the HO3D / FreiHAND leaderboard values of a (hand, ground truth) pair, all
+# in [0, 1]: the AUC of the PCK curve over HAND_BENCH_AUC = np.linspace(lo, hi, n) metres for joints and vertices and the vertex F-score at
+# the HAND_BENCH_F_THRESH distances (metres), each raw and after the similarity alignment ('PA')
+HAND_BENCH_NAMES = ('AUC_J', 'PA_AUC_J', 'AUC_V', 'PA_AUC_V', 'F@5', 'F@15', 'PA_F@5', 'PA_F@15')
+HAND_BENCH_F_THRESH = (0.005, 0.015)
+HAND_BENCH_AUC = (0.0, 0.05, 100)
+# evaluate.hand_bench_block: the eight values of the aggregated hand, then of the regression hand (16 columns, after every older block)
+HAND_BENCH_SOURCES = ('agg', 'reg')
+HAND_BENCH_COLUMNS = tuple(f'hand_bench/{s}/{k}' for s in HAND_BENCH_SOURCES for k in HAND_BENCH_NAMES)
+# evaluate.hand_bench_multi_block (eval_best AND eval_hand_bench): every sampled hypothesis, per image reduced to hypothesis 0, best-of-S
+# (the MAXIMUM of each value on its own) and mean-of-S (24 columns, last of all)
+HAND_BENCH_MULTI_COLUMNS = tuple(f'hand_bench/{t}/{k}' for t in MULTI_TABLES for k in HAND_BENCH_NAMES)
+# the keys of every source of the summarize-level / EVAL_JSON table 'hand_bench': means over the images
+HAND_BENCH_TABLE = HAND_BENCH_NAMES

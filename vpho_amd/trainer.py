@@ -214,7 +214,8 @@ class Trainer:
             seen += n
 
     @torch.no_grad()
-    def eval(self, loader=None, eval_best=None, eval_physics=None, physics_multi=None, eval_volume=None, volume_multi=None):
+    def eval(self, loader=None, eval_best=None, eval_physics=None, physics_multi=None, eval_volume=None, volume_multi=None, eval_hand_bench=None,
+             hand_bench_multi=None):
         """``evaluate(testing_dataloader)`` (train_diff_hand_obj.py:202-357).  ``loader``: see ``_eval_batches``; default synthetic.
         ``eval_best`` (default: cfg.eval_best, the reference's is_eval_best): also score every sampled hypothesis and report the
         one_candidate, best_of_S and mean_of_S tables (rows of evaluate.ROW_BEST columns).  ``eval_physics`` (default:
@@ -227,8 +228,13 @@ class Trainer:
         ``volume_multi`` (default: cfg.eval_best and cfg.eval_volume, i.e. both command-line flags; it needs eval_best and eval_volume):
         every sampled hypothesis' intersection volume as well (evaluate.VOL_MULTI more columns immediately before the VOL block; the
         ``volume`` table gains one_candidate, best_of_S and mean_of_S).  As with physics_multi, a caller that passes eval_best /
-        eval_volume itself gets the rows it always got unless it asks for the new block too."""
+        eval_volume itself gets the rows it always got unless it asks for the new block too.  ``eval_hand_bench`` (default:
+        cfg.eval_hand_bench): also report the hand F-scores and PCK AUC of the HO3D / FreiHAND leaderboards for the aggregated and the
+        regression hand, the ``hand_bench`` table (evaluate.HAND_BENCH more columns after everything above); ``hand_bench_multi``
+        (default: cfg.eval_best and cfg.eval_hand_bench; it needs eval_best and eval_hand_bench): every sampled hypothesis as well
+        (evaluate.HAND_BENCH_MULTI more columns, last of all; the table gains one_candidate, best_of_S and mean_of_S)."""
         from .configs.args import cfg
+        eval_hand_bench = bool(cfg.eval_hand_bench if eval_hand_bench is None else eval_hand_bench)
         eval_volume = bool(cfg.eval_volume if eval_volume is None else eval_volume)
         # the keyword travels to metric_rows only when it is set: without it the call is the one it always was
         vol = dict(eval_volume=True) if eval_volume else {}
@@ -238,6 +244,19 @@ class Trainer:
             vol['volume_multi'] = True
         eval_physics = bool(cfg.eval_physics if eval_physics is None else eval_physics)
         physics_multi = bool((cfg.eval_best and cfg.eval_physics) if physics_multi is None else physics_multi) and eval_best and eval_physics
+        hand_bench_multi = bool((cfg.eval_best and cfg.eval_hand_bench) if hand_bench_multi is None else hand_bench_multi) and eval_best and eval_hand_bench
+        bench_cols = E.hand_bench_width(hand_bench_multi) if eval_hand_bench else 0
+
+        def batch_rows(out, batch, gt, first):
+            rows = E.metric_rows(out, batch, gt[0], gt[1], first, self.assets, eval_best, eval_physics, physics_multi, **vol)
+            if not eval_hand_bench:
+                return rows
+            # the hand benchmark blocks come last of all (the 16, then the 24): still one row tensor, one all-gather
+            blocks = [rows, E.hand_bench_block(out, batch, gt[0], gt[1])]
+            if hand_bench_multi:
+                blocks.append(E.hand_bench_multi_block(out, batch, gt[0], gt[1]))
+            return torch.cat(blocks, 1)
+
         if eval_physics:
             # object meshes and their tables (with eval_best also the multi-hypothesis kernel's), once, before the timed loop
             E.physics_meter(self.assets, self.device, multi=physics_multi)
@@ -258,10 +277,9 @@ class Trainer:
                     # synthetic run: batch 0 provides the ground truth (its own regression output), so it is evaluated first
                     out0 = pipe.submit(b).result()
                     gt = (out0['reg_hand_joint'] + b['root_joint'][:, None], out0['reg_hand_vert'] + b['root_joint'][:, None])
-                    rows.append(E.metric_rows(out0, b, gt[0], gt[1], first, self.assets, eval_best, eval_physics, physics_multi, **vol))
+                    rows.append(batch_rows(out0, b, gt, first))
                 else:
-                    futs.append(pipe.submit(b, lambda out, batch, eng, first=first, gt=gt: E.metric_rows(out, batch, gt[0], gt[1], first, self.assets,
-                                                                                                    eval_best, eval_physics, physics_multi, **vol)))
+                    futs.append(pipe.submit(b, lambda out, batch, eng, first=first, gt=gt: batch_rows(out, batch, gt, first)))
                 item = gen.send(gt)
         except StopIteration:
             pass
@@ -269,7 +287,7 @@ class Trainer:
         pipe.close()
         # a rank whose shard is empty still takes part in the collective (with zero rows: the ragged gather carries the counts first);
         # raising here would leave the other ranks blocked in their all-gather.  Only an evaluation without ANY image is an error
-        mine = torch.cat(rows, 0) if rows else torch.zeros((0, E.row_width(eval_best, eval_physics, physics_multi, volume_multi, eval_volume)), device=self.device, dtype=torch.float32)
+        mine = torch.cat(rows, 0) if rows else torch.zeros((0, E.row_width(eval_best, eval_physics, physics_multi, volume_multi, eval_volume) + bench_cols), device=self.device, dtype=torch.float32)
         rows = E.gather_rows(mine)
         if rows.shape[0] == 0:
             raise ValueError('Trainer.eval: the loader yielded no batch on any rank')
@@ -279,9 +297,12 @@ class Trainer:
             what = 'synthetic images' if loader is None else 'images'
             print(f'evaluated {rows.shape[0]} {what} on {self.world} GPU(s) in {dt:.2f} s ({rows.shape[0] / dt:.1f} images/s)')
             print(f'aggregation_mode_hand {cfg.aggregation_mode_hand}  aggregation_mode_obj {cfg.aggregation_mode_obj}')
-            table = E.summarize(rows.cpu())
+            host = rows.cpu()
+            table = E.summarize(host[:, :-bench_cols] if bench_cols else host)
+            if bench_cols:
+                table['hand_bench'] = E.hand_bench_table(host[:, -bench_cols:])
             for name, r in table.items():
-                if name not in ('object', 'physics', 'volume') + E.MULTI_TABLES:
+                if name not in ('object', 'physics', 'volume', 'hand_bench') + E.MULTI_TABLES:
                     print(f'{name:>5s}: n={r["n"]:5d}  MJE reg {r["MJE_reg"]:.2f}  first {r["MJE_first"]:.2f}  agg {r["MJE_agg"]:.2f}  MVE agg {r["MVE_agg"]:.2f}  (mm)')
             print('object (aggregated pose): ' + '  '.join(f'{k} {v:.2f}' for k, v in table['object'].items()))
             for name in E.MULTI_TABLES:
@@ -294,6 +315,9 @@ class Trainer:
             if 'volume' in table:
                 for src, r in table['volume'].items():
                     print(f'volume {src} (pitch {cfg.physics_voxel_pitch * 1000.0:g} mm): ' + '  '.join(f'{k} {v:.3f}' for k, v in r.items()))
+            if 'hand_bench' in table:
+                for src, r in table['hand_bench'].items():
+                    print(f'hand_bench {src}: ' + '  '.join(f'{k} {v:.4f}' for k, v in r.items()))
             import json
             print('EVAL_JSON ' + json.dumps({'images': int(rows.shape[0]), 'world': self.world, 'aggregation_mode_hand': cfg.aggregation_mode_hand,
                                              'aggregation_mode_obj': cfg.aggregation_mode_obj, 'table': table}))
