@@ -180,11 +180,11 @@ def test_trainer_eval_with_both_flags(monkeypatch, capsys):
     seen, right = [], []
     orig_rows = E.metric_rows
 
-    def spy(out, data, gt_joint, gt_vert, first, assets=None, eval_best=False, eval_physics=False, physics_multi=False):
-        rows = orig_rows(out, data, gt_joint, gt_vert, first, assets, eval_best, eval_physics, physics_multi)
-        if physics_multi:
+    def spy(out, data, gt_joint, gt_vert, first, assets=None, *a, **k):
+        rows = orig_rows(out, data, gt_joint, gt_vert, first, assets, *a, **k)
+        if k['layout'].has('physics_multi'):
             # the same outputs through the row builder with the new block switched off: the rows of this tree before the feature
-            without = orig_rows(out, data, gt_joint, gt_vert, first, assets, eval_best, eval_physics, physics_multi=False)
+            without = orig_rows(out, data, gt_joint, gt_vert, first, assets, True, True, physics_multi=False)
             meter = E.physics_meter(assets, rows.device)
             S = out['diff_final_hand_vert'].shape[1]
             # hypothesis 0 in the camera frame, written out (postprocess' arithmetic, not the helper the block itself uses):

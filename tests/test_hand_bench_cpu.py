@@ -125,9 +125,10 @@ def test_signatures_the_new_keywords_and_the_frozen_ones():
     assert list(p)[-3:] == ['volume_multi', 'eval_hand_bench', 'hand_bench_multi']
     assert p['eval_hand_bench'].default is None and p['hand_bench_multi'].default is None
     assert list(inspect.signature(E.row_width).parameters) == ['eval_best', 'eval_physics', 'physics_multi', 'volume_multi', 'eval_volume']
+    # the positional order every older caller relies on stays; the hand benchmark flags and the layout come after it
     assert list(inspect.signature(E.metric_rows).parameters) == ['out', 'data', 'gt_joint', 'gt_vert', 'first_index', 'assets', 'eval_best', 'eval_physics',
-                                                                  'physics_multi', 'volume_multi', 'eval_volume']
-    assert list(inspect.signature(E.summarize).parameters) == ['rows']
+                                                                  'physics_multi', 'volume_multi', 'eval_volume', 'eval_hand_bench', 'hand_bench_multi', 'layout']
+    assert list(inspect.signature(E.summarize).parameters) == ['rows', 'layout'] and inspect.signature(E.summarize).parameters['layout'].default is None
     for fn in (E.hand_bench_block, E.hand_bench_multi_block):
         assert list(inspect.signature(fn).parameters) == ['out', 'data', 'gt_joint', 'gt_vert']
 

@@ -184,7 +184,7 @@ def test_row_width_and_column_names():
     assert len(set(widths)) == len(widths)                                     # summarize tells the layouts apart by their width
     import inspect
     assert list(inspect.signature(E.row_width).parameters)[-1] == 'eval_volume'
-    assert list(inspect.signature(E.metric_rows).parameters)[-1] == 'eval_volume'
+    assert list(inspect.signature(E.metric_rows).parameters)[10] == 'eval_volume'          # last of the positional flags; later keywords follow it
     assert inspect.signature(E.metric_rows).parameters['eval_volume'].default is False
 
 

@@ -9,52 +9,17 @@ The forward pass itself needs no collective: the image batch is the only sharded
 import torch
 import torch.distributed as dist
 
-from .ops_names import MULTI_TABLES  # noqa: F401  (table names of summarize with eval_best)
+from .eval_layout import BLOCKS, RowLayout
+from .ops_names import HAND_BENCH_SOURCES, HAND_BENCH_TABLE, HAND_METRIC_NAMES, MULTI_TABLES, OBJ_METRIC_NAMES, PHYSICS_SOURCES
 
-# row layout: [global image index, MJE(regression), MJE(first hypothesis), MJE(aggregated), MVE(aggregated),
-#              |agg - regression| mean joint distance (mm), object translation norm (m), is_right,
-#              PA-MJE(regression), PA-MJE(aggregated), PA-MVE(aggregated), 0,
-#              then the 16 object metrics of the aggregated pose in the order of ops.OBJ_METRIC_NAMES (TesterObject,
-#              test.py:240-503: MCE, OCE, MCE2, ADD, ADD-S, ADD<0.1d, ADD-S<0.1d, REP, REP<5px, CD, F-score x6)]
-ROW = 28
-OBJ_COL = 12
-# with eval_best (cfg.eval_best, the reference's is_eval_best) every row carries MULTI more columns from ROW on, in the order of
-# ops_names.MULTI_COLUMNS: hand one_candidate / best_of_S / mean_of_S (MJE, PA-MJE, MVE, PA-MVE in mm, 4 each), then object
-# one_candidate / best_of_S / mean_of_S (the 16 OBJ_METRIC_NAMES each).  Columns 0-27 are the same with and without the flag.
-MULTI = 60
+# the row layout -- which blocks there are, their order and widths -- is eval_layout.BLOCKS; these are its widths, in its order
+ROW, MULTI, PHYS, PHYS_MULTI, VOL_MULTI, VOL, HAND_BENCH, HAND_BENCH_MULTI = (width for _, _, width, _ in BLOCKS)
 ROW_BEST = ROW + MULTI
-# with eval_physics (cfg.eval_physics) every row carries PHYS more columns, last (after the eval_best block if there is one), in the
-# order of ops_names.PHYSICS_COLUMNS: PD (m), n_inside, min sd (m), contact of (aggregated hand, aggregated object), then of (ground-truth
-# hand, ground-truth object).  The columns before them are the same with and without the flag.
-PHYS = 8
-# with physics_multi (both command-line flags, cfg.eval_best AND cfg.eval_physics; an explicit argument of Trainer.eval / metric_rows
-# otherwise, so that callers who pass the two older flags themselves get the rows they always got) every row carries PHYS_MULTI more
-# columns, last (after the PHYS block), in the order of
-# ops_names.PHYSICS_MULTI_COLUMNS: PD (m), n_inside, min sd (m), contact of (hand hypothesis s, object hypothesis s) reduced per image to
-# hypothesis 0, best-of-S and mean-of-S.  The 96 columns before them are the same with and without the block.
-PHYS_MULTI = 12
-# with eval_volume (cfg.eval_volume; independent of the flags above) every row carries VOL more columns, last of all, in the order of
-# ops_names.VOLUME_COLUMNS: IV (m^3) and the solid-cell count of (aggregated hand, aggregated object), then of the ground-truth pair.
-# Every column before them is the same with and without the flag.
-VOL = 4
-# with volume_multi (both command-line flags, cfg.eval_best AND cfg.eval_volume; an explicit argument of Trainer.eval / metric_rows
-# otherwise, as physics_multi) every row carries VOL_MULTI more columns IMMEDIATELY BEFORE the VOL block -- rows[:, -VOL:] is the volume
-# block in every layout --, in the order of ops_names.VOLUME_MULTI_COLUMNS: IV (m^3) and the solid-cell count of (hand hypothesis s,
-# object hypothesis s) reduced per image to hypothesis 0, best-of-S and mean-of-S.  Widths 98, 106 and 118: no other layout has them.
-VOL_MULTI = 6
-# with eval_hand_bench (cfg.eval_hand_bench; Trainer.eval, not metric_rows: its signature and summarize's width table are frozen) the
-# pipeline callback appends HAND_BENCH more columns AFTER everything metric_rows returns, in the order of ops_names.HAND_BENCH_COLUMNS:
-# the eight leaderboard values of the aggregated hand, then of the regression hand; with hand_bench_multi (both
-# command-line flags, cfg.eval_best AND cfg.eval_hand_bench; an explicit argument of Trainer.eval otherwise) HAND_BENCH_MULTI more after
-# those (ops_names.HAND_BENCH_MULTI_COLUMNS).  summarize never sees them: Trainer.eval cuts them off and tabulates them by
-# hand_bench_table.  In these layouts rows[:, -VOL:] is NOT the volume block.
-HAND_BENCH = 16
-HAND_BENCH_MULTI = 24
+OBJ_COL = 12                 # first of the 16 object metrics of the aggregated pose within the base block
 
 
 def row_width(eval_best=False, eval_physics=False, physics_multi=False, volume_multi=False, eval_volume=False):
-    return (ROW_BEST if eval_best else ROW) + (PHYS if eval_physics else 0) + (PHYS_MULTI if eval_best and eval_physics and physics_multi else 0) + \
-        (VOL_MULTI if eval_best and eval_volume and volume_multi else 0) + (VOL if eval_volume else 0)
+    return RowLayout.resolve(eval_best, eval_physics, physics_multi, eval_volume, volume_multi).width
 
 
 def mje_mm(pd, gt):
@@ -79,17 +44,34 @@ def postprocess(out, root_joint, is_right):
 _OBJ_METRICS = {}
 
 
+def _object_metrics(assets, device):
+    """the ops.ObjectMetrics of an asset set on a device, built once"""
+    key = (id(assets), str(device))
+    if key not in _OBJ_METRICS:
+        from . import ops
+        _OBJ_METRICS[key] = ops.ObjectMetrics(assets['ycb'], device)
+    return _OBJ_METRICS[key]
+
+
+def _agg_obj_rt(out, data):
+    """(bs, 3, 4) fp64: the aggregated object pose in the camera frame, obj_9D_to_mat + root joint"""
+    from . import ops
+    return ops.obj_9d_to_rt(out['agg_obj_6d'].double().contiguous(), data['root_joint'].float().contiguous())
+
+
+def _hypothesis_obj_rt(out, root):
+    """(bs, S, 3, 4) fp64: every object candidate in the camera frame, obj_9D_to_mat + its image's root joint (``root``: fp32, contiguous)"""
+    from . import ops
+    x = out['diff_final_obj_6d']
+    bs, S = x.shape[:2]
+    return ops.obj_9d_to_rt(x.reshape(bs * S, 9).double().contiguous(), root.repeat_interleave(S, 0).contiguous()).view(bs, S, 3, 4)
+
+
 def object_metric_block(out, data, assets):
     """(bs,16) fp64: TesterObject on the aggregated object pose ('mean_candidate_pose', train_diff_hand_obj.py:249-258,
     498-501) -- obj_9D_to_mat + root joint, then the device metric kernels.  Needs data['gt_obj_rt'], data['cam_intr']."""
-    from . import ops
-    dev = out['agg_obj_6d'].device
-    key = (id(assets), str(dev))
-    if key not in _OBJ_METRICS:
-        _OBJ_METRICS[key] = ops.ObjectMetrics(assets['ycb'], dev)
-    M = _OBJ_METRICS[key]
-    pd_rt = ops.obj_9d_to_rt(out['agg_obj_6d'].double().contiguous(), data['root_joint'].float().contiguous())
-    return M(pd_rt, data['gt_obj_rt'].double().contiguous(), data['cam_intr'].double().contiguous(), M.obj_ids(data['obj_name']))
+    M = _object_metrics(assets, out['agg_obj_6d'].device)
+    return M(_agg_obj_rt(out, data), data['gt_obj_rt'].double().contiguous(), data['cam_intr'].double().contiguous(), M.obj_ids(data['obj_name']))
 
 
 def multi_hypothesis_block(out, data, gt_joint, gt_vert, assets=None):
@@ -100,8 +82,7 @@ def multi_hypothesis_block(out, data, gt_joint, gt_vert, assets=None):
     from . import ops
     if not gt_joint.is_cuda:
         raise RuntimeError('multi_hypothesis_block: the multi-hypothesis metrics run on the GPU only (no CPU path)')
-    bs = gt_joint.shape[0]
-    blk = torch.zeros((bs, MULTI), device=gt_joint.device, dtype=torch.float32)
+    blk = torch.zeros((gt_joint.shape[0], MULTI), device=gt_joint.device, dtype=torch.float32)
     root = data['root_joint'].float().contiguous()
     c = lambda t: t.float().contiguous()
     mje, pa_mje = ops.hand_metrics_multi(c(out['diff_final_hand_joint']), c(gt_joint), root, data['is_right'])
@@ -111,14 +92,8 @@ def multi_hypothesis_block(out, data, gt_joint, gt_vert, assets=None):
     blk[:, 4:8] = hand.amin(1)
     blk[:, 8:12] = hand.mean(1)
     if assets is not None and 'gt_obj_rt' in data:
-        key = (id(assets), str(gt_joint.device))
-        if key not in _OBJ_METRICS:
-            _OBJ_METRICS[key] = ops.ObjectMetrics(assets['ycb'], gt_joint.device)
-        M = _OBJ_METRICS[key]
-        x = out['diff_final_obj_6d']
-        S = x.shape[1]
-        pd_rt = ops.obj_9d_to_rt(x.reshape(bs * S, 9).double().contiguous(), root.repeat_interleave(S, 0).contiguous()).view(bs, S, 3, 4)
-        per, best, mean = M.multi(pd_rt, data['gt_obj_rt'].double().contiguous(), data['cam_intr'].double().contiguous(),
+        M = _object_metrics(assets, gt_joint.device)
+        per, best, mean = M.multi(_hypothesis_obj_rt(out, root), data['gt_obj_rt'].double().contiguous(), data['cam_intr'].double().contiguous(),
                                   M.obj_ids(data['obj_name']))
         blk[:, 12:28] = per[:, 0].float()
         blk[:, 28:44] = best.float()
@@ -134,39 +109,34 @@ def physics_meter(assets, device, multi=False, volume=False, volume_multi=False)
     tables for the multi-hypothesis kernel only with ``multi`` (eval_best and eval_physics together), once as well; with ``volume``
     (eval_volume) the closed hand mesh (physics_eval.hand_faces) and the objects' solids at cfg.physics_voxel_pitch, once per pitch;
     with ``volume_multi`` (eval_best and eval_volume together) also the solids' lattice columns, once per pitch"""
+    from .configs.args import cfg
     key = (id(assets), str(device))
     if key not in _PHYSICS:
         from . import ops
-        from .configs.args import cfg
         from .physics_eval import object_meshes
         _PHYSICS[key] = ops.HandObjectPenetration(object_meshes(assets, cfg.asset_root), device, accel=False)
+    meter = _PHYSICS[key]
     if multi:
-        _PHYSICS[key].build_accel()
+        meter.build_accel()
     if volume or volume_multi:
-        from .configs.args import cfg
-        if _PHYSICS[key].hand_faces is None:
+        if meter.hand_faces is None:
             from .physics_eval import hand_faces
-            _PHYSICS[key].set_hand_faces(hand_faces(assets))
-        _PHYSICS[key].build_solids(float(cfg.physics_voxel_pitch))
-        if volume_multi:
-            _PHYSICS[key].build_solid_columns(float(cfg.physics_voxel_pitch))
-    return _PHYSICS[key]
+            meter.set_hand_faces(hand_faces(assets))
+        (meter.build_solid_columns if volume_multi else meter.build_solids)(float(cfg.physics_voxel_pitch))
+    return meter
 
 
 def physics_block(pp, out, data, gt_vert, meshes):
     """(bs, PHYS) fp32: hand-object penetration and contact of the aggregated hand vertices (pp['agg_hand_vert'],
     postprocessed: camera frame) with the aggregated object pose (obj_9D_to_mat + root, as object_metric_block), then of the ground-truth
     vertices gt_vert with data['gt_obj_rt'] (NaN without it).  ``meshes``: an ops.HandObjectPenetration (physics_meter)."""
-    from . import ops
     from .configs.args import cfg
     if not gt_vert.is_cuda:
         raise RuntimeError('physics_block: the penetration metrics run on the GPU only (no CPU path)')
-    bs = gt_vert.shape[0]
-    blk = torch.full((bs, PHYS), float('nan'), device=gt_vert.device, dtype=torch.float32)
+    blk = torch.full((gt_vert.shape[0], PHYS), float('nan'), device=gt_vert.device, dtype=torch.float32)
     ids = meshes.obj_ids(data['obj_name'])
     th = float(cfg.physics_contact_thresh)
-    pd_rt = ops.obj_9d_to_rt(out['agg_obj_6d'].double().contiguous(), data['root_joint'].float().contiguous())
-    blk[:, 0:4] = meshes(pp['agg_hand_vert'].float().contiguous(), pd_rt, ids, th).float()
+    blk[:, 0:4] = meshes(pp['agg_hand_vert'].float().contiguous(), _agg_obj_rt(out, data), ids, th).float()
     if 'gt_obj_rt' in data:
         blk[:, 4:8] = meshes(gt_vert.float().contiguous(), data['gt_obj_rt'].double().contiguous(), ids, th).float()
     return blk
@@ -176,16 +146,13 @@ def volume_block(pp, out, data, gt_vert, meshes):
     """(bs, VOL) fp32: the hand-object intersection volume of the pairs of physics_block -- the aggregated hand
     vertices (pp['agg_hand_vert'], camera frame) with the aggregated object pose, then the ground-truth vertices with data['gt_obj_rt']
     (NaN without it) -- as IV (m^3) | solid-cell count each.  ``meshes``: physics_meter(..., volume=True)."""
-    from . import ops
     from .configs.args import cfg
     if not gt_vert.is_cuda:
         raise RuntimeError('volume_block: the intersection volume runs on the GPU only (no CPU path)')
-    bs = gt_vert.shape[0]
-    blk = torch.full((bs, VOL), float('nan'), device=gt_vert.device, dtype=torch.float32)
+    blk = torch.full((gt_vert.shape[0], VOL), float('nan'), device=gt_vert.device, dtype=torch.float32)
     ids = meshes.obj_ids(data['obj_name'])
     h = float(cfg.physics_voxel_pitch)
-    pd_rt = ops.obj_9d_to_rt(out['agg_obj_6d'].double().contiguous(), data['root_joint'].float().contiguous())
-    blk[:, 0:2] = meshes.volume(pp['agg_hand_vert'].float().contiguous(), pd_rt, ids, h).flip(1).float()
+    blk[:, 0:2] = meshes.volume(pp['agg_hand_vert'].float().contiguous(), _agg_obj_rt(out, data), ids, h).flip(1).float()
     if 'gt_obj_rt' in data:
         blk[:, 2:4] = meshes.volume(gt_vert.float().contiguous(), data['gt_obj_rt'].double().contiguous(), ids, h).flip(1).float()
     return blk
@@ -199,44 +166,38 @@ def hypotheses_to_camera(x, root_joint, is_right):
     return v + root_joint[:, None, None]
 
 
-def physics_multi_block(out, data, meshes):
-    """(bs, PHYS_MULTI) fp32: penetration and contact of every sampled hypothesis -- hand candidate s
-    (out['diff_final_hand_vert'][:, s], un-flipped + root as the multi-hypothesis hand metrics) against object candidate s
-    (obj_9D_to_mat + root of out['diff_final_obj_6d'][:, s]) -- reduced per image to hypothesis 0 | best-of-S | mean-of-S by ONE
-    HandObjectPenetration.multi launch pair.  ``meshes``: physics_meter(..., multi=True)."""
-    from . import ops
-    from .configs.args import cfg
-    hv = out['diff_final_hand_vert']
-    if not hv.is_cuda:
-        raise RuntimeError('physics_multi_block: the penetration metrics run on the GPU only (no CPU path)')
-    bs, S = hv.shape[:2]
+def _hypothesis_pairs(out, data):
+    """(verts (bs, S, V, 3) fp32, pd_rt (bs, S, 3, 4) fp64), both in the camera frame: hand candidate s (out['diff_final_hand_vert'][:, s],
+    un-flipped + root as the multi-hypothesis hand metrics) and object candidate s (obj_9D_to_mat + root of out['diff_final_obj_6d'][:, s])"""
     root = data['root_joint'].float().contiguous()
-    verts = hypotheses_to_camera(hv.float(), root, data['is_right']).contiguous()
-    pd_rt = ops.obj_9d_to_rt(out['diff_final_obj_6d'].reshape(bs * S, 9).double().contiguous(), root.repeat_interleave(S, 0).contiguous()).view(bs, S, 3, 4)
+    return hypotheses_to_camera(out['diff_final_hand_vert'].float(), root, data['is_right']).contiguous(), _hypothesis_obj_rt(out, root)
+
+
+def physics_multi_block(out, data, meshes):
+    """(bs, PHYS_MULTI) fp32: penetration and contact of every sampled hypothesis -- the pairs of _hypothesis_pairs --
+    reduced per image to hypothesis 0 | best-of-S | mean-of-S by ONE HandObjectPenetration.multi launch pair.
+    ``meshes``: physics_meter(..., multi=True)."""
+    from .configs.args import cfg
+    if not out['diff_final_hand_vert'].is_cuda:
+        raise RuntimeError('physics_multi_block: the penetration metrics run on the GPU only (no CPU path)')
+    verts, pd_rt = _hypothesis_pairs(out, data)
     table, _ = meshes.multi(verts, pd_rt, meshes.obj_ids(data['obj_name']), contact_thresh=float(cfg.physics_contact_thresh))
     return table.float()
 
 
 def volume_multi_block(out, data, meshes):
-    """(bs, VOL_MULTI) fp32: the intersection volume of every sampled hypothesis, the pairing of
-    physics_multi_block -- hand candidate s (out['diff_final_hand_vert'][:, s], un-flipped + root) against object candidate s
-    (obj_9D_to_mat + root of out['diff_final_obj_6d'][:, s]) -- reduced per image to hypothesis 0 | best-of-S | mean-of-S by ONE
-    HandObjectPenetration.volume_multi launch pair.  ``meshes``: physics_meter(..., volume_multi=True)."""
-    from . import ops
+    """(bs, VOL_MULTI) fp32: the intersection volume of every sampled hypothesis -- the pairs of _hypothesis_pairs --
+    reduced per image to hypothesis 0 | best-of-S | mean-of-S by ONE HandObjectPenetration.volume_multi launch pair.
+    ``meshes``: physics_meter(..., volume_multi=True)."""
     from .configs.args import cfg
-    hv = out['diff_final_hand_vert']
-    if not hv.is_cuda:
+    if not out['diff_final_hand_vert'].is_cuda:
         raise RuntimeError('volume_multi_block: the intersection volume runs on the GPU only (no CPU path)')
-    bs, S = hv.shape[:2]
-    root = data['root_joint'].float().contiguous()
-    verts = hypotheses_to_camera(hv.float(), root, data['is_right']).contiguous()
-    pd_rt = ops.obj_9d_to_rt(out['diff_final_obj_6d'].reshape(bs * S, 9).double().contiguous(), root.repeat_interleave(S, 0).contiguous()).view(bs, S, 3, 4)
+    verts, pd_rt = _hypothesis_pairs(out, data)
     table, _ = meshes.volume_multi(verts, pd_rt, meshes.obj_ids(data['obj_name']), float(cfg.physics_voxel_pitch))
     return table.float()
 
 
 def hand_bench_width(multi=False):
-    """columns that Trainer.eval appends after metric_rows' with eval_hand_bench: 16, or 40 with the multi-hypothesis block"""
     return HAND_BENCH + (HAND_BENCH_MULTI if multi else 0)
 
 
@@ -282,7 +243,6 @@ def hand_bench_table(block):
     """the table 'hand_bench' of Trainer.eval / EVAL_JSON from the (n, 16 | 40) columns hand_bench_block [+ hand_bench_multi_block] made:
     {'agg': {...}, 'reg': {...}[, 'one_candidate': ..., 'best_of_S': ..., 'mean_of_S': ...]}, each the ops_names.HAND_BENCH_TABLE keys as
     fp64 means over the images, in [0, 1] (NaN where a column holds one)"""
-    from .ops_names import HAND_BENCH_SOURCES, HAND_BENCH_TABLE, MULTI_TABLES
     if block.shape[1] not in (HAND_BENCH, HAND_BENCH + HAND_BENCH_MULTI):
         raise ValueError(f'hand_bench_table: {block.shape[1]} columns, expected {HAND_BENCH} or {HAND_BENCH + HAND_BENCH_MULTI}')
     mean = block.double().mean(0)
@@ -291,15 +251,19 @@ def hand_bench_table(block):
 
 
 def metric_rows(out, data, gt_joint, gt_vert, first_index, assets=None, eval_best=False, eval_physics=False, physics_multi=False, volume_multi=False,
-                eval_volume=False):
-    """(bs, ROW) fp32 on the model's device; (bs, ROW_BEST) with eval_best (multi_hypothesis_block appended); PHYS more columns with
-    eval_physics (physics_block), and with both and ``physics_multi`` PHYS_MULTI more (physics_multi_block; without it that block
-    and its launch are left out: the rows of the two flags as they always were); VOL more with ``eval_volume`` (volume_block), last of
-    all, whatever the other flags are; with eval_best, eval_volume and ``volume_multi`` VOL_MULTI more immediately before them
-    (volume_multi_block; without it that block and its launches are left out)."""
+                eval_volume=False, eval_hand_bench=False, hand_bench_multi=False, layout=None):
+    """(bs, layout.width) fp32 on the model's device: the blocks of ``layout`` (an eval_layout.RowLayout; default: the one that
+    RowLayout.resolve makes of the seven flags, so a *_multi block needs eval_best and the flag of its single-pose block), each filled
+    by its block function; a block that the layout does not have costs no launch.  With ``layout`` the flags are not looked at."""
+    if layout is None:
+        layout = RowLayout.resolve(eval_best, eval_physics, physics_multi, eval_volume, volume_multi, eval_hand_bench, hand_bench_multi)
+    if assets is None and layout.has('physics'):
+        raise ValueError('metric_rows: eval_physics needs the asset tables (object meshes)')
+    if assets is None and layout.has('volume'):
+        raise ValueError('metric_rows: eval_volume needs the asset tables (object meshes, hand faces)')
     pp = postprocess(out, data['root_joint'], data['is_right'])
-    bs = gt_joint.shape[0]
-    rows = torch.empty((bs, row_width(eval_best, eval_physics, physics_multi, volume_multi, eval_volume)), device=gt_joint.device, dtype=torch.float32)
+    bs, dev = gt_joint.shape[0], gt_joint.device
+    rows = torch.empty((bs, layout.width), device=dev, dtype=torch.float32)
     if torch.is_tensor(first_index):                 # per-image ids (a loader batch that is not a run of the data set)
         rows[:, 0] = first_index.to(device=rows.device, dtype=torch.float32).reshape(bs)
     else:
@@ -320,31 +284,25 @@ def metric_rows(out, data, gt_joint, gt_vert, first_index, assets=None, eval_bes
         rows[:, 10] = ops.hand_metrics(c(pp['agg_hand_vert']), c(gt_vert))[1] * 1000.0
         if assets is not None and 'gt_obj_rt' in data:
             rows[:, OBJ_COL:OBJ_COL + 16] = object_metric_block(out, data, assets).float()
-    if eval_best:
-        rows[:, ROW:ROW_BEST] = multi_hypothesis_block(out, data, gt_joint, gt_vert, assets)
-    if eval_physics:
-        if assets is None:
-            raise ValueError('metric_rows: eval_physics needs the asset tables (object meshes)')
-        p0 = ROW_BEST if eval_best else ROW
-        rows[:, p0:p0 + PHYS] = physics_block(pp, out, data, gt_vert, physics_meter(assets, gt_joint.device))
-        if eval_best and physics_multi:
-            rows[:, p0 + PHYS:p0 + PHYS + PHYS_MULTI] = physics_multi_block(out, data, physics_meter(assets, gt_joint.device, multi=True))
-    if eval_volume:
-        if assets is None:
-            raise ValueError('metric_rows: eval_volume needs the asset tables (object meshes, hand faces)')
-        v0 = rows.shape[1] - VOL
-        rows[:, v0:] = volume_block(pp, out, data, gt_vert, physics_meter(assets, gt_joint.device, volume=True))
-        if eval_best and volume_multi:
-            rows[:, v0 - VOL_MULTI:v0] = volume_multi_block(out, data, physics_meter(assets, gt_joint.device, volume_multi=True))
+    # in the order the blocks always ran; each lambda finds its block function in this module when it is called (tests put spies there)
+    for name, block in (('multi', lambda: multi_hypothesis_block(out, data, gt_joint, gt_vert, assets)),
+                        ('physics', lambda: physics_block(pp, out, data, gt_vert, physics_meter(assets, dev))),
+                        ('physics_multi', lambda: physics_multi_block(out, data, physics_meter(assets, dev, multi=True))),
+                        ('volume', lambda: volume_block(pp, out, data, gt_vert, physics_meter(assets, dev, volume=True))),
+                        ('volume_multi', lambda: volume_multi_block(out, data, physics_meter(assets, dev, volume_multi=True))),
+                        ('hand_bench', lambda: hand_bench_block(out, data, gt_joint, gt_vert)),
+                        ('hand_bench_multi', lambda: hand_bench_multi_block(out, data, gt_joint, gt_vert))):
+        if layout.has(name):
+            rows[:, layout.slice(name)] = block()
     from .configs.args import cfg
     if cfg.aggregation_mode_hand == '2D_pt_joint':
         # that mode fuses joints only; its vertices are the reference's all-zero mesh (aggregation.py:364-366): no vertex metric of it
         rows[:, 4] = float('nan')
         rows[:, 10] = float('nan')
-        if eval_physics:
-            rows[:, p0:p0 + 4] = float('nan')
-        if eval_volume:
-            rows[:, v0:v0 + 2] = float('nan')
+        if layout.has('physics'):
+            rows[:, layout.slice('physics')][:, 0:4] = float('nan')
+        if layout.has('volume'):
+            rows[:, layout.slice('volume')][:, 0:2] = float('nan')
     return rows
 
 
@@ -453,8 +411,14 @@ def shard_range(n_items, rank, world):
     return lo, min(lo + per, n_items)
 
 
-def summarize(rows):
-    """Table like train_diff_hand_obj.py:336-357 for right / left / both hands."""
+def summarize(rows, layout=None):
+    """Table like train_diff_hand_obj.py:336-357 for right / left / both hands, then one table per block of ``layout`` (default:
+    RowLayout.from_width, for rows without hand-benchmark blocks; a width it does not know is a ValueError)."""
+    if layout is None:
+        layout = RowLayout.from_width(rows.shape[1])
+    elif rows.shape[1] != layout.width:
+        raise ValueError(f'summarize: rows of {rows.shape[1]} columns with a layout of {layout.width}')
+    block = lambda name: rows[:, layout.slice(name)]
     res = {}
     for name, mask in (('right', rows[:, 7] > 0.5), ('left', rows[:, 7] < 0.5), ('both', torch.ones_like(rows[:, 7], dtype=torch.bool))):
         sel = rows[mask]
@@ -464,42 +428,31 @@ def summarize(rows):
                          MJE_agg=float(sel[:, 3].mean()), MVE_agg=float(sel[:, 4].mean()), PA_MJE_reg=float(sel[:, 8].mean()),
                          PA_MJE_agg=float(sel[:, 9].mean()), PA_MVE_agg=float(sel[:, 10].mean()))
     # object table (test.py:521-584 'average_instance' column: distances in mm, hit rates / F-scores in percent, REP in pixels)
-    from .ops_names import OBJ_METRIC_NAMES
-    obj = rows[:, OBJ_COL:OBJ_COL + 16].double().mean(0)
-    res['object'] = _object_table(obj)
-    # the widths without the volume block are 28, 88, 36, 96 and 108; with it each is 4 wider, and the three with the eval_best block
-    # another 6 wider with the volume_multi block (98, 106, 118): no two layouts share a width
-    if rows.shape[1] in tuple(w + VOL_MULTI + VOL for w in (ROW_BEST, ROW_BEST + PHYS, ROW_BEST + PHYS + PHYS_MULTI)):
-        from .ops_names import MULTI_TABLES
-        res['volume'] = _volume_table(rows[:, -VOL:])
-        # every hypothesis' volume reduced per image (volume_multi_block): for mean_of_S an image counts as intersecting when its mean
-        # cell count is > 0
-        res['volume'].update(_volume_table(rows[:, -VOL - VOL_MULTI:-VOL], MULTI_TABLES))
-        rows = rows[:, :-VOL - VOL_MULTI]
-    elif rows.shape[1] in tuple(w + VOL for w in (ROW, ROW_BEST, ROW + PHYS, ROW_BEST + PHYS, ROW_BEST + PHYS + PHYS_MULTI)):
-        res['volume'] = _volume_table(rows[:, -VOL:])
-        rows = rows[:, :-VOL]
-    p0 = {ROW + PHYS: ROW, ROW_BEST + PHYS: ROW_BEST, ROW_BEST + PHYS + PHYS_MULTI: ROW_BEST}.get(rows.shape[1])
-    if p0 is not None:
-        from .ops_names import MULTI_TABLES, PHYSICS_SOURCES
-        res['physics'] = _physics_table(rows[:, p0:p0 + PHYS], PHYSICS_SOURCES)
-        if rows.shape[1] > p0 + PHYS:
+    res['object'] = _object_table(rows[:, OBJ_COL:OBJ_COL + 16].double().mean(0))
+    if layout.has('volume'):
+        res['volume'] = _volume_table(block('volume'))
+        if layout.has('volume_multi'):
+            # every hypothesis' volume reduced per image: for mean_of_S an image counts as intersecting when its mean cell count is > 0
+            res['volume'].update(_volume_table(block('volume_multi'), MULTI_TABLES))
+    if layout.has('physics'):
+        res['physics'] = _physics_table(block('physics'), PHYSICS_SOURCES)
+        if layout.has('physics_multi'):
             # every hypothesis' penetration reduced per image (physics_multi_block): for mean_of_S an image counts as penetrating when
             # its mean inside-vertex count is > 0, and its contact is the fraction of its hypotheses in contact
-            res['physics'].update(_physics_table(rows[:, p0 + PHYS:], MULTI_TABLES))
-    if rows.shape[1] >= ROW_BEST:
+            res['physics'].update(_physics_table(block('physics_multi'), MULTI_TABLES))
+    if layout.has('multi'):
         # multi-hypothesis tables (train_diff_hand_obj.py:466-469,494-496 one_candidate; TesterObject.postprocess best_candidate_pose),
         # over all images: hand in mm, object in the units of the object table
-        from .ops_names import HAND_METRIC_NAMES, MULTI_TABLES
-        blk = rows[:, ROW:ROW_BEST].double().mean(0)
+        blk = block('multi').double().mean(0)
         for t, name in enumerate(MULTI_TABLES):
             res[name] = dict(hand={k: float(blk[4 * t + i]) for i, k in enumerate(HAND_METRIC_NAMES)},
                              object=_object_table(blk[12 + 16 * t:28 + 16 * t]))
+    if layout.has('hand_bench'):
+        res['hand_bench'] = hand_bench_table(torch.cat([block(n) for n in ('hand_bench', 'hand_bench_multi') if layout.has(n)], 1))
     return res
 
 
 def _object_table(obj):
-    from .ops_names import OBJ_METRIC_NAMES
     return {k: float(obj[i] * (1000.0 if k in ('MCE', 'OCE', 'MCE2', 'ADD', 'ADDS', 'CD') else (1.0 if k == 'REP' else 100.0)))
             for i, k in enumerate(OBJ_METRIC_NAMES)}
 
@@ -507,7 +460,6 @@ def _object_table(obj):
 def _volume_table(blk, names=None):
     """volume table over all images, per source (pred / gt; one_candidate / best_of_S / mean_of_S): mean and largest intersection volume
     (cm^3) and the share of images with at least one solid cell of the object inside the hand (%); NaN for a source without values"""
-    from .ops_names import PHYSICS_SOURCES
     blk = blk.double()
     res = {}
     for s, name in enumerate(PHYSICS_SOURCES if names is None else names):

@@ -1378,24 +1378,14 @@ class HandObjectPenetration:
         poses in the camera frame, obj_id as in __call__; ``pitch`` (m; default cfg.physics_voxel_pitch).  -> (n,2) fp64 = n_cells (solid
         cell centres of the object inside the posed hand mesh) | IV = n_cells * pitch^3 (m^3); with ``flags`` also (n, max_pts) uint8,
         one flag per solid centre of the pair's object in the order of build_solids(pitch) (0 behind its last centre)."""
-        if pitch is None:
-            from .configs.args import cfg
-            pitch = cfg.physics_voxel_pitch
-        pitch = float(pitch)
-        if not pitch > 0.0:
-            raise VphoError(f'HandObjectPenetration.volume: the voxel pitch must be positive ({pitch})')
+        pitch = self._check_pitch(pitch, 'volume')
         if self.hand_faces is None:
             raise VphoError('HandObjectPenetration.volume: no hand mesh (pass hand_faces= or call set_hand_faces)')
         n, V = verts.shape[:2]
         assert verts.shape == (n, V, 3) and obj_rt.shape == (n, 3, 4)
         if self.hand_faces_max >= V:
             raise VphoError(f'HandObjectPenetration.volume: the hand faces index vertex {self.hand_faces_max}, the hands have {V}')
-        if not torch.is_tensor(obj_id):
-            ids = [int(i) for i in obj_id]
-            if len(ids) != n or any(i < 0 or i >= len(self.names) for i in ids):
-                raise VphoError(f'HandObjectPenetration: object ids {ids} outside [0, {len(self.names)}) or not one per image')
-            obj_id = _ids_to_device(ids, self.device)
-        assert obj_id.shape == (n,)
+        obj_id = self._check_ids(obj_id, n)
         sol = self.build_solids(pitch)
         F_ = int(self.hand_faces.shape[0])
         out = _new((n, 2), obj_rt, torch.float64)
@@ -1441,12 +1431,7 @@ class HandObjectPenetration:
         -> table (n,6) fp64 in the order of ops_names.VOLUME_MULTI_COLUMNS (hypothesis 0 | the minima over S | mean_cells = integer sum /
         S and mean_IV = pitch^3 * mean_cells; a NaN hypothesis makes best and mean NaN) and per_hyp (n,S,2) fp64 = n_cells | IV, the bits
         ``volume`` gives for the n*S pairs; with ``flags`` also (n,S,max_pts) uint8 with its bits.  n * S <= VOLUME_MULTI_MAX_PAIRS."""
-        if pitch is None:
-            from .configs.args import cfg
-            pitch = cfg.physics_voxel_pitch
-        pitch = float(pitch)
-        if not pitch > 0.0:
-            raise VphoError(f'HandObjectPenetration.volume_multi: the voxel pitch must be positive ({pitch})')
+        pitch = self._check_pitch(pitch, 'volume_multi')
         if self.hand_faces is None:
             raise VphoError('HandObjectPenetration.volume_multi: no hand mesh (pass hand_faces= or call set_hand_faces)')
         n, S, V = verts.shape[:3]
@@ -1457,12 +1442,7 @@ class HandObjectPenetration:
             raise VphoError(f'HandObjectPenetration.volume_multi: {n} x {S} pairs, at most {VOLUME_MULTI_MAX_PAIRS} in one call')
         if self.hand_faces_max >= V:
             raise VphoError(f'HandObjectPenetration.volume_multi: the hand faces index vertex {self.hand_faces_max}, the hands have {V}')
-        if not torch.is_tensor(obj_id):
-            ids = [int(i) for i in obj_id]
-            if len(ids) != n or any(i < 0 or i >= len(self.names) for i in ids):
-                raise VphoError(f'HandObjectPenetration: object ids {ids} outside [0, {len(self.names)}) or not one per image')
-            obj_id = _ids_to_device(ids, self.device)
-        assert obj_id.shape == (n,)
+        obj_id = self._check_ids(obj_id, n)
         sol = self.build_solids(pitch)
         cols = self.build_solid_columns(pitch)
         F_ = int(self.hand_faces.shape[0])
@@ -1479,6 +1459,27 @@ class HandObjectPenetration:
               _f32(verts), I(n), I(S), I(V), _f64(obj_rt), _i32(obj_id), C.c_double(pitch), _f64(per), _f64(table), _u8(fl), _ptr(ws), LL(need))
         return (table, per, fl) if flags else (table, per)
 
+    def _check_ids(self, obj_id, n):
+        """obj_id of the four metric calls as an (n,) device tensor: a host sequence of ints is range-checked and copied"""
+        if not torch.is_tensor(obj_id):
+            ids = [int(i) for i in obj_id]
+            if len(ids) != n or any(i < 0 or i >= len(self.names) for i in ids):
+                raise VphoError(f'HandObjectPenetration: object ids {ids} outside [0, {len(self.names)}) or not one per image')
+            obj_id = _ids_to_device(ids, self.device)
+        assert obj_id.shape == (n,)
+        return obj_id
+
+    @staticmethod
+    def _check_pitch(pitch, who):
+        """the voxel pitch (m) of ``volume`` / ``volume_multi`` as a float; default cfg.physics_voxel_pitch"""
+        if pitch is None:
+            from .configs.args import cfg
+            pitch = cfg.physics_voxel_pitch
+        pitch = float(pitch)
+        if not pitch > 0.0:
+            raise VphoError(f'HandObjectPenetration.{who}: the voxel pitch must be positive ({pitch})')
+        return pitch
+
     def obj_ids(self, names):
         """class indices of a batch as a device tensor (pinned host memory, asynchronous copy on the caller's stream, as
         ObjectMetrics.obj_ids); an unknown name raises VphoError"""
@@ -1494,12 +1495,7 @@ class HandObjectPenetration:
         with per_vertex also sd (n,V) fp64 and inside (n,V) uint8."""
         n, V = verts.shape[:2]
         assert verts.shape == (n, V, 3) and obj_rt.shape == (n, 3, 4)
-        if not torch.is_tensor(obj_id):
-            ids = [int(i) for i in obj_id]
-            if len(ids) != n or any(i < 0 or i >= len(self.names) for i in ids):
-                raise VphoError(f'HandObjectPenetration: object ids {ids} outside [0, {len(self.names)}) or not one per image')
-            obj_id = _ids_to_device(ids, self.device)
-        assert obj_id.shape == (n,)
+        obj_id = self._check_ids(obj_id, n)
         per = _new((n, 4), obj_rt, torch.float64)
         sd = _new((n, V), obj_rt, torch.float64)
         inside = _new((n, V), obj_rt, torch.uint8)
@@ -1517,12 +1513,7 @@ class HandObjectPenetration:
             raise VphoError('HandObjectPenetration.multi: built with accel=False (call build_accel() first)')
         n, S, V = verts.shape[:3]
         assert verts.shape == (n, S, V, 3) and obj_rt.shape == (n, S, 3, 4)
-        if not torch.is_tensor(obj_id):
-            ids = [int(i) for i in obj_id]
-            if len(ids) != n or any(i < 0 or i >= len(self.names) for i in ids):
-                raise VphoError(f'HandObjectPenetration: object ids {ids} outside [0, {len(self.names)}) or not one per image')
-            obj_id = _ids_to_device(ids, self.device)
-        assert obj_id.shape == (n,)
+        obj_id = self._check_ids(obj_id, n)
         table = _new((n, 12), obj_rt, torch.float64)
         per = _new((n, S, 4), obj_rt, torch.float64)
         sd = _new((n, S, V), obj_rt, torch.float64) if per_vertex else None

@@ -217,52 +217,20 @@ class Trainer:
     def eval(self, loader=None, eval_best=None, eval_physics=None, physics_multi=None, eval_volume=None, volume_multi=None, eval_hand_bench=None,
              hand_bench_multi=None):
         """``evaluate(testing_dataloader)`` (train_diff_hand_obj.py:202-357).  ``loader``: see ``_eval_batches``; default synthetic.
-        ``eval_best`` (default: cfg.eval_best, the reference's is_eval_best): also score every sampled hypothesis and report the
-        one_candidate, best_of_S and mean_of_S tables (rows of evaluate.ROW_BEST columns).  ``eval_physics`` (default:
-        cfg.eval_physics): also report hand-object penetration and contact, the ``physics`` table (evaluate.PHYS more columns, last);
-        ``physics_multi`` (default: cfg.eval_best and cfg.eval_physics, i.e. both command-line flags; it needs both of the above):
-        every sampled hypothesis' penetration as well (evaluate.PHYS_MULTI more columns, last; the ``physics`` table gains
-        one_candidate, best_of_S and mean_of_S).  A caller that passes eval_best / eval_physics itself gets the rows it always got
-        unless it asks for the new block too.  ``eval_volume`` (default: cfg.eval_volume; independent of the others): also report the
-        hand-object intersection volume at cfg.physics_voxel_pitch, the ``volume`` table (evaluate.VOL more columns, last of all).
-        ``volume_multi`` (default: cfg.eval_best and cfg.eval_volume, i.e. both command-line flags; it needs eval_best and eval_volume):
-        every sampled hypothesis' intersection volume as well (evaluate.VOL_MULTI more columns immediately before the VOL block; the
-        ``volume`` table gains one_candidate, best_of_S and mean_of_S).  As with physics_multi, a caller that passes eval_best /
-        eval_volume itself gets the rows it always got unless it asks for the new block too.  ``eval_hand_bench`` (default:
-        cfg.eval_hand_bench): also report the hand F-scores and PCK AUC of the HO3D / FreiHAND leaderboards for the aggregated and the
-        regression hand, the ``hand_bench`` table (evaluate.HAND_BENCH more columns after everything above); ``hand_bench_multi``
-        (default: cfg.eval_best and cfg.eval_hand_bench; it needs eval_best and eval_hand_bench): every sampled hypothesis as well
-        (evaluate.HAND_BENCH_MULTI more columns, last of all; the table gains one_candidate, best_of_S and mean_of_S)."""
+        The seven flags choose the column blocks of the returned rows and the tables printed from them (eval_layout.BLOCKS has the blocks
+        and their order, INTEGRATION.md §1 what they hold): ``eval_best`` (the reference's is_eval_best) scores every sampled hypothesis
+        (tables one_candidate, best_of_S, mean_of_S), ``eval_physics`` reports hand-object penetration and contact (``physics``),
+        ``eval_volume`` the intersection volume at cfg.physics_voxel_pitch (``volume``), ``eval_hand_bench`` the hand F-scores and PCK AUC
+        of the HO3D / FreiHAND leaderboards (``hand_bench``); ``physics_multi`` / ``volume_multi`` / ``hand_bench_multi`` add every sampled
+        hypothesis to that table and need eval_best and the table's own flag.  Defaults (None): cfg.eval_best / eval_physics / eval_volume
+        / eval_hand_bench, and for a *_multi flag cfg.eval_best and cfg.eval_<its table>, i.e. both command-line flags: a caller that
+        passes eval_best / eval_physics / ... itself gets the rows it always got unless it asks for the newer block too."""
         from .configs.args import cfg
-        eval_hand_bench = bool(cfg.eval_hand_bench if eval_hand_bench is None else eval_hand_bench)
-        eval_volume = bool(cfg.eval_volume if eval_volume is None else eval_volume)
-        # the keyword travels to metric_rows only when it is set: without it the call is the one it always was
-        vol = dict(eval_volume=True) if eval_volume else {}
-        eval_best = bool(cfg.eval_best if eval_best is None else eval_best)
-        volume_multi = bool((cfg.eval_best and cfg.eval_volume) if volume_multi is None else volume_multi) and eval_best and eval_volume
-        if volume_multi:
-            vol['volume_multi'] = True
-        eval_physics = bool(cfg.eval_physics if eval_physics is None else eval_physics)
-        physics_multi = bool((cfg.eval_best and cfg.eval_physics) if physics_multi is None else physics_multi) and eval_best and eval_physics
-        hand_bench_multi = bool((cfg.eval_best and cfg.eval_hand_bench) if hand_bench_multi is None else hand_bench_multi) and eval_best and eval_hand_bench
-        bench_cols = E.hand_bench_width(hand_bench_multi) if eval_hand_bench else 0
-
-        def batch_rows(out, batch, gt, first):
-            rows = E.metric_rows(out, batch, gt[0], gt[1], first, self.assets, eval_best, eval_physics, physics_multi, **vol)
-            if not eval_hand_bench:
-                return rows
-            # the hand benchmark blocks come last of all (the 16, then the 24): still one row tensor, one all-gather
-            blocks = [rows, E.hand_bench_block(out, batch, gt[0], gt[1])]
-            if hand_bench_multi:
-                blocks.append(E.hand_bench_multi_block(out, batch, gt[0], gt[1]))
-            return torch.cat(blocks, 1)
-
-        if eval_physics:
-            # object meshes and their tables (with eval_best also the multi-hypothesis kernel's), once, before the timed loop
-            E.physics_meter(self.assets, self.device, multi=physics_multi)
-        if eval_volume:
-            # the closed hand mesh and the objects' solids at the configured pitch, once, before the timed loop
-            E.physics_meter(self.assets, self.device, volume=True, volume_multi=volume_multi)
+        layout = E.RowLayout.resolve(eval_best, eval_physics, physics_multi, eval_volume, volume_multi, eval_hand_bench, hand_bench_multi)
+        batch_rows = lambda out, batch, gt, first: E.metric_rows(out, batch, gt[0], gt[1], first, self.assets, layout=layout)
+        if layout.has('physics') or layout.has('volume'):
+            # object meshes, acceleration tables, the closed hand mesh, the objects' solids: what the layout needs, once, before the timed loop
+            E.physics_meter(self.assets, self.device, multi=layout.has('physics_multi'), volume=layout.has('volume'), volume_multi=layout.has('volume_multi'))
         rows = []
         t0 = time.perf_counter()
         # three batches in flight (independent images; see evaluate.PipelinedPredictor)
@@ -287,7 +255,7 @@ class Trainer:
         pipe.close()
         # a rank whose shard is empty still takes part in the collective (with zero rows: the ragged gather carries the counts first);
         # raising here would leave the other ranks blocked in their all-gather.  Only an evaluation without ANY image is an error
-        mine = torch.cat(rows, 0) if rows else torch.zeros((0, E.row_width(eval_best, eval_physics, physics_multi, volume_multi, eval_volume) + bench_cols), device=self.device, dtype=torch.float32)
+        mine = torch.cat(rows, 0) if rows else torch.zeros((0, layout.width), device=self.device, dtype=torch.float32)
         rows = E.gather_rows(mine)
         if rows.shape[0] == 0:
             raise ValueError('Trainer.eval: the loader yielded no batch on any rank')
@@ -297,10 +265,7 @@ class Trainer:
             what = 'synthetic images' if loader is None else 'images'
             print(f'evaluated {rows.shape[0]} {what} on {self.world} GPU(s) in {dt:.2f} s ({rows.shape[0] / dt:.1f} images/s)')
             print(f'aggregation_mode_hand {cfg.aggregation_mode_hand}  aggregation_mode_obj {cfg.aggregation_mode_obj}')
-            host = rows.cpu()
-            table = E.summarize(host[:, :-bench_cols] if bench_cols else host)
-            if bench_cols:
-                table['hand_bench'] = E.hand_bench_table(host[:, -bench_cols:])
+            table = E.summarize(rows.cpu(), layout)
             for name, r in table.items():
                 if name not in ('object', 'physics', 'volume', 'hand_bench') + E.MULTI_TABLES:
                     print(f'{name:>5s}: n={r["n"]:5d}  MJE reg {r["MJE_reg"]:.2f}  first {r["MJE_first"]:.2f}  agg {r["MJE_agg"]:.2f}  MVE agg {r["MVE_agg"]:.2f}  (mm)')
@@ -309,15 +274,9 @@ class Trainer:
                 if name in table:
                     print(f'{name} hand (mm): ' + '  '.join(f'{k} {v:.2f}' for k, v in table[name]['hand'].items()))
                     print(f'{name} object: ' + '  '.join(f'{k} {v:.2f}' for k, v in table[name]['object'].items()))
-            if 'physics' in table:
-                for src, r in table['physics'].items():
-                    print(f'physics {src}: ' + '  '.join(f'{k} {v:.2f}' for k, v in r.items()))
-            if 'volume' in table:
-                for src, r in table['volume'].items():
-                    print(f'volume {src} (pitch {cfg.physics_voxel_pitch * 1000.0:g} mm): ' + '  '.join(f'{k} {v:.3f}' for k, v in r.items()))
-            if 'hand_bench' in table:
-                for src, r in table['hand_bench'].items():
-                    print(f'hand_bench {src}: ' + '  '.join(f'{k} {v:.4f}' for k, v in r.items()))
+            for name, note, fmt in (('physics', '', '.2f'), ('volume', f' (pitch {cfg.physics_voxel_pitch * 1000.0:g} mm)', '.3f'), ('hand_bench', '', '.4f')):
+                for src, r in table.get(name, {}).items():
+                    print(f'{name} {src}{note}: ' + '  '.join(f'{k} {v:{fmt}}' for k, v in r.items()))
             import json
             print('EVAL_JSON ' + json.dumps({'images': int(rows.shape[0]), 'world': self.world, 'aggregation_mode_hand': cfg.aggregation_mode_hand,
                                              'aggregation_mode_obj': cfg.aggregation_mode_obj, 'table': table}))
