@@ -781,6 +781,21 @@ VPHO_API int vpho_adamw_f32(float* param, const float* grad, float* exp_avg, flo
  * first_block = running sum of ceil(n / 1024) over the preceding records, total_blocks = that sum over all records. */
 VPHO_API int vpho_adamw_multi_f32(const void* segments, int n_segments, long long total_blocks, float lr, float beta1, float beta2, float eps,
                          float weight_decay, int step, float grad_scale, void* stream);
+/* ---- optimiser tail (optim.hip): global gradient norm + Adam / AdamW with the clip coefficient formed on the device ------------------
+ * sum of grad[i]^2 over a contiguous fp32 buffer (any 4-byte alignment) into ONE fp64 value on the device.  fp64 accumulation in a
+ * fixed order (a grid that depends on n alone, contiguous chunks, lanes then waves, then the partials in ascending index; no atomics):
+ * two runs, and data-parallel replicas holding the same gradients, get the same bits.  workspace: vpho_grad_sqnorm_workspace_bytes(n)
+ * bytes, 8-byte aligned (-1 = bad argument). */
+VPHO_API long long vpho_grad_sqnorm_workspace_bytes(long long n);
+VPHO_API int vpho_grad_sqnorm_f64(const float* grad, long long n, double* out, void* workspace, void* stream);
+/* vpho_adamw_multi_f32's segment table and block ownership, plus: kind 0 = torch.optim.AdamW (decoupled decay; with sqnorm NULL the
+ * bits of vpho_adamw_multi_f32), kind 1 = torch.optim.Adam with L2 decay (g += weight_decay * param before the moments).  sqnorm
+ * (device, may be NULL) = the sum of squares of the SUMMED gradient: every thread forms torch.nn.utils.clip_grad_norm_'s
+ * coef = min(1, max_norm / (grad_scale * sqrt(*sqnorm) + 1e-6)) in fp64, rounds it once to fp32 and steps with (g * grad_scale) * coef;
+ * coef == 1 leaves the bits of the unclipped step, a non-finite norm makes the update NaN as torch does.  grad_scale =
+ * 1 / (world_size * accumulation_steps).  The gradients are only read. */
+VPHO_API int vpho_optim_multi_f32(const void* segments, int n_segments, long long total_blocks, int kind, float lr, float beta1, float beta2, float eps,
+                         float weight_decay, int step, float grad_scale, const double* sqnorm, float max_norm, void* stream);
 
 /* ---- physics branch of the training step (lib/model/VPHO.py:170-172,205-212 under loss.backward()) -------------------------------
  * backward of vpho_cross_tokens_f32 (cross_module.py:125-133: .view(bs,32,-1) of the projected maps, cat, + positional code):

@@ -6,7 +6,7 @@ from vpho_amd.trainer import Trainer
 def main():
     trainer = Trainer(cfg)
     if cfg.mode == 'train':
-        trainer.run()
+        trainer.train()
     elif cfg.mode == 'eval':
         trainer.eval()
     elif cfg.mode == 'infer':

@@ -69,6 +69,14 @@ class Config:
         self.weight_torque_loss = 1.0
         self.weight_supervised_loss = 1.0
         self.weight_CoM_loss = 1.0
+        # the training loop of Trainer.fit (lib/configs/args.py:131-144; max_epochs None = one pass of Trainer.run, nothing written)
+        self.max_epochs = None
+        self.optimizer = 'adamw'
+        self.scheduler = 'exp'
+        self.gamma = 0.96
+        self.lr_step = 5
+        self.gradient_accumulation_steps = 1
+        self.print_freq = 500
         self.cross_dropout = 0.1      # the reference's nn.TransformerEncoderLayer / PositionalEncoding default (cross_module.py:64,104-107)
 
 
@@ -126,6 +134,13 @@ def _parser():
     p.add_argument('--weight_supervised_loss', type=float, default=10)
     p.add_argument('--weight_CoM_loss', type=float, default=1e2)
     p.add_argument('--cross_dropout', type=float, default=0.1)
+    p.add_argument('--max_epochs', type=int, default=None)
+    p.add_argument('--optimizer', type=str, default='adamw', choices=['adamw', 'adam'])
+    p.add_argument('--scheduler', type=str, default='exp', choices=['exp', 'cosine', 'step'])
+    p.add_argument('--gamma', type=float, default=0.96)
+    p.add_argument('--lr_step', type=int, default=5)
+    p.add_argument('--gradient_accumulation_steps', type=int, default=1)
+    p.add_argument('--print_freq', type=int, default=500)
     return p
 
 

@@ -54,11 +54,16 @@ class GradBuckets:
             self.range[b] = (min(lo, off), off + n)
             off += n
         self._work, self._flushed = [], set()
+        self._accumulate = self._hold = False
 
     # ---- one step -------------------------------------------------------------------------------------------------------
-    def begin(self):
-        """tensors no loss of this batch reaches keep a zero gradient"""
-        self.flat.zero_()
+    def begin(self, accumulate=False, hold=False):
+        """tensors no loss of this batch reaches keep a zero gradient.  Gradient accumulation (accelerate's ``accumulate`` =
+        DistributedDataParallel.no_sync): ``accumulate`` -- a later micro-step: the buffer is kept and ``put`` adds into it; ``hold`` -- not
+        the last micro-step: ``flush`` exchanges nothing, the sum of the micro-steps travels once, at the last one"""
+        if not accumulate:
+            self.flat.zero_()
+        self._accumulate, self._hold = bool(accumulate), bool(hold)
         self._work, self._flushed = [], set()
 
     def put(self, grads):
@@ -76,13 +81,19 @@ class GradBuckets:
                 g = pk
             elif g.shape != slot.shape and k in self.conv_meta:       # a reference-layout gradient from elsewhere: one strided copy
                 cout, cin, kh, kw = self.conv_meta[k]
-                slot.view(cout, kh, kw, -1)[..., :cin].copy_(g.reshape(cout, cin, kh, kw).permute(0, 2, 3, 1))
+                ref = g.reshape(cout, cin, kh, kw).permute(0, 2, 3, 1)
+                if self._accumulate:
+                    slot.view(cout, kh, kw, -1)[..., :cin].add_(ref)
+                else:
+                    slot.view(cout, kh, kw, -1)[..., :cin].copy_(ref)
                 continue
             else:
                 g = g.reshape(slot.shape)
             dst.append(slot)
             src.append(g if g.is_contiguous() else g.contiguous())
-        if dst:
+        if dst and self._accumulate:
+            torch._foreach_add_(dst, src)
+        elif dst:
             torch._foreach_copy_(dst, src)
 
     def flush(self, bucket):
@@ -90,7 +101,7 @@ class GradBuckets:
         assert bucket not in self._flushed, bucket
         self._flushed.add(bucket)
         from .launch import group_active
-        if bucket not in self.range or not group_active():
+        if bucket not in self.range or self._hold or not group_active():
             return
         lo, hi = self.range[bucket]
         seg = self.flat[lo:hi]

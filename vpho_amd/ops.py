@@ -26,6 +26,7 @@ lib.vpho_obj_metrics_multi_workspace_bytes.restype = C.c_longlong
 lib.vpho_bn_workspace_bytes.restype = C.c_longlong
 lib.vpho_conv2d_wgrad_workspace_bytes.restype = C.c_longlong
 lib.vpho_mha_bwd_workspace_bytes.restype = C.c_longlong
+lib.vpho_grad_sqnorm_workspace_bytes.restype = C.c_longlong
 lib.vpho_infer_record_bytes.restype = C.c_longlong
 lib.vpho_hand_obj_intersection_workspace_bytes.restype = C.c_longlong
 lib.vpho_hand_obj_intersection_multi_workspace_bytes.restype = C.c_longlong
@@ -1772,6 +1773,55 @@ class AdamWList:
               I(step), F(grad_scale))
         # the kernel wrote through raw pointers: tell torch, so that everything cached per weight VERSION (the Winograd transforms of
         # winograd_weights_device, the bf16 planes) is rebuilt -- no launch, a counter per tensor
+        torch.autograd.graph.increment_version([q[0] for q in self.keep])
+
+
+def grad_sqnorm(flat, ws=None, out=None):
+    """sum of squares of a contiguous fp32 buffer -> 0-d fp64 tensor that stays on the device (fixed summation order: two runs give the
+    same bits).  ``ws``: a uint8 workspace of at least ``grad_sqnorm_workspace_bytes(n)`` bytes to reuse; ``out``: a 0-d fp64 tensor to write"""
+    n = flat.numel()
+    need = lib.vpho_grad_sqnorm_workspace_bytes(LL(n))
+    if need < 0:
+        raise VphoError(f'vpho_grad_sqnorm_workspace_bytes: bad argument (n={n})')
+    if ws is None:
+        ws = torch.empty(need // 8, dtype=torch.float64, device=flat.device)
+    elif ws.numel() * ws.element_size() < need:
+        raise VphoError(f'grad_sqnorm: a workspace of {ws.numel() * ws.element_size()} bytes, {need} are needed')
+    if out is None:
+        out = _new((), flat, torch.float64)
+    _call('vpho_grad_sqnorm_f64', _f32(flat), LL(n), _f64(out), _ptr(ws))
+    return out
+
+
+def grad_sqnorm_workspace_bytes(n):
+    return int(lib.vpho_grad_sqnorm_workspace_bytes(LL(n)))
+
+
+OPTIM_KINDS = {'adamw': 0, 'adam': 1}
+
+
+class OptimList:
+    """torch.optim.AdamW (kind 0) or torch.optim.Adam with L2 decay (kind 1) on a fixed list of (param, grad, exp_avg, exp_avg_sq) tensors
+    as ONE launch (vpho_optim_multi_f32).  ``sqnorm`` (0-d fp64 device tensor from ``grad_sqnorm`` of the summed gradients) + ``max_norm``:
+    the kernel forms clip_grad_norm_'s coefficient itself; the gradients are never written."""
+    def __init__(self, quads):
+        self.keep = quads
+        rows, blk = [], 0
+        for p, g, m, v in quads:
+            for t in (p, g, m, v):
+                _ptr(t, torch.float32)
+            assert p.numel() == g.numel() == m.numel() == v.numel()
+            rows.append([p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), blk])
+            blk += (p.numel() + 1023) // 1024
+        self.blocks, self.n = blk, len(rows)
+        self.table = torch.tensor(rows, dtype=torch.int64).to(quads[0][0].device)
+
+    def step(self, step, kind=0, lr=2e-4, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.01, grad_scale=1.0, sqnorm=None, max_norm=0.0):
+        if sqnorm is not None and not (sqnorm.numel() == 1 and max_norm > 0):
+            raise VphoError(f'OptimList.step: clipping needs one fp64 value and max_norm > 0 (got {tuple(sqnorm.shape)}, {max_norm})')
+        _call('vpho_optim_multi_f32', _ptr(self.table, torch.int64), I(self.n), LL(self.blocks), I(OPTIM_KINDS.get(kind, kind)), F(lr), F(beta1),
+              F(beta2), F(eps), F(weight_decay), I(step), F(grad_scale), _f64(sqnorm), F(max_norm))
+        # raw-pointer writes: bump the version counters, as AdamWList.step does (Winograd transforms and bf16 planes are cached per version)
         torch.autograd.graph.increment_version([q[0] for q in self.keep])
 
 

@@ -23,11 +23,18 @@ from .train_score import ScoreTrainer, SUFFIXES
 
 
 class DiffusionTrainStep:
-    def __init__(self, state_dict, device, lr=None, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, loss_weights=None, assets=None,
-                 cross_dropout=None):
+    def __init__(self, state_dict, device, lr=None, betas=(0.9, 0.999), eps=1e-8, weight_decay=None, loss_weights=None, assets=None,
+                 cross_dropout=None, optimizer='adamw'):
+        """``optimizer``: 'adamw' (train_diff_hand_obj.py:52; decoupled decay, default 0.01) or 'adam' (:54; L2 decay, default 0.0005) --
+        'adam' is stepped by the fused tail only (``step(..., fused=True)``)."""
+        from .checkpoint import optimizer_hyper
         self.dev = torch.device(device)
         sd = state_dict
         lr = cfg.base_learning_rate if lr is None else lr
+        self.optimizer = optimizer
+        weight_decay = optimizer_hyper(optimizer, lr, betas, eps, weight_decay)['weight_decay']
+        # position of every trained tensor in vpho_net(...).named_parameters(): the index optimizer.bin keeps its state under
+        self.param_order = [k for k in sd if not k.endswith(('.running_mean', '.running_var', '.num_batches_tracked'))]
         self.fpn = FPNTrain(sd, 'feature_extractor', self.dev)
         self.hm = dict(h=HeatmapHeadTrain(sd, 'head_hm_hand', self.dev), o=HeatmapHeadTrain(sd, 'head_hm_obj', self.dev))
         self.enc = dict(h=EncoderTrain(sd, 'encoder_hand', self.dev), o=EncoderTrain(sd, 'encoder_obj', self.dev))
@@ -49,6 +56,7 @@ class DiffusionTrainStep:
         self.w.update(loss_weights or {})
         self.hyper = dict(lr=lr, beta1=betas[0], beta2=betas[1], eps=eps, weight_decay=weight_decay)
         self.steps = 0
+        self._shape0 = {k: tuple(v.shape) for k, v in sd.items()}          # the reference's shapes (optimizer_state)
         # optimiser state: AdamW (element-wise) steps every tensor in the layout the kernels read it in -- the live tensor IS the master.
         # Convolution weights stay packed (cout, kh*kw*cin_pad; padded input channels are zero and stay zero: zero gradient, decoupled
         # decay of zero), their gradients arrive packed from the weight-gradient kernels, and the reference's (cout, cin, kh, kw) is
@@ -148,6 +156,11 @@ class DiffusionTrainStep:
         self.flat_grad, self.grad_view = self.buckets.flat, self.buckets.view
         self.m = {k: torch.zeros_like(v) for k, v in self.master.items()}
         self.v = {k: torch.zeros_like(v) for k, v in self.master.items()}
+        # trained tensors in module order; what the state_dict holds beside them (buffers such as the Fourier features) is not a parameter
+        self.param_order = [k for k in self.param_order if k in self.master]
+        assert len(self.param_order) == len(self.master), sorted(set(self.master) - set(self.param_order))[:5]
+        self.stepped = set()                               # tensors the optimiser has stepped at least once (torch keeps state for those only)
+        self._acc_live = set()
 
     # ------------------------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -317,15 +330,24 @@ class DiffusionTrainStep:
 
     # ------------------------------------------------------------------------------------------------------------------
     @torch.no_grad()
-    def step(self, data, gt_hand, gt_obj, draws=None, repeat_num=None, eps=1e-5, lr=None, gradient_clip=None):
+    def step(self, data, gt_hand, gt_obj, draws=None, repeat_num=None, eps=1e-5, lr=None, gradient_clip=None, fused=False, accumulation=None):
         """loss_and_grads + gradient average over the ranks (bucketed all-reduces issued DURING the backward, grad_buckets.py) + AdamW on
         every tensor.
-        Without `draws` they are made like loss_fn's (torch.rand / torch.randn on the device, score_based_model.py:24,31)."""
+        Without `draws` they are made like loss_fn's (torch.rand / torch.randn on the device, score_based_model.py:24,31).
+        ``fused=True``: the optimiser tail as two launches (``_fused_step``: one fixed-order fp64 norm when clipping, one Adam / AdamW
+        update that clips by itself); ``flat_grad`` keeps the unclipped sum and ``losses['grad_norm']`` holds the averaged norm.
+        ``accumulation=(i, A)`` (fused only): micro-step i of A -- gradients add up in the flat buffer, buckets travel and the optimiser
+        steps at micro-step A - 1 only (or at ``(i, A, True)``: the loader ends inside a group), with 1 / A in the gradient scale
+        (accel.accumulate, train_diff_hand_obj.py:176-185)."""
         bs = data['rgb'].shape[0]
         reps = cfg.repeat_num if repeat_num is None else repeat_num
         if draws is None:
             u = lambda: torch.rand(reps, bs, device=self.dev) * (1. - eps) + eps
             draws = dict(t_h=u(), z_h=torch.randn(reps, bs, 96, device=self.dev), t_o=u(), z_o=torch.randn(reps, bs, 9, device=self.dev))
+        if fused:
+            return self._fused_step(data, gt_hand, gt_obj, draws, lr, gradient_clip, accumulation)
+        if accumulation is not None or self.optimizer != 'adamw':
+            raise ValueError("gradient accumulation and optimizer='adam' need step(..., fused=True)")
         self.buckets.begin()
         losses, grads = self.loss_and_grads(data, gt_hand, gt_obj, draws, sink=self.buckets)
         unknown = set(grads) - set(self.names)
@@ -358,7 +380,120 @@ class DiffusionTrainStep:
                     self._repack[k](self.master[k])
             self.dgrad_weights.refresh()
             self.wino_weights.refresh()
+        self.stepped.update(live)
         return losses
+
+    def _fused_step(self, data, gt_hand, gt_obj, draws, lr, gradient_clip, accumulation):
+        i, A = (0, 1) if accumulation is None else (int(accumulation[0]), int(accumulation[1]))
+        if not 0 <= i < A:
+            raise ValueError(f'accumulation=(i, A) needs 0 <= i < A, got {accumulation}')
+        last = i == A - 1 or (len(accumulation or ()) > 2 and bool(accumulation[2]))     # (i, A, True): the epoch ends inside a group
+        self.buckets.begin(accumulate=i > 0, hold=not last)
+        if i == 0:
+            self._acc_live = set()
+        losses, grads = self.loss_and_grads(data, gt_hand, gt_obj, draws, sink=self.buckets)
+        unknown = set(grads) - set(self.names)
+        assert not unknown, sorted(unknown)[:5]
+        self._acc_live.update(grads)
+        if not last:
+            return losses                                        # nothing exchanged, nothing stepped: the sum waits in flat_grad
+        multi = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
+        live = list(self.names) if multi else [k for k in self.names if k in self._acc_live]         # as step(): see there
+        scale = self.buckets.finish()
+        if A > 1:
+            scale = scale / A
+        clip = cfg.gradient_clip if gradient_clip is None else gradient_clip
+        self.steps += 1
+        hyper = dict(self.hyper, lr=self.hyper['lr'] if lr is None else lr)
+        with torch.cuda.device(self.dev):
+            sq = None
+            if clip > 0:
+                if getattr(self, '_sqn_ws', None) is None:
+                    self._sqn_ws = torch.empty(ops.grad_sqnorm_workspace_bytes(self.flat_grad.numel()) // 8, device=self.dev, dtype=torch.float64)
+                sq = ops.grad_sqnorm(self.flat_grad, ws=self._sqn_ws)
+                losses['grad_norm'] = sq.sqrt() * scale          # the norm accel.clip_grad_norm_ returns: of the averaged gradient
+            key = (self.optimizer,) + tuple(live)
+            if getattr(self, '_optim_key', None) != key:
+                self._optim = ops.OptimList([(self.master[k], self.grad_view[k], self.m[k], self.v[k]) for k in live])
+                self._optim_key = key
+            self._optim.step(self.steps, kind=self.optimizer, grad_scale=scale, sqnorm=sq, max_norm=float(clip) if clip > 0 else 0.0, **hyper)
+            for k in live:
+                if self._repack[k] is not None:
+                    self._repack[k](self.master[k])
+            self.dgrad_weights.refresh()
+            self.wino_weights.refresh()
+        self.stepped.update(live)
+        return losses
+
+    # ------------------------------------------------------------------------------------------------------------------
+    def _ref_moment(self, name, t):
+        """a moment tensor (kept in the layout of its master) in the reference's layout: the view of ``_ref_view``, padding dropped"""
+        if name in self._conv_meta:
+            cout, cin, kh, kw = self._conv_meta[name]
+            return t.view(cout, kh, kw, -1)[..., :cin].permute(0, 3, 1, 2)
+        return t
+
+    def _order(self, param_names):
+        """the parameter list optimizer.bin indexes: ``[n for n, _ in vpho_net(...).named_parameters()]``.  Default: the trained tensors
+        in the order of the constructor's state_dict -- that list when every module is trained (``assets`` with MANO and anchor tables)."""
+        order = self.param_order if param_names is None else list(param_names)
+        missing = set(self.master) - set(order)
+        if missing:
+            raise ValueError(f'param_names lacks trained tensors: {sorted(missing)[:5]}')
+        return order
+
+    def optimizer_state(self, param_names=None):
+        """``torch.optim.AdamW / Adam.state_dict()`` of this step: ``state[i]`` = {step (float tensor), exp_avg, exp_avg_sq} in the
+        REFERENCE's shapes, i = position in ``vpho_net(...).named_parameters()`` (``_order``; frozen parameters, tensors this step does
+        not train and tensors no step has reached are counted and carry no state, as torch keeps none for a parameter without a
+        gradient); ``param_groups`` with torch's keys and this step's hyper-parameters"""
+        from .checkpoint import param_groups
+        state = {}
+        shapes = self._ref_shapes()
+        order = self._order(param_names)
+        for i, k in enumerate(order):
+            if k in self.stepped:
+                state[i] = dict(step=torch.tensor(float(self.steps)),
+                                exp_avg=self._ref_moment(k, self.m[k]).reshape(shapes[k]).clone(memory_format=torch.contiguous_format).cpu(),
+                                exp_avg_sq=self._ref_moment(k, self.v[k]).reshape(shapes[k]).clone(memory_format=torch.contiguous_format).cpu())
+        h = self.hyper
+        groups = param_groups(self.optimizer, len(order), h['lr'], (h['beta1'], h['beta2']), h['eps'], h['weight_decay'])
+        return dict(state=state, param_groups=groups)
+
+    def _ref_shapes(self):
+        return {k: (self._conv_meta[k] if k in self._conv_meta else tuple(self._shape0[k])) for k in self.master}
+
+    @torch.no_grad()
+    def load_optimizer_state(self, state, param_names=None):
+        """the inverse of ``optimizer_state``: moments (reference layout) into the packed buffers, the step count, and the group's
+        hyper-parameters (lr, betas, eps, weight_decay).  Accepts what ``accel.save_state`` wrote for the reference's optimiser."""
+        groups = state['param_groups']
+        order = self._order(param_names)
+        n = sum(len(g['params']) for g in groups)
+        if n != len(order):
+            raise ValueError(f'optimizer state of {n} parameters, this model has {len(order)}')
+        g0 = groups[0]
+        self.hyper.update(lr=float(g0['lr']), beta1=float(g0['betas'][0]), beta2=float(g0['betas'][1]), eps=float(g0['eps']),
+                          weight_decay=float(g0['weight_decay']))
+        steps, self.stepped = set(), set()
+        for k in self.master:
+            self.m[k].zero_()
+            self.v[k].zero_()
+        for i, st in state['state'].items():
+            k = order[int(i)]
+            if k not in self.master:
+                continue
+            for dst, key in ((self.m[k], 'exp_avg'), (self.v[k], 'exp_avg_sq')):
+                src = st[key].to(self.dev, torch.float32)
+                if k in self._conv_meta:
+                    self._ref_moment(k, dst).copy_(src.reshape(self._conv_meta[k]))
+                else:
+                    dst.copy_(src.reshape(dst.shape))
+            steps.add(int(float(st['step'])))
+            self.stepped.add(k)
+        if len(steps) > 1:
+            raise ValueError(f'optimizer state with different step counts per parameter ({sorted(steps)[:4]}...): one count is kept for all tensors')
+        self.steps = steps.pop() if steps else 0
 
     def state_dict(self):
         """trained tensors + BatchNorm running statistics under the reference's names"""

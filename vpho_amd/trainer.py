@@ -8,6 +8,8 @@ same RANK/LOCAL_RANK/WORLD_SIZE variables).  There is no dataset in this build: 
 backbone, heat-map heads, encoders, MANO head and score networks are all updated); ``--train_scope score`` trains the two score
 networks on frozen features (``ScoreTrainer.step``: the reference's ``repeat_num`` DSM draws, backward, data-parallel gradient
 average and AdamW per denoiser).
+``fit`` (``--mode train --max_epochs N``): the reference's epoch loop around that step -- LR schedule, gradient clipping and accumulation,
+a checkpoint in accelerate's format after every epoch, resume (vpho_amd/checkpoint.py).
 ``infer`` (``--mode infer``): the same batches through the same pipeline, predictions written to files (vpho_amd/infer.py).
 """
 import os
@@ -61,6 +63,11 @@ def loader_indices_are_consecutive(index):
     return bool((i[1:] - i[:-1] == 1).all()) if i.numel() > 1 else True
 
 
+def train_entry(cfg):
+    """which Trainer method ``main.py --mode train`` runs: 'fit' (epochs, scheduler, checkpoints) when --max_epochs is given, else 'run'"""
+    return 'fit' if getattr(cfg, 'max_epochs', None) is not None else 'run'
+
+
 class Trainer:
     def __init__(self, cfg):
         self.cfg = cfg
@@ -99,8 +106,8 @@ class Trainer:
         gt_obj = torch.cat([rot[:, 16, :2, :].reshape(bs, 6), torch.randn(bs, 3, generator=g) * 0.05], -1).to(self.device)
         return gt_hand, gt_obj, g
 
-    def _train_batches(self, loader, n_batches, mano):
-        """yields (batch on the device, gt_hand (bs,96) rot6d, gt_obj (bs,9)).  ``loader`` None: synthetic batches with synthetic targets.
+    def _train_batches(self, loader, n_batches, mano, start=0):
+        """``start``: number of the first synthetic batch (Trainer.fit numbers them through the epochs).  yields (batch on the device, gt_hand (bs,96) rot6d, gt_obj (bs,9)).  ``loader`` None: synthetic batches with synthetic targets.
         Otherwise any iterable of collated Appendix-A batch dicts with the training keys of lib/dataset/dexycb6.py:471-509 (hm_hand,
         hm_obj, gt_mano, gt_obj, gt_hand_vert_flip, gt_hand_jt3d_flip, force_local, ...): the targets are derived as the reference's
         forward does, gt_hand = mano_aa_to_6D(gt_mano)[..., :96] (VPHO.py:190, head_mano.py:10-18), gt_obj as it stands."""
@@ -116,7 +123,7 @@ class Trainer:
                     raise KeyError(f'training batch lacks {missing} (lib/dataset/dexycb6.py:471-509)')
                 yield b, _aa_to_rot6d(b['gt_mano'][:, :48].float()), b['gt_obj'].float().contiguous()
             return
-        for i in range(cfg.num_batches if n_batches is None else n_batches):
+        for i in range(start, start + (cfg.num_batches if n_batches is None else n_batches)):
             batch = self._to_device(synth_batch(bs, self.assets, seed=cfg.random_seed + i, rank=self.rank))
             gt_hand, gt_obj, g = self._synthetic_targets(bs, i)
             batch['hm_hand'] = (torch.rand(bs, 21, cfg.heatmap_size, cfg.heatmap_size, generator=g) * 0.2).to(self.device)
@@ -136,10 +143,82 @@ class Trainer:
         for i, (batch, gt_hand, gt_obj) in enumerate(self._train_batches(loader, n_batches, step.mano_head.mano)):
             L = step.step(batch, gt_hand, gt_obj)
             hist.append({k: float(v) for k, v in L.items()})
-            if self.rank == 0 and i % max(1, getattr(cfg, 'print_freq', 10)) == 0:
+            if self.rank == 0 and i % 10 == 0:
                 print(f'[{i:04d}] ' + '  '.join(f'{k.replace("_loss", "")} {v:.3e}' for k, v in hist[-1].items()))
         self.model.load_state_dict(step.state_dict(), strict=False)
         return hist
+
+    def train(self):
+        """``--mode train``: the epoch loop ``fit`` when ``--max_epochs`` is given, else one pass ``run`` (nothing written)"""
+        return getattr(self, train_entry(self.cfg))()
+
+    def fit(self, loader=None, epochs=None, save_dir=None, eval_loader=None):
+        """The reference's training loop (train_diff_hand_obj.py:126-199, base_trainer.py:81-96): ``epochs`` (default cfg.max_epochs)
+        epochs of ``steps_per_epoch`` batches (``len(loader)``; synthetic: cfg.num_batches, numbered through the epochs so that a
+        resumed run draws the batches a straight run would), each through the fused training step with cfg.gradient_clip,
+        cfg.gradient_accumulation_steps and the scheduler's learning rate; after every epoch the scheduler step, the weights written back
+        into ``self.model``, ``<save_dir>/checkpoint/epoch_<e+1>.state`` (vpho_amd/checkpoint.py: what ``accel.save_state`` writes) and, with
+        ``eval_loader``, ``self.eval(eval_loader)``; after the last epoch ``<save_dir>/final_model.pt``.  ``cfg.checkpoint`` naming such a
+        state directory resumes it: optimiser, scheduler and generators restored, first epoch = the N of ``epoch_N.state``.
+        ``save_dir`` defaults to ``<output_dir>/<timestamp>_<mark>_train_<model>`` (base_trainer.py:52-55).  Returns a dict
+        (save_dir, start_epoch, epochs, per epoch the learning rate it ran at and its last loss line as floats)."""
+        from . import checkpoint as CK
+        from .train_step import DiffusionTrainStep
+        cfg = self.cfg
+        if getattr(cfg, 'train_scope', 'full') != 'full':
+            raise ValueError("Trainer.fit (--max_epochs) trains end to end: it needs --train_scope full; --train_scope score has no "
+                             "epochs, schedulers or checkpoints (use Trainer.run)")
+        epochs = cfg.max_epochs if epochs is None else epochs
+        if epochs is None or epochs < 1:
+            raise ValueError(f'Trainer.fit needs epochs >= 1 (--max_epochs), got {epochs}')
+        steps_per_epoch = cfg.num_batches if loader is None else len(loader)
+        A = max(1, int(getattr(cfg, 'gradient_accumulation_steps', 1)))
+        print_freq = max(1, int(getattr(cfg, 'print_freq', 500)))
+        if save_dir is None:
+            names = [os.path.join(cfg.output_dir, f"{time.strftime('%Y%m%d_%H%M%S', time.localtime())}_{cfg.mark}_train_{cfg.model}")]
+            if self.world > 1:
+                dist.broadcast_object_list(names, src=0)           # one directory for all ranks (base_trainer.py:53-54)
+            save_dir = names[0]
+        step = DiffusionTrainStep(self.model.state_dict(), self.device, assets=self.assets, optimizer=getattr(cfg, 'optimizer', 'adamw'))
+        sched = CK.make_scheduler(getattr(cfg, 'scheduler', 'exp'), cfg.base_learning_rate, self.world, getattr(cfg, 'gamma', 0.96),
+                                  getattr(cfg, 'lr_step', 5), epochs, steps_per_epoch)
+        start_epoch, seen = 0, 0
+        if CK.is_training_state(cfg.checkpoint):                   # the weights and running statistics came in through get_model
+            st = CK.load_state(cfg.checkpoint, self.rank)          # ... this restores the generators too
+            step.load_optimizer_state(st['optimizer'])
+            sched.load_state_dict(st['scheduler'])
+            sched.load_group(st['optimizer']['param_groups'][0])
+            start_epoch, seen = CK.epoch_of(cfg.checkpoint), st['step']
+            if self.rank == 0:
+                print(f'resumed {cfg.checkpoint}: epoch {start_epoch}, optimiser step {step.steps}, lr {sched.lr:.3e}')
+        out = dict(save_dir=save_dir, start_epoch=start_epoch, epochs=epochs, lr=[], losses=[])
+        for epoch in range(start_epoch, epochs):
+            if self.rank == 0:
+                print(f'Epoch: {epoch}/{epochs} | Learning Rate: {sched.lr:.3e}')
+            out['lr'].append(sched.lr)
+            step.hyper['beta1'] = sched.beta1
+            L = None
+            for i, (batch, gt_hand, gt_obj) in enumerate(self._train_batches(loader, steps_per_epoch, step.mano_head.mano, start=epoch * steps_per_epoch)):
+                L = step.step(batch, gt_hand, gt_obj, lr=sched.lr, gradient_clip=cfg.gradient_clip, fused=True,
+                              accumulation=(i % A, A, i == steps_per_epoch - 1) if A > 1 else None)
+                if self.rank == 0 and i % print_freq == 0:
+                    print(f'[{i:04d}/{steps_per_epoch}]| Loss ' + ' '.join(f'{k.replace("_loss", "")}:{float(v):.2e}' for k, v in L.items()))
+            out['losses'].append({k: float(v) for k, v in L.items()} if L is not None else {})
+            sched.step_epoch()
+            seen = step.steps
+            self.model.load_state_dict(step.state_dict(), strict=False)
+            opt = step.optimizer_state()
+            for g in opt['param_groups']:                          # the group as the reference's optimiser holds it after scheduler.step()
+                g.update(lr=sched.lr, betas=(sched.beta1, g['betas'][1]), **sched.group_extras())
+            CK.save_state(os.path.join(save_dir, 'checkpoint', f'epoch_{epoch + 1}.state'), self.model.state_dict(), opt, sched.state_dict(),
+                          self.rank, self.world, step=seen)
+            if eval_loader is not None:
+                self.eval(eval_loader)
+        self.model.load_state_dict(step.state_dict(), strict=False)
+        CK.save_model(os.path.join(save_dir, 'final_model.pt'), self.model.state_dict(), self.rank)
+        if self.rank == 0:
+            print(f'trained epochs {start_epoch}..{epochs} of {steps_per_epoch} batches: {save_dir}')
+        return out
 
     def run(self, n_batches=None, loader=None):
         """``Trainer.run`` (train_diff_hand_obj.py:126-153).  ``loader``: an iterable of Appendix-A batch dicts; default synthetic."""
@@ -167,7 +246,7 @@ class Trainer:
             lh, _ = hand.step(f['encoding_hand'], gt_hand, repeat_num=getattr(cfg, 'repeat_num', 20))
             lo, _ = obj.step(f['encoding_obj'], gt_obj, repeat_num=getattr(cfg, 'repeat_num', 20))
             losses.append((float(lh), float(lo)))
-            if self.rank == 0 and i % max(1, getattr(cfg, 'print_freq', 10)) == 0:
+            if self.rank == 0 and i % 10 == 0:
                 print(f'[{i:04d}/{n_batches}] diff_hand_loss {losses[-1][0]:.3e}  diff_obj_loss {losses[-1][1]:.3e}')
         self.model.load_state_dict({**hand.state_dict(), **obj.state_dict()}, strict=False)
         return losses
