@@ -10,10 +10,10 @@ import re
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # entry points with no wrapper named in a GPU test file, each with the reason it is acceptable.  The test fails on an entry that is no
-# longer needed, and none of the kernels of the leaf-test issues may ever be listed here (LEAF_KERNELS, CASCADE_KERNELS below).
+# longer needed, and none of the kernels of the leaf-test issues may ever be listed here (LEAF_KERNELS, CASCADE_KERNELS,
+# SPATIAL_BWD_KERNELS below).
 EXCEPTIONS = {
     'vpho_conv3x3_winograd_gate_nhwc_f32': 'gated Winograd input gradient of the training blocks: compared through the bottleneck / FPN / encoder training goldens only',
-    'vpho_maxpool_bwd_nhwc_f32': 'one-pass form without an ops wrapper: test_gpu_conv_backward.py calls it through ops._call against the workspace form',
     'vpho_mha_f32': 'alias of vpho_mha_dropout_f32 without a mask (no wrapper): that entry point is tested directly in test_gpu_train_physics.py',
     'vpho_mha_bwd_f32': 'alias of vpho_mha_bwd_ws_f32 for short sequences (no wrapper): that entry point is tested directly in test_gpu_train_physics.py',
 }
@@ -43,6 +43,12 @@ CASCADE_WRAPPERS = {'Aggregation.' + m for m in (
     'hand_phys_fuse')}
 # of these, the three that other GPU test files also call by name (weakly: equality with the engine, an error message, finiteness)
 CASCADE_CALLED_ELSEWHERE = {'vpho_obj_fuse_f64', 'vpho_hand_phys_score_f32', 'vpho_hand_phys_fuse_f32'}
+
+# the spatial backward entry points whose every launch form tests/test_gpu_spatial_bwd.py covers (maxpool_bwd reaches both pool entries:
+# the workspace form by default, the one-pass form with one_pass=True)
+SPATIAL_BWD_KERNELS = {'vpho_maxpool_bwd_nhwc_f32', 'vpho_maxpool_bwd_ws_nhwc_f32', 'vpho_resize_bilinear_bwd_nhwc_f32',
+                       'vpho_roi_align_bwd_nhwc_f32', 'vpho_align_heatmap_bwd_nhwc_f32'}
+SPATIAL_BWD_WRAPPERS = {'maxpool_bwd', 'resize_bilinear_bwd', 'roi_align_bwd', 'align_heatmap_bwd'}
 
 
 def _declared():
@@ -286,6 +292,23 @@ def test_without_the_cascade_file_the_gap_of_the_issue_is_back():
     the thirteen kernels that had no direct call come back as uncovered (the other three are called by name elsewhere)"""
     back = set(uncovered(skip=('test_gpu_cascade_leaves.py',))) - set(EXCEPTIONS)
     assert back == CASCADE_KERNELS - CASCADE_CALLED_ELSEWHERE, sorted(back ^ (CASCADE_KERNELS - CASCADE_CALLED_ELSEWHERE))
+
+
+def test_the_spatial_backward_kernels_are_never_an_exception_and_each_wrapper_is_called_directly():
+    assert not (set(EXCEPTIONS) & SPATIAL_BWD_KERNELS)
+    declared = set(_declared())
+    assert SPATIAL_BWD_KERNELS <= declared, sorted(SPATIAL_BWD_KERNELS - declared)
+    W = wrappers()
+    assert SPATIAL_BWD_WRAPPERS <= set(W), sorted(SPATIAL_BWD_WRAPPERS - set(W))
+    assert W['maxpool_bwd'] == {'vpho_maxpool_bwd_nhwc_f32', 'vpho_maxpool_bwd_ws_nhwc_f32'}
+    reached = set().union(*(W[w] for w in SPATIAL_BWD_WRAPPERS))
+    assert reached == SPATIAL_BWD_KERNELS, sorted(reached ^ SPATIAL_BWD_KERNELS)
+    src = open(os.path.join(ROOT, 'tests', 'test_gpu_spatial_bwd.py')).read()
+    calls = ops_calls_in(src, ops_classes(), ops_factories(), package_attributes())
+    assert SPATIAL_BWD_WRAPPERS <= calls, sorted(SPATIAL_BWD_WRAPPERS - calls)
+    tree = ast.parse(src)                                            # and the one-pass pool form is asked for by its keyword there
+    assert any(isinstance(n, ast.Call) and isinstance(n.func, ast.Attribute) and n.func.attr == 'maxpool_bwd'
+               and any(k.arg == 'one_pass' for k in n.keywords) for n in ast.walk(tree))
 
 
 _SAMPLE = '''

@@ -1710,9 +1710,13 @@ def lrelu_bwd(dy, y, slope):
     return dx
 
 
-def maxpool_bwd(x, dy, k, stride, pad):
+def maxpool_bwd(x, dy, k, stride, pad, one_pass=False):
+    """one_pass: the gather that scans every window itself (vpho_maxpool_bwd_nhwc_f32), also where the windows overlap"""
     N, H, W, Cc = x.shape
     dx = torch.empty_like(x)
+    if one_pass:
+        _call('vpho_maxpool_bwd_nhwc_f32', _f32(x), _f32(dy), I(N), I(H), I(W), I(Cc), I(k), I(stride), I(pad), _f32(dx))
+        return dx
     need = lib.vpho_maxpool_bwd_workspace_bytes(N, H, W, Cc, k, stride, pad)
     ws = torch.empty(need, dtype=torch.uint8, device=x.device) if need > 0 else None
     _call('vpho_maxpool_bwd_ws_nhwc_f32', _f32(x), _f32(dy), I(N), I(H), I(W), I(Cc), I(k), I(stride), I(pad), _f32(dx), _u8(ws))
