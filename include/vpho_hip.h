@@ -796,6 +796,14 @@ VPHO_API int vpho_grad_sqnorm_f64(const float* grad, long long n, double* out, v
  * 1 / (world_size * accumulation_steps).  The gradients are only read. */
 VPHO_API int vpho_optim_multi_f32(const void* segments, int n_segments, long long total_blocks, int kind, float lr, float beta1, float beta2, float eps,
                          float weight_decay, int step, float grad_scale, const double* sqnorm, float max_norm, void* stream);
+/* ---- moving average of the weights (ema.hip): ExponentialMovingAverage.update (lib/model/ema.py:25-44) for a list of tensors in one
+ * launch.  table: device array of n_tensors records { const float* param; float* shadow; long long n; long long first_block; } with
+ * first_block = running sum of ceil(n / 1024) over the preceding records, blocks = that sum over all records (the scheme of
+ * vpho_optim_multi_f32).  shadow -= one_minus_decay * (shadow - param) as torch evaluates it: three fp32 operations, each rounded
+ * once, never contracted; NaN and infinities propagate.  The caller forms one_minus_decay = 1 - min(decay, (1 + k) / (10 + k)) in
+ * double (k = number of updates, this one included) and rounds it once.  param is only read.  n_tensors == 0 (or blocks == 0): success
+ * without a launch; a negative count or a NULL table with n_tensors > 0: bad argument. */
+VPHO_API int vpho_ema_multi_f32(const void* table, int n_tensors, long long blocks, float one_minus_decay, void* stream);
 
 /* ---- physics branch of the training step (lib/model/VPHO.py:170-172,205-212 under loss.backward()) -------------------------------
  * backward of vpho_cross_tokens_f32 (cross_module.py:125-133: .view(bs,32,-1) of the projected maps, cat, + positional code):

@@ -153,22 +153,32 @@ def _cpu(obj):
     return obj
 
 
-def save_state(dir, model_state_dict, optimizer_state, scheduler_state, rank=0, world=1, step=0):
-    """``accel.save_state(dir)``: rank 0 writes the three shared files, every rank its RNG file, then a barrier"""
+def custom_file(index):
+    """accelerate's file of the index-th object passed to ``register_for_checkpointing`` (checkpointing.py: save_custom_state)"""
+    return f'custom_checkpoint_{index}.pkl'
+
+
+def save_state(dir, model_state_dict, optimizer_state, scheduler_state, rank=0, world=1, step=0, *, custom=None):
+    """``accel.save_state(dir)``: rank 0 writes the three shared files, every rank its RNG file, then a barrier.  ``custom``: the
+    ``state_dict()`` of every object registered for checkpointing, in order (the weights' moving average, vpho_amd/ema.py): rank 0 writes
+    ``custom_checkpoint_<i>.pkl`` as ``save_custom_state`` does; None or empty: no such file"""
     os.makedirs(dir, exist_ok=True)
     if rank == 0:
         from safetensors.torch import save_file
         save_file({k: v.clone() for k, v in _cpu(model_state_dict).items()}, os.path.join(dir, MODEL_FILE), metadata={'format': 'pt'})
         torch.save(_cpu(optimizer_state), os.path.join(dir, OPTIMIZER_FILE))
         torch.save(_cpu(scheduler_state), os.path.join(dir, SCHEDULER_FILE))
+        for i, state in enumerate(custom or ()):
+            torch.save(_cpu(state), os.path.join(dir, custom_file(i)))
     torch.save(rng_state(step), os.path.join(dir, rng_file(rank)))
     _barrier()
     return dir
 
 
 def load_state(dir, rank=0, restore_rng=True):
-    """-> dict(model=state_dict, optimizer=..., scheduler=..., rng=..., step=...) of a directory written by ``save_state`` or by
-    ``accel.save_state``; the process's generators are set from the rank's RNG file (a missing one is tolerated, as accelerate does)"""
+    """-> dict(model=state_dict, optimizer=..., scheduler=..., rng=..., step=..., custom=[...]) of a directory written by ``save_state``
+    or by ``accel.save_state``; the process's generators are set from the rank's RNG file (a missing one is tolerated, as accelerate
+    does); ``custom``: the content of ``custom_checkpoint_0.pkl``, ``_1`` ... (an empty list when the directory has none)"""
     if not is_training_state(dir):
         raise FileNotFoundError(f'{dir} is no training state: it needs {OPTIMIZER_FILE} (an accel.save_state directory, <save_dir>/checkpoint/epoch_N.state)')
     from safetensors.torch import load_file
@@ -179,7 +189,9 @@ def load_state(dir, rank=0, restore_rng=True):
         model = torch.load(os.path.join(dir, 'pytorch_model.bin'), map_location='cpu', weights_only=True)
     out = dict(model={(k[len('module.'):] if k.startswith('module.') else k): v for k, v in model.items()},
                optimizer=torch.load(os.path.join(dir, OPTIMIZER_FILE), map_location='cpu', weights_only=True),
-               scheduler=torch.load(os.path.join(dir, SCHEDULER_FILE), map_location='cpu', weights_only=False), rng=None, step=0)
+               scheduler=torch.load(os.path.join(dir, SCHEDULER_FILE), map_location='cpu', weights_only=False), rng=None, step=0, custom=[])
+    while os.path.exists(os.path.join(dir, custom_file(len(out['custom'])))):     # registered objects, as load_custom_state reads them
+        out['custom'].append(torch.load(os.path.join(dir, custom_file(len(out['custom']))), map_location='cpu', weights_only=False))
     rng = os.path.join(dir, rng_file(rank))
     if os.path.exists(rng):
         out['rng'] = torch.load(rng, map_location='cpu', weights_only=False)      # python / numpy generator states: plain pickled tuples

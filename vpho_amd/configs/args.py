@@ -77,6 +77,8 @@ class Config:
         self.lr_step = 5
         self.gradient_accumulation_steps = 1
         self.print_freq = 500
+        self.ema_rate = 0.0           # decay of a moving average of the weights kept by Trainer.fit (lib/model/ema.py); 0 = none
+        self.use_ema = False          # --mode eval / infer: the averaged weights of a --checkpoint state directory (custom_checkpoint_0.pkl)
         self.cross_dropout = 0.1      # the reference's nn.TransformerEncoderLayer / PositionalEncoding default (cross_module.py:64,104-107)
 
 
@@ -141,6 +143,8 @@ def _parser():
     p.add_argument('--lr_step', type=int, default=5)
     p.add_argument('--gradient_accumulation_steps', type=int, default=1)
     p.add_argument('--print_freq', type=int, default=500)
+    p.add_argument('--ema_rate', type=float, default=0.0)
+    p.add_argument('--use_ema', action='store_true')
     return p
 
 

@@ -1829,6 +1829,32 @@ class OptimList:
         torch.autograd.graph.increment_version([q[0] for q in self.keep])
 
 
+class EmaList:
+    """ExponentialMovingAverage.update (lib/model/ema.py:25-44) on a fixed list of (param, shadow) fp32 tensors as ONE launch
+    (vpho_ema_multi_f32): shadow -= one_minus_decay * (shadow - param), the three fp32 roundings of torch's own expression.  The
+    parameters are only read.  An empty list launches nothing."""
+    def __init__(self, pairs):
+        self.keep = pairs
+        rows, blk = [], 0
+        for p, s in pairs:
+            for t in (p, s):
+                _ptr(t, torch.float32)
+            if p.device != s.device:
+                raise VphoError(f'EmaList: parameter on {p.device}, shadow on {s.device}')
+            if p.numel() != s.numel():
+                raise VphoError(f'EmaList: a parameter of {p.numel()} elements with a shadow of {s.numel()}')
+            rows.append([p.data_ptr(), s.data_ptr(), p.numel(), blk])
+            blk += (p.numel() + 1023) // 1024
+        self.blocks, self.n = blk, len(rows)
+        self.table = torch.tensor(rows, dtype=torch.int64).to(pairs[0][0].device) if rows else None
+
+    def update(self, one_minus_decay):
+        if self.n == 0:
+            return
+        _call('vpho_ema_multi_f32', _ptr(self.table, torch.int64), I(self.n), LL(self.blocks), F(one_minus_decay))
+        torch.autograd.graph.increment_version([q[1] for q in self.keep])
+
+
 # ----------------------------------------------------------------------------------------------- physics branch (training)
 def cross_tokens_bwd(dtok, want_hand=True, want_obj=True):
     bs = dtok.shape[0]

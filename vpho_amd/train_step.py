@@ -24,9 +24,11 @@ from .train_score import ScoreTrainer, SUFFIXES
 
 class DiffusionTrainStep:
     def __init__(self, state_dict, device, lr=None, betas=(0.9, 0.999), eps=1e-8, weight_decay=None, loss_weights=None, assets=None,
-                 cross_dropout=None, optimizer='adamw'):
+                 cross_dropout=None, optimizer='adamw', ema=None):
         """``optimizer``: 'adamw' (train_diff_hand_obj.py:52; decoupled decay, default 0.01) or 'adam' (:54; L2 decay, default 0.0005) --
-        'adam' is stepped by the fused tail only (``step(..., fused=True)``)."""
+        'adam' is stepped by the fused tail only (``step(..., fused=True)``).
+        ``ema``: None, or the decay of an exponential moving average of every trained tensor (lib/model/ema.py: one shadow per master,
+        in the master's layout, moved by ONE launch after every optimiser update; ``ema_state`` / ``state_dict(ema=True)`` read it)."""
         from .checkpoint import optimizer_hyper
         self.dev = torch.device(device)
         sd = state_dict
@@ -68,6 +70,15 @@ class DiffusionTrainStep:
         from .conv_backward import DgradWeightCache
         self.dgrad_weights = DgradWeightCache()          # the input-gradient layouts of every convolution weight, rebuilt once per step
         self.wino_weights = ops.WinogradWeightBatch()    # ... and the Winograd transforms of the 3x3 weights (forward + input gradient)
+        # moving average (off: nothing is allocated and nothing more is launched).  The shadows keep the packed layout of their masters --
+        # padded input channels are zero in both and stay zero -- and ALL of them move after every update, as the reference's class
+        # moves every parameter, whether this step's losses reached it or not
+        self.ema = self.shadow = self._ema_list = None
+        if ema is not None:
+            from .ema import WeightEma
+            self.ema = WeightEma(float(ema))
+            self.shadow = {k: v.clone() for k, v in self.master.items()}
+            self._ema_list = ops.EmaList([(self.master[k], self.shadow[k]) for k in self.master])
 
     # ------------------------------------------------------------------------------------------------------------------
     def _register(self):
@@ -375,6 +386,7 @@ class DiffusionTrainStep:
                 self._adam = ops.AdamWList([(self.master[k], self.grad_view[k], self.m[k], self.v[k]) for k in live])
                 self._adam_key = key
             self._adam.step(self.steps, grad_scale=scale, **hyper)
+            self._ema_update()
             for k in live:
                 if self._repack[k] is not None:
                     self._repack[k](self.master[k])
@@ -417,6 +429,7 @@ class DiffusionTrainStep:
                 self._optim = ops.OptimList([(self.master[k], self.grad_view[k], self.m[k], self.v[k]) for k in live])
                 self._optim_key = key
             self._optim.step(self.steps, kind=self.optimizer, grad_scale=scale, sqnorm=sq, max_norm=float(clip) if clip > 0 else 0.0, **hyper)
+            self._ema_update()
             for k in live:
                 if self._repack[k] is not None:
                     self._repack[k](self.master[k])
@@ -424,6 +437,11 @@ class DiffusionTrainStep:
             self.wino_weights.refresh()
         self.stepped.update(live)
         return losses
+
+    def _ema_update(self):
+        """ExponentialMovingAverage.update (ema.py:25-44) after an optimiser update: the masters are only read"""
+        if self.ema is not None:
+            self._ema_list.update(self.ema.next_one_minus_decay())
 
     # ------------------------------------------------------------------------------------------------------------------
     def _ref_moment(self, name, t):
@@ -495,9 +513,45 @@ class DiffusionTrainStep:
             raise ValueError(f'optimizer state with different step counts per parameter ({sorted(steps)[:4]}...): one count is kept for all tensors')
         self.steps = steps.pop() if steps else 0
 
-    def state_dict(self):
-        """trained tensors + BatchNorm running statistics under the reference's names"""
-        out = {k: (self._ref_view(k).clone(memory_format=torch.contiguous_format) if k in self._conv_meta else v.clone()) for k, v in self.master.items()}
+    def _need_ema(self):
+        if self.ema is None:
+            raise ValueError('this training step keeps no moving average: construct it with ema=<decay> (--ema_rate)')
+
+    def ema_state(self, param_names=None):
+        """``ExponentialMovingAverage.state_dict()`` of this step (ema.py:85-87): decay, num_updates and ``shadow_params``, one CPU tensor
+        per trained tensor in the REFERENCE's shape, in the order of ``vpho_net(...).named_parameters()`` (``_order``, as
+        ``optimizer_state``; the views of ``_ref_moment``, padding dropped)"""
+        self._need_ema()
+        shapes = self._ref_shapes()
+        self.ema.shadow_params = [self._ref_moment(k, self.shadow[k]).reshape(shapes[k]).clone(memory_format=torch.contiguous_format).cpu()
+                                  for k in self._order(param_names) if k in self.master]
+        return dict(self.ema.state_dict())
+
+    @torch.no_grad()
+    def load_ema_state(self, state, param_names=None):
+        """the inverse of ``ema_state``: decay and num_updates as the reference's ``load_state_dict`` takes them (ema.py:89-92; a
+        num_updates of None = a fixed decay) and the shadows, reference layout, into the packed buffers"""
+        self._need_ema()
+        order = [k for k in self._order(param_names) if k in self.master]
+        if len(state['shadow_params']) != len(order):
+            raise ValueError(f"EMA state of {len(state['shadow_params'])} tensors, this step trains {len(order)}")
+        self.ema.load_state_dict(state)
+        for k, src in zip(order, self.ema.shadow_params):
+            src = src.to(self.dev)
+            if src.numel() != self._ref_moment(k, self.shadow[k]).numel():
+                raise ValueError(f'EMA shadow of {k}: {tuple(src.shape)}, the parameter is {self._ref_shapes()[k]}')
+            if k in self._conv_meta:
+                self._ref_moment(k, self.shadow[k]).copy_(src.reshape(self._conv_meta[k]))
+            else:
+                self.shadow[k].copy_(src.reshape(self.shadow[k].shape))
+
+    def state_dict(self, ema=False):
+        """trained tensors + BatchNorm running statistics under the reference's names.  ``ema=True``: the trained tensors are their moving
+        averages (what ``copy_to`` would put into the module, ema.py:47-58); running statistics and the Fourier ``W`` stay the live ones"""
+        if ema:
+            self._need_ema()
+        src = self.shadow if ema else self.master
+        out = {k: (self._ref_moment(k, v).clone(memory_format=torch.contiguous_format) if k in self._conv_meta else v.clone()) for k, v in src.items()}
         for tr in self.score.values():
             out[f'{tr.prefix}.t_encoder.0.W'] = tr.fourier_W.clone()
 

@@ -48,6 +48,25 @@ def load_checkpoint_state_dict(path):
     return sd, path
 
 
+def ema_state_dict(checkpoint, state_dict, param_names):
+    """``--use_ema``: the state_dict of ``--checkpoint`` with its trained tensors replaced by their moving averages.  The averages live in
+    the state DIRECTORY a run with ``--ema_rate`` wrote (``custom_checkpoint_0.pkl``, shadow i = parameter i of
+    ``vpho_net(...).named_parameters()``); ``final_model_ema.pt`` already IS the averaged model and is passed as it stands."""
+    from . import checkpoint as CK
+    from .ema import CUSTOM_INDEX, overlay
+    name = CK.custom_file(CUSTOM_INDEX)
+    if not checkpoint:
+        raise ValueError(f'--use_ema needs --checkpoint <save_dir>/checkpoint/epoch_N.state (a state directory holding {name})')
+    if not os.path.isdir(checkpoint):
+        raise ValueError(f'--use_ema reads the moving average from a state directory ({name}), but --checkpoint {checkpoint} is a plain '
+                         f'state_dict file: pass final_model_ema.pt itself as --checkpoint, without --use_ema')
+    path = os.path.join(checkpoint, name)
+    if not os.path.exists(path):
+        raise FileNotFoundError(f'--use_ema: {checkpoint} holds no {name} (written by a run with --ema_rate > 0); it contains: '
+                                f'{sorted(os.listdir(checkpoint))[:20]}')
+    return overlay(state_dict, torch.load(path, map_location='cpu', weights_only=True), param_names), path
+
+
 def synthetic_mano_targets(mano, gt_rot6d, gt_shape, is_right):
     """ground-truth vertices / joints of a synthetic hand pose: the MANO forward of the training kernel with zero loss weights"""
     bs = gt_rot6d.shape[0]
@@ -90,8 +109,13 @@ class Trainer:
     def get_model(self):
         from .model.VPHO import vpho_net
         model = vpho_net(self.assets)
+        use_ema = bool(getattr(self.cfg, 'use_ema', False))
+        if use_ema and not self.cfg.checkpoint:
+            ema_state_dict(self.cfg.checkpoint, None, None)        # raises: nothing to take an average from
         if self.cfg.checkpoint:
             sd, path = load_checkpoint_state_dict(self.cfg.checkpoint)
+            if use_ema:                                            # the averaged weights over the live ones, by parameter order
+                sd, path = ema_state_dict(self.cfg.checkpoint, sd, [k for k, p in model.named_parameters() if p.requires_grad])
             missing, unexpected = model.load_state_dict(sd, strict=False)      # base_trainer.py:81-83 (strict=False)
             if self.rank == 0:
                 print(f'loaded {path}: {len(missing)} missing, {len(unexpected)} unexpected keys')
@@ -161,8 +185,13 @@ class Trainer:
         ``eval_loader``, ``self.eval(eval_loader)``; after the last epoch ``<save_dir>/final_model.pt``.  ``cfg.checkpoint`` naming such a
         state directory resumes it: optimiser, scheduler and generators restored, first epoch = the N of ``epoch_N.state``.
         ``save_dir`` defaults to ``<output_dir>/<timestamp>_<mark>_train_<model>`` (base_trainer.py:52-55).  Returns a dict
-        (save_dir, start_epoch, epochs, per epoch the learning rate it ran at and its last loss line as floats)."""
+        (save_dir, start_epoch, epochs, per epoch the learning rate it ran at and its last loss line as floats).
+        ``cfg.ema_rate`` > 0 keeps the reference's moving average of the weights (lib/model/ema.py; vpho_amd/ema.py): every state directory
+        gets ``custom_checkpoint_0.pkl`` (accelerate's file of a registered object) beside the live ``model.safetensors``, a resume restores
+        it (a state directory without one starts the average from the restored weights with 0 updates), ``eval_loader`` is evaluated with
+        the AVERAGED weights, ``<save_dir>/final_model_ema.pt`` is written next to ``final_model.pt`` and the dict says ``ema=True``."""
         from . import checkpoint as CK
+        from .ema import CUSTOM_INDEX
         from .train_step import DiffusionTrainStep
         cfg = self.cfg
         if getattr(cfg, 'train_scope', 'full') != 'full':
@@ -179,7 +208,12 @@ class Trainer:
             if self.world > 1:
                 dist.broadcast_object_list(names, src=0)           # one directory for all ranks (base_trainer.py:53-54)
             save_dir = names[0]
-        step = DiffusionTrainStep(self.model.state_dict(), self.device, assets=self.assets, optimizer=getattr(cfg, 'optimizer', 'adamw'))
+        if getattr(cfg, 'use_ema', False):
+            raise ValueError('--use_ema loads the averaged weights for --mode eval / infer; training keeps its average with --ema_rate')
+        ema_rate = float(getattr(cfg, 'ema_rate', 0.0) or 0.0)
+        ema = ema_rate > 0                                         # --ema_rate 0: nothing allocated, launched or written
+        step = DiffusionTrainStep(self.model.state_dict(), self.device, assets=self.assets, optimizer=getattr(cfg, 'optimizer', 'adamw'),
+                                  ema=ema_rate if ema else None)
         sched = CK.make_scheduler(getattr(cfg, 'scheduler', 'exp'), cfg.base_learning_rate, self.world, getattr(cfg, 'gamma', 0.96),
                                   getattr(cfg, 'lr_step', 5), epochs, steps_per_epoch)
         start_epoch, seen = 0, 0
@@ -191,7 +225,15 @@ class Trainer:
             start_epoch, seen = CK.epoch_of(cfg.checkpoint), st['step']
             if self.rank == 0:
                 print(f'resumed {cfg.checkpoint}: epoch {start_epoch}, optimiser step {step.steps}, lr {sched.lr:.3e}')
+            if ema and len(st['custom']) > CUSTOM_INDEX:
+                step.load_ema_state(st['custom'][CUSTOM_INDEX])   # decay and num_updates come with it (ema.py:89-92)
+                if self.rank == 0:
+                    print(f'resumed the moving average: decay {step.ema.decay}, {step.ema.num_updates} updates')
+            elif ema and self.rank == 0:                           # a checkpoint of the reference, or of a run without --ema_rate
+                print(f'{cfg.checkpoint} holds no {CK.custom_file(CUSTOM_INDEX)}: the moving average starts from the restored weights, 0 updates')
         out = dict(save_dir=save_dir, start_epoch=start_epoch, epochs=epochs, lr=[], losses=[])
+        if ema:
+            out['ema'] = True
         for epoch in range(start_epoch, epochs):
             if self.rank == 0:
                 print(f'Epoch: {epoch}/{epochs} | Learning Rate: {sched.lr:.3e}')
@@ -211,10 +253,21 @@ class Trainer:
             for g in opt['param_groups']:                          # the group as the reference's optimiser holds it after scheduler.step()
                 g.update(lr=sched.lr, betas=(sched.beta1, g['betas'][1]), **sched.group_extras())
             CK.save_state(os.path.join(save_dir, 'checkpoint', f'epoch_{epoch + 1}.state'), self.model.state_dict(), opt, sched.state_dict(),
-                          self.rank, self.world, step=seen)
+                          self.rank, self.world, step=seen, custom=[step.ema_state()] if ema else None)
             if eval_loader is not None:
+                if ema:
+                    # the averaged weights are the ones evaluated.  The step's masters may BE the module's tensors (a packed 1x1 weight
+                    # is a view of the parameter it was built from), so the live values are copied out first and put back right after
+                    live = step.state_dict()
+                    self.model.load_state_dict(step.state_dict(ema=True), strict=False)
                 self.eval(eval_loader)
+                if ema:
+                    self.model.load_state_dict(live, strict=False)
         self.model.load_state_dict(step.state_dict(), strict=False)
+        if ema:                                                    # the module's state_dict with the averages in place of the trained tensors
+            averaged = dict(self.model.state_dict())
+            averaged.update({k: v.reshape(averaged[k].shape) for k, v in step.state_dict(ema=True).items()})
+            CK.save_model(os.path.join(save_dir, 'final_model_ema.pt'), averaged, self.rank)
         CK.save_model(os.path.join(save_dir, 'final_model.pt'), self.model.state_dict(), self.rank)
         if self.rank == 0:
             print(f'trained epochs {start_epoch}..{epochs} of {steps_per_epoch} batches: {save_dir}')
