@@ -804,6 +804,33 @@ VPHO_API int vpho_optim_multi_f32(const void* segments, int n_segments, long lon
  * double (k = number of updates, this one included) and rounds it once.  param is only read.  n_tensors == 0 (or blocks == 0): success
  * without a launch; a negative count or a NULL table with n_tensors > 0: bad argument. */
 VPHO_API int vpho_ema_multi_f32(const void* table, int n_tensors, long long blocks, float one_minus_decay, void* stream);
+/* ---- frames in (frames.hip): the per-image work of the reference's Dataset.__getitem__, lib/dataset/dexycb6.py:339-469 -------------
+ * vpho_frame_patch_f32: frames (n,H,W,3) uint8 -> out (n,3,P,P) fp32, the `rgb` of the batch schema.  Replaces cv2.warpAffine(rgb,
+ * rotmat_2d[:2], (P,P), INTER_CUBIC) (dexycb6.py:345), the RGB shift / brightness / saturation of image_augmentor.run_color (:389-391,
+ * base.py:381-382), the left-hand mirror rgb_patch[:, ::-1] (:398-399), normalize_rgb (:442, base.py:97-102) and timm's RandomErasing
+ * mode 'pixel' (:444).  minv (n,6) fp64: rows 0-1 of the INVERSE of rotmat_2d, patch (x, y, 1) -> frame; the coordinate, its floor and
+ * fraction are fp64, the Keys weights (A = -0.75, taps floor-1 .. floor+2, outside the frame 0) and the sums fp32, rows first; the sum is
+ * rounded to nearest (ties to even) and clamped to [0, 255].  OpenCV's 1/32-pixel coordinate grid and 15-bit weights are NOT reproduced.
+ * colour (n,5) fp32 or NULL: dr, dg, db, brightness b, saturation s -- v + d, then v * b, then s * v + (1 - s) * gray with gray =
+ * round(0.299 R + 0.587 G + 0.114 B); every stage ends rounded and clamped.  flip (n) uint8 or NULL: non-zero writes patch column x at
+ * P - 1 - x.  Then (v / 255 - mean) / std in three fp32 operations (ImageNet mean / std).  erase (n,4,4) int32 or NULL: up to four
+ * rectangles x0, y0, x1, y1 (half open, OUTPUT coordinates, x1 <= x0 = none) filled with N(0,1): Philox4x32-10, counter (y * P + x, 0, 0,
+ * 0), key (n,2) uint32; a word's upper 23 bits give u = (k + 0.5) / 2^23; (w0, w1) and (w2, w3) are two Box-Muller pairs
+ * sqrt(-2 ln u1) (cos, sin)(2 pi u2); channels 0, 1, 2 take cos, sin of the first pair and cos of the second.  n == 0: success
+ * without a launch.  frames are only read. */
+VPHO_API int vpho_frame_patch_f32(const unsigned char* frames, int n, int H, int W, const double* minv, const float* colour, const unsigned char* flip,
+                         const int* erase, const unsigned int* key, int P, float* out, void* stream);
+/* vpho_heatmap_targets_f32: out (n,J,S,S) fp32 heat-map targets of lib/utils/misc_fn.py:285-385, no intermediate map.  pts (n,J,2) fp64
+ * patch coordinates; g (G,G) fp32: the reference's Gaussian table rounded to fp32 (what it stores into its fp32 map); sigma as the
+ * generator holds it.  adaptive == 0, HeatmapGenerator.get_heatmap (:324-330, :297-322): box (n,4) fp64 = x0, y0, max_wh, unused;
+ * p = (pt - box[:2]) / max_wh * (S - 1), + 1 in x where left (n) uint8 (NULL: nowhere) is non-zero; truncated toward zero, a joint outside
+ * [0,S) gives a zero map; the table lies with its corner at rint(x - 3 sigma - 1) (ties to even, as np.round), up to rint(x + 3 sigma + 2),
+ * clipped to the map.  adaptive != 0, AdaptiveHeatmapGenerator.__call__ (:372-385): box = x0, y0, w, h; res (n,2) int32 = the tight map's
+ * width and height (>= 1: the caller checks); p = (pt - box[:2]) * res / (w, h) in that order; the tight map's stamp is evaluated at the
+ * four taps of a half-pixel-centre bilinear resize to S x S (source (d + 0.5) * res / S - 0.5, taps clamped to the edge: the convention of
+ * cv2.resize INTER_LINEAR), weights and sums fp32; values below gmin (the table's fp64 minimum) become 0.  n == 0: no launch. */
+VPHO_API int vpho_heatmap_targets_f32(const double* pts, const double* box, const int* res, const unsigned char* left, const float* g, int G, double sigma,
+                             double gmin, int n, int J, int S, int adaptive, float* out, void* stream);
 
 /* ---- physics branch of the training step (lib/model/VPHO.py:170-172,205-212 under loss.backward()) -------------------------------
  * backward of vpho_cross_tokens_f32 (cross_module.py:125-133: .view(bs,32,-1) of the projected maps, cat, + positional code):

@@ -36,7 +36,7 @@ class Config:
         self.patch_size = 256
         self.batch_size = 64
         self.eval_batch_size = 32
-        self.num_batches = 4          # synthetic evaluation only (no dataset in this build)
+        self.num_batches = 4          # synthetic batches / synthetic frames (--frame_source synthetic); a frame directory has its own length
         self.model = 'vpho_net'
         self.sde_mode = 've'
         self.repeat_num = 20
@@ -79,6 +79,24 @@ class Config:
         self.print_freq = 500
         self.ema_rate = 0.0           # decay of a moving average of the weights kept by Trainer.fit (lib/model/ema.py); 0 = none
         self.use_ema = False          # --mode eval / infer: the averaged weights of a --checkpoint state directory (custom_checkpoint_0.pkl)
+        # frames in (vpho_amd/frames.py; lib/configs/args.py:156-199): 'none' = the synthetic batch dicts, nothing of the front end is imported
+        self.frame_source = 'none'    # none | synthetic | a FrameDirectory path
+        self.bbox_scale_factor = 1.2
+        self.center_jittering = 0.2
+        self.scale_factor = 0.2
+        self.max_rot = 30.0
+        self.rot_prob = 1.0
+        self.RGB_shift_prob = 0.5
+        self.shift_limit = (-20.0, 20.0)
+        self.color_jitter_prob = 0.5
+        self.brightness = (0.6, 1.3)
+        self.saturation = (0.6, 1.3)
+        self.random_erasing_prob = 0.5
+        self.random_erasing_min_area = 0.02
+        self.random_erasing_max_area = 0.2
+        self.random_erasing_max_count = 1
+        self.heatmap_hand_sigma = 2.0
+        self.heatmap_obj_sigma = 2.0
         self.cross_dropout = 0.1      # the reference's nn.TransformerEncoderLayer / PositionalEncoding default (cross_module.py:64,104-107)
 
 
@@ -145,6 +163,23 @@ def _parser():
     p.add_argument('--print_freq', type=int, default=500)
     p.add_argument('--ema_rate', type=float, default=0.0)
     p.add_argument('--use_ema', action='store_true')
+    p.add_argument('--frame_source', type=str, default='none')
+    p.add_argument('--bbox_scale_factor', type=float, default=1.2)
+    p.add_argument('--center_jittering', type=float, default=0.2)
+    p.add_argument('--scale_factor', type=float, default=0.2)
+    p.add_argument('--max_rot', type=float, default=30.0)
+    p.add_argument('--rot_prob', type=float, default=1.0)
+    p.add_argument('--RGB_shift_prob', type=float, default=0.5)
+    p.add_argument('--shift_limit', type=float, nargs=2, default=(-20.0, 20.0))          # the reference's default pair, settable as two numbers
+    p.add_argument('--color_jitter_prob', type=float, default=0.5)
+    p.add_argument('--brightness', type=float, nargs=2, default=(0.6, 1.3))
+    p.add_argument('--saturation', type=float, nargs=2, default=(0.6, 1.3))
+    p.add_argument('--random_erasing_prob', type=float, default=0.5)
+    p.add_argument('--random_erasing_min_area', type=float, default=0.02)
+    p.add_argument('--random_erasing_max_area', type=float, default=0.2)
+    p.add_argument('--random_erasing_max_count', type=int, default=1)
+    p.add_argument('--heatmap_hand_sigma', type=float, default=2.0)
+    p.add_argument('--heatmap_obj_sigma', type=float, default=2.0)
     return p
 
 

@@ -1855,6 +1855,50 @@ class EmaList:
         torch.autograd.graph.increment_version([q[1] for q in self.keep])
 
 
+# ----------------------------------------------------------------------------------------------- frames in (frames.hip)
+def frame_patch(frames, minv, patch, colour=None, flip=None, erase=None, key=None, out=None):
+    """(n,H,W,3) uint8 frames -> (n,3,patch,patch) fp32 normalised crops (vpho_frame_patch_f32: dexycb6.py:345,389-399,442-444).
+    ``minv`` (n,6) fp64: rows 0-1 of the inverse crop matrix (patch -> frame).  Optional, per sample: ``colour`` (n,5) fp32 dr, dg, db,
+    brightness, saturation; ``flip`` (n) uint8; ``erase`` (n,4,4) int32 rectangles x0, y0, x1, y1 in output coordinates with ``key``
+    (n,2) int32 holding the two uint32 words of the Philox key.  n == 0 launches nothing."""
+    if frames.dim() != 4 or frames.shape[3] != 3:
+        raise VphoError(f'frame_patch: frames of shape {tuple(frames.shape)}, expected (n, H, W, 3)')
+    n, H, W, _ = frames.shape
+    for name, t, shape in (('minv', minv, (n, 6)), ('colour', colour, (n, 5)), ('flip', flip, (n,)), ('erase', erase, (n, 4, 4)), ('key', key, (n, 2))):
+        if t is not None and tuple(t.shape) != shape:
+            raise VphoError(f'frame_patch: {name} of shape {tuple(t.shape)}, expected {shape}')
+    if erase is not None and key is None:
+        raise VphoError('frame_patch: erase rectangles need a Philox key')
+    if out is None:
+        out = _new((n, 3, patch, patch), frames)
+    elif tuple(out.shape) != (n, 3, patch, patch):
+        raise VphoError(f'frame_patch: out of shape {tuple(out.shape)}, expected {(n, 3, patch, patch)}')
+    _call('vpho_frame_patch_f32', _u8(frames), I(n), I(H), I(W), _f64(minv), _f32(colour), _u8(flip), None if erase is None else _i32(erase),
+          None if key is None else _i32(key), I(patch), _f32(out))
+    return out
+
+
+def heatmap_targets(pts, box, g, sigma, gmin, size, res=None, left=None, out=None):
+    """(n,J,2) fp64 patch points -> (n,J,size,size) fp32 heat-map targets (vpho_heatmap_targets_f32, misc_fn.py:285-385).  ``g`` (G,G) fp32
+    Gaussian table, ``gmin`` its fp64 minimum.  ``res`` None: HeatmapGenerator.get_heatmap with ``box`` (n,4) fp64 = x0, y0, max_wh, unused
+    and ``left`` (n) uint8; ``res`` (n,2) int32: AdaptiveHeatmapGenerator.__call__ with ``box`` = x0, y0, w, h.  n == 0 launches nothing."""
+    if pts.dim() != 3 or pts.shape[2] != 2:
+        raise VphoError(f'heatmap_targets: points of shape {tuple(pts.shape)}, expected (n, J, 2)')
+    n, J, _ = pts.shape
+    for name, t, shape in (('box', box, (n, 4)), ('res', res, (n, 2)), ('left', left, (n,))):
+        if t is not None and tuple(t.shape) != shape:
+            raise VphoError(f'heatmap_targets: {name} of shape {tuple(t.shape)}, expected {shape}')
+    if g.dim() != 2 or g.shape[0] != g.shape[1]:
+        raise VphoError(f'heatmap_targets: a Gaussian table of shape {tuple(g.shape)}')
+    if out is None:
+        out = _new((n, J, size, size), pts)
+    elif tuple(out.shape) != (n, J, size, size):
+        raise VphoError(f'heatmap_targets: out of shape {tuple(out.shape)}, expected {(n, J, size, size)}')
+    _call('vpho_heatmap_targets_f32', _f64(pts), _f64(box), None if res is None else _i32(res), _u8(left), _f32(g), I(g.shape[0]), C.c_double(sigma),
+          C.c_double(gmin), I(n), I(J), I(size), I(0 if res is None else 1), _f32(out))
+    return out
+
+
 # ----------------------------------------------------------------------------------------------- physics branch (training)
 def cross_tokens_bwd(dtok, want_hand=True, want_obj=True):
     bs = dtok.shape[0]
