@@ -11,7 +11,6 @@
 
 namespace {
 
-using vpho::sym3_eig;
 using vpho::wave_sum;
 using vpho::similarity_from_cov;
 
@@ -56,35 +55,11 @@ __global__ __launch_bounds__(256) void hand_metrics_kernel(const float* __restri
     double H[3][3];
     for (int k = 0; k < 9; ++k) H[k / 3][k % 3] = block_sum(h[k], red) / n;
     const double varA = block_sum(va, red) / n;
-    if (tid == 0) {
-        // H = U S V^T; eigen of H^T H gives V and S^2, U = H V S^-1;  R = V U^T (numpy: Vh.T @ U.T)
-        double M[3][3], w[3], V[3][3], U[3][3], s[3];
-        for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) { M[i][j] = 0; for (int k = 0; k < 3; ++k) M[i][j] += H[k][i] * H[k][j]; }
-        sym3_eig(M, w, V);
-        for (int k = 0; k < 3; ++k) s[k] = sqrt(w[k] > 0 ? w[k] : 0.0);
-        for (int k = 0; k < 3; ++k) {
-            double u[3] = {0, 0, 0};
-            for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) u[i] += H[i][j] * V[j][k];
-            const double nu = sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
-            if (k < 2 || nu > 1e-12 * (s[0] + 1e-300)) for (int i = 0; i < 3; ++i) U[i][k] = u[i] / (nu > 0 ? nu : 1.0);
-            else {   // rank-deficient H: complete the basis (sign fixed by the determinant rule below)
-                U[0][2] = U[1][0] * U[2][1] - U[2][0] * U[1][1];
-                U[1][2] = U[2][0] * U[0][1] - U[0][0] * U[2][1];
-                U[2][2] = U[0][0] * U[1][1] - U[1][0] * U[0][1];
-            }
-        }
-        auto build = [&](double R[3][3]) { for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) { R[i][j] = 0; for (int k = 0; k < 3; ++k) R[i][j] += V[i][k] * U[j][k]; } };
-        double R[3][3];
-        build(R);
-        const double det = R[0][0] * (R[1][1] * R[2][2] - R[1][2] * R[2][1]) - R[0][1] * (R[1][0] * R[2][2] - R[1][2] * R[2][0]) +
-                           R[0][2] * (R[1][0] * R[2][1] - R[1][1] * R[2][0]);
-        if (det < 0) { s[2] = -s[2]; for (int i = 0; i < 3; ++i) V[i][2] = -V[i][2]; build(R); }
-        const double c = (s[0] + s[1] + s[2]) / varA;
-        for (int i = 0; i < 3; ++i) {
-            double t = cB[i];
-            for (int j = 0; j < 3; ++j) { T[i * 3 + j] = c * R[i][j]; t -= c * R[i][j] * cA[j]; }
-            T[9 + i] = t;
-        }
+    if (tid == 0) {   // the one solve of procrustes.h, as in the multi-hypothesis and the benchmark kernels
+        double Tl[12];
+        similarity_from_cov(H, cA, cB, varA, Tl);
+#pragma unroll
+        for (int k = 0; k < 12; ++k) T[k] = Tl[k];
     }
     __syncthreads();
     double sp = 0;

@@ -54,8 +54,8 @@ __device__ inline double wave_sum(double v) {
     return v;
 }
 
-// similarity transform of rigid_transform_3D_AtoB (transform_fn.py:43-58) from the centred cross-covariance H, as in
-// hand_metrics_kernel: eigen of H^T H gives V and S^2, U = H V S^-1, R = V U^T with the reflection fix; T = [c R | cB - c R cA]
+// similarity transform of rigid_transform_3D_AtoB (transform_fn.py:43-58) from the centred cross-covariance H, the one solve of all
+// three PA kernels: eigen of H^T H gives V and S^2, U from H V, R = V U^T with the reflection fix; T = [c R | cB - c R cA]
 __device__ inline void similarity_from_cov(const double H[3][3], const double cA[3], const double cB[3], double varA, double T[12]) {
     double M[3][3], w[3], V[3][3], U[3][3], s[3];
 #pragma unroll
@@ -65,17 +65,40 @@ __device__ inline void similarity_from_cov(const double H[3][3], const double cA
     sym3_eig(M, w, V);
 #pragma unroll
     for (int k = 0; k < 3; ++k) s[k] = sqrt(w[k] > 0 ? w[k] : 0.0);
+    // U is orthonormal by construction.  Jacobi on H^T H separates v2 from v3 only to eps * w1 / (w2 - w3): with a rank-1 H (s2/s1 ~ 1e-7,
+    // a collinear ground truth) H v3 keeps a component along u2 far above any threshold on |H v3|, and normalising it gave a U with two
+    // parallel columns.  So: U0 = H v1 / |H v1|; U1 = H v2 orthogonalised against U0 (any perpendicular if nothing is left of it);
+    // U2 = +-(U0 x U1), the sign from H v3 where |H v3| is significant (it decides a reflection), else by the determinant rule below.
+    double u[3][3], nu[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        double u[3] = {0, 0, 0};
-        for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) u[i] += H[i][j] * V[j][k];
-        const double nu = sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
-        if (k < 2 || nu > 1e-12 * (s[0] + 1e-300)) for (int i = 0; i < 3; ++i) U[i][k] = u[i] / (nu > 0 ? nu : 1.0);
-        else {   // rank-deficient H: complete the basis (sign fixed by the determinant rule below)
-            U[0][2] = U[1][0] * U[2][1] - U[2][0] * U[1][1];
-            U[1][2] = U[2][0] * U[0][1] - U[0][0] * U[2][1];
-            U[2][2] = U[0][0] * U[1][1] - U[1][0] * U[0][1];
-        }
+#pragma unroll
+        for (int i = 0; i < 3; ++i) { u[i][k] = 0; for (int j = 0; j < 3; ++j) u[i][k] += H[i][j] * V[j][k]; }
+        nu[k] = sqrt(u[0][k] * u[0][k] + u[1][k] * u[1][k] + u[2][k] * u[2][k]);
+    }
+    const double tiny = 1e-12 * (s[0] + 1e-300);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) U[i][0] = u[i][0] / (nu[0] > 0 ? nu[0] : 1.0);
+    const double d01 = U[0][0] * u[0][1] + U[1][0] * u[1][1] + U[2][0] * u[2][1];
+    double g[3] = {u[0][1] - d01 * U[0][0], u[1][1] - d01 * U[1][0], u[2][1] - d01 * U[2][0]};
+    double ng = sqrt(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]);
+    if (!(ng > tiny)) {   // rank 1 to rounding: U0 x e, e the axis U0 is least along
+        const double a0 = fabs(U[0][0]), a1 = fabs(U[1][0]), a2 = fabs(U[2][0]);
+        const bool p0 = a0 <= a1 && a0 <= a2, p1 = !p0 && a1 <= a2;
+        const double e0 = p0 ? 1.0 : 0.0, e1 = p1 ? 1.0 : 0.0, e2 = (p0 || p1) ? 0.0 : 1.0;
+        g[0] = U[1][0] * e2 - U[2][0] * e1;
+        g[1] = U[2][0] * e0 - U[0][0] * e2;
+        g[2] = U[0][0] * e1 - U[1][0] * e0;
+        ng = sqrt(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]);
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) U[i][1] = g[i] / (ng > 0 ? ng : 1.0);
+    {
+        double x[3] = {U[1][0] * U[2][1] - U[2][0] * U[1][1], U[2][0] * U[0][1] - U[0][0] * U[2][1], U[0][0] * U[1][1] - U[1][0] * U[0][1]};
+        const double nx = sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
+        const double sgn = (nu[2] > tiny && u[0][2] * x[0] + u[1][2] * x[1] + u[2][2] * x[2] < 0) ? -1.0 : 1.0;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) U[i][2] = sgn * (x[i] / (nx > 0 ? nx : 1.0));
     }
     auto build = [&](double R[3][3]) {
 #pragma unroll
