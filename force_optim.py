@@ -3,7 +3,10 @@ optimisation over hand-object pairs.  No data set in this build -> synthetic pai
 random contact maps); pairs are sharded over the ranks of one node (one process per GPU), no collective on the data path.
 
     python force_optim.py --pairs 10000 [--batch_size 64]            # or torch.distributed.run --nproc-per-node N ...
-Prints one JSON line per run (rank 0): pairs/s over all ranks, final mean losses."""
+Prints one JSON line per run (rank 0): pairs/s over all ranks, final mean losses.
+
+    python force_optim.py --frame_source synthetic|DIR [--num_frames N] [--out PATH]
+labels a frame source from its annotations instead (contact, grasp and pseudo-forces: label_frames) and writes physics_labels.npz."""
 import argparse
 import json
 import os
@@ -20,10 +23,23 @@ def main():
     p.add_argument('--iters', type=int, default=3000)
     p.add_argument('--phase1', type=int, default=300)
     p.add_argument('--gpus', type=int, default=int(os.environ.get('WORLD_SIZE', '1')))
+    # labels for a frame source instead of the synthetic pairs (label_frames below): 'synthetic' or a FrameDirectory path
+    p.add_argument('--frame_source', type=str, default='none')
+    p.add_argument('--num_frames', type=int, default=None)
+    p.add_argument('--out', type=str, default=None)
     args = p.parse_args()
+    if args.frame_source != 'none':
+        if args.gpus != 1:
+            p.error('--frame_source labels one source on one GPU: run it with --gpus 1')
+        if args.frame_source == 'synthetic' and not args.out:
+            p.error('--frame_source synthetic has no directory to write into: give --out PATH')
+        if not 1 <= args.batch_size <= 64:
+            p.error('--batch_size: the force optimiser takes batches of 1 .. 64 pairs')
     from vpho_amd.launch import maybe_spawn, world_from_env
     maybe_spawn(args.gpus)             # N > 1 from a bare shell: start the N rank processes (before any GPU call)
     sys.argv = sys.argv[:1]
+    if args.frame_source != 'none':
+        return label_frames(args)
     import torch
     import torch.distributed as dist
     from vpho_amd import ops
@@ -94,6 +110,74 @@ def main():
                           'seconds': float(dt.item()), 'mean_losses_force_gravity_moment_dist': losses, 'data': 'synthetic'}))
     if world > 1:
         dist.destroy_process_group()
+
+
+CHAIN_BATCH = 256
+
+
+def label_frames(args):
+    """--frame_source synthetic|DIR: the physics labels of every frame of the source, from its annotations alone
+    (vpho_amd/physics_labels.py).  The pipeline runs in evaluation mode (no draws: the reference sets ``trainset.is_train = False`` for this
+    pass), the contact chain per loader batch, the pseudo-force optimisation over all pairs at the end: the full batches of --batch_size
+    in one call, a remainder as a second one.  Writes DIR/physics_labels.npz (or --out) and prints one JSON line."""
+    import numpy as np
+    import torch
+    from vpho_amd.configs.args import cfg
+    from vpho_amd.assets import load_assets
+    from vpho_amd import frames as FR
+    from vpho_amd.physics_labels import PhysicsLabeler
+
+    torch.cuda.set_device(0)
+    dev = torch.device('cuda', 0)
+    assets = load_assets(cfg.asset_root)
+    if args.frame_source == 'synthetic':
+        source = FR.synthetic_frames(args.num_frames if args.num_frames is not None else 4 * args.batch_size, assets, seed=int(cfg.random_seed))
+        path = args.out
+    else:
+        source = FR.FrameDirectory(args.frame_source)
+        path = args.out or os.path.join(args.frame_source, FR.LABEL_FILE)
+    n = len(source) if args.num_frames is None else min(int(args.num_frames), len(source))
+    if n < 1:
+        raise SystemExit(f'force_optim.py: {args.frame_source} holds no frame to label')
+
+    class Head:                                            # the first n frames of the source
+        def __len__(self):
+            return n
+
+        def __getitem__(self, i):
+            return source[i]
+
+    labeler = PhysicsLabeler(cfg, assets, dev)
+    # the contact chain is per sample: it runs on loader batches of up to CHAIN_BATCH frames, whatever the optimiser's batch size is
+    loader = FR.FrameLoader(Head(), min(n, max(args.batch_size, CHAIN_BATCH)), FR.FramePipeline(cfg, assets, dev, train=False, seed=int(cfg.random_seed)))
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    keep = {k: [] for k in ('index', 'hv', 'gravity', 'com', 'hand_contact', 'force_contact', 'is_grasped')}
+    for batch in loader:
+        lab = labeler(batch)
+        sign = torch.where(batch['is_right'].bool(), 1.0, -1.0)[:, None] * torch.tensor([1.0, 0.0, 0.0], device=dev) + torch.tensor([0.0, 1.0, 1.0], device=dev)
+        for k, v in (('index', batch['index']), ('hv', batch['gt_hand_vert_flip']), ('gravity', batch['gravity'].reshape(-1, 3) * sign),
+                     ('com', batch['obj_CoM'].reshape(-1, 3) * sign), ('hand_contact', lab['hand_contact']), ('force_contact', lab['force_contact']),
+                     ('is_grasped', lab['is_grasped'])):
+            keep[k].append(v)
+    keep = {k: torch.cat(v) for k, v in keep.items()}
+    torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    opt = labeler.optimize(keep['hv'].contiguous(), keep['gravity'].contiguous(), keep['com'].contiguous(), keep['force_contact'],
+                           keep['is_grasped'].to(torch.uint8), args.batch_size, iters=args.iters, phase1=args.phase1)
+    torch.cuda.synchronize()
+    t2 = time.perf_counter()
+    meta = dict(labeler.meta(), iters=args.iters, phase1=args.phase1, batch_size=args.batch_size, frame_source=args.frame_source)
+    host = lambda t: t.detach().cpu().numpy()
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    np.savez(path, index=host(keep['index']).astype(np.int64), hand_contact=host(keep['hand_contact']), force_contact=host(keep['force_contact']),
+             is_grasped=host(keep['is_grasped']).astype(bool), force_local=host(opt['force_local']), force_global=host(opt['force_global']),
+             meta=np.array(json.dumps(meta)))
+    print(json.dumps({'metric': f'physics labels from annotations, pairs/s ({args.iters} AdamW iterations per pair)', 'value': n / (t2 - t0), 'unit': 'pairs/s',
+                      'pairs': n, 'batch_size': args.batch_size, 'iters': args.iters, 'seconds': t2 - t0, 'seconds_contact_chain_with_frames': t1 - t0,
+                      'seconds_force_optimize': t2 - t1, 'grasped_share': float(keep['is_grasped'].float().mean()),
+                      'mean_losses_force_gravity_moment_dist': opt['losses'].mean(0).tolist(), 'out': path, 'gap_table': meta['gap_table'],
+                      'data': args.frame_source}))
 
 
 def pmc_traffic(kernel):

@@ -649,6 +649,26 @@ VPHO_API int vpho_contact_detect_f32(const float* query, const float* query_norm
                             float* weight, int* nn_index, void* stream);
 VPHO_API int vpho_force_contact_f32(const vpho_anchor_tables* t, const float* hand_contact, int ld, int n, float thresh,
                            float* force_contact, unsigned char* is_grasped, void* stream);
+/* The front of that chain (appended within ABI version 13): vertex normals of the posed hand mesh and the finger-gap fill, one
+ * workgroup per sample.  Replaces lib/dataset/base.py:887-891 (trimesh.Trimesh(hand_verts, hand_faces).vertex_normals, n / (|n| + 1e-20),
+ * the fill, n / (|n| + 1e-20) again) and lib/utils/hand_fn.py:294-384 (fill_finger_gaps_in_mano, 778 -> 1080 rows).
+ * Table (device arrays, built and VALIDATED once per mesh by the caller; the kernel trusts every index): faces [F][3]; the incidence list
+ * vertex -> (face, corner) in CSR form, csr_offset [V + 1], csr_entry [3 F] = face * 4 + corner with the faces of a vertex in ascending
+ * index; links [L][2] and alpha [L] (fp64) of the gap fill.  V in 1 .. 1024, F <= 2048, L <= 1024, larger sizes are refused.
+ * verts [n][V][3] -> verts_filled, normals_filled [n][V + L][3].
+ * Normals (a restatement of trimesh's angle-weighted vertex normals): face normal = cross(v1 - v0, v2 - v0) unitised, a face whose cross
+ * product is exactly zero contributes nothing; corner angle = acos(clamp(u . w, -1, 1)) of the two unit edge vectors leaving the corner;
+ * vertex normal = sum over csr_entry of angle * face normal, unitised (the zero vector when the sum is zero: an unreferenced vertex,
+ * cancelling faces), then n / (|n| + 1e-20).  Rows V + l of both outputs = alpha[l] * x[links[l][0]] + (1 - alpha[l]) * x[links[l][1]];
+ * every normal row is then divided by (|n| + 1e-20) once more.  fp64 from the fp32 input, each output rounded to fp32 once; fixed
+ * summation order, no atomics: bit-reproducible.  A NaN coordinate reaches its faces, the normals of their vertices and the links
+ * through either; every other value stays finite.  n == 0: success without a launch. */
+typedef struct {
+    const int* faces; const int* csr_offset; const int* csr_entry; const int* links; const double* alpha;
+    int V, F, L;
+} vpho_hand_surface_table;
+VPHO_API int vpho_hand_surface_f32(const vpho_hand_surface_table* t, const float* verts, int n, float* verts_filled, float* normals_filled,
+                          void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Training of the score networks (first slice): the denoising-score-matching step of

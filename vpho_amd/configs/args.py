@@ -97,6 +97,10 @@ class Config:
         self.random_erasing_max_count = 1
         self.heatmap_hand_sigma = 2.0
         self.heatmap_obj_sigma = 2.0
+        # physics labels from annotations (vpho_amd/physics_labels.py): the gates of get_hand_contact (lib/configs/args.py:44-45)
+        self.contact_normal_distance_thresh = (-0.01, 0.01)
+        self.contact_vertical_distance_thresh = 0.005
+        self.frame_contact = False    # FramePipeline also emits hand_contact / force_contact and takes is_grasped from them
         self.cross_dropout = 0.1      # the reference's nn.TransformerEncoderLayer / PositionalEncoding default (cross_module.py:64,104-107)
 
 
@@ -180,6 +184,9 @@ def _parser():
     p.add_argument('--random_erasing_max_count', type=int, default=1)
     p.add_argument('--heatmap_hand_sigma', type=float, default=2.0)
     p.add_argument('--heatmap_obj_sigma', type=float, default=2.0)
+    p.add_argument('--contact_normal_distance_thresh', type=float, nargs=2, default=(-0.01, 0.01))
+    p.add_argument('--contact_vertical_distance_thresh', type=float, default=0.005)
+    p.add_argument('--frame_contact', action='store_true')
     return p
 
 

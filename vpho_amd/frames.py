@@ -309,6 +309,10 @@ class FramePipeline:
             sigma = float(getattr(cfg, f'heatmap_{who}_sigma'))
             g, gmin = gauss_table(sigma)
             self.tables[who] = (torch.from_numpy(g).to(self.device), sigma, gmin)
+        self.labeler = None
+        if getattr(cfg, 'frame_contact', False):        # --frame_contact: contact labels from the annotations, on the device
+            from .physics_labels import PhysicsLabeler
+            self.labeler = PhysicsLabeler(cfg, assets, self.device)
 
     def _dev(self, a, dtype=None):
         t = torch.as_tensor(np.ascontiguousarray(a))
@@ -362,6 +366,11 @@ class FramePipeline:
             out['force_local'] = f32(rec['force_local'])
         out['obj_name'], out['obj_id'] = names, self._dev(np.asarray(rec['obj_id']).reshape(n).astype(np.int64))
         out['index'] = torch.from_numpy(index)
+        if self.labeler is not None:
+            # get_hand_contact .. check_is_grasped (dexycb6.py:320-332) on the labels as they stand after the augmentation: the in-plane
+            # rotation moves hand and object alike.  A record's own is_grasped is not used then.
+            lab = self.labeler(out)
+            out['hand_contact'], out['force_contact'], out['is_grasped'] = lab['hand_contact'], lab['force_contact'], lab['is_grasped']
         return out
 
 
@@ -479,12 +488,16 @@ class synthetic_frames:
 
 RECORD_KEYS = ('jt2d', 'joint_3d', 'mano_pose', 'mano_betas', 'is_right', 'obj_id', 'obj_rt', 'cam_intr')
 OPTIONAL_KEYS = ('hand_vert', 'gravity', 'force_local', 'is_grasped')
+LABEL_FILE = 'physics_labels.npz'                        # beside annotations.npz, one row per frame
+LABEL_KEYS = ('is_grasped', 'force_local', 'force_contact')
 
 
 class FrameDirectory:
     """A source read from a directory: ``annotations.npz`` with the stacked arrays ``image`` (file names relative to the directory),
     jt2d, joint_3d, mano_pose (48), mano_betas, is_right, obj_id, obj_rt, cam_intr and optionally hand_vert, gravity, force_local,
-    is_grasped.  A frame is a ``.npy`` (H,W,3) uint8 array, or an image file read with PIL when PIL can be imported."""
+    is_grasped.  A frame is a ``.npy`` (H,W,3) uint8 array, or an image file read with PIL when PIL can be imported.  When the directory
+    also holds ``physics_labels.npz`` (force_optim.py --frame_source DIR), is_grasped and force_local are read from it and the records
+    carry force_contact too; a file with another number of rows raises ValueError."""
     def __init__(self, path):
         self.path = str(path)
         ann = os.path.join(self.path, 'annotations.npz')
@@ -499,6 +512,15 @@ class FrameDirectory:
         bad = [k for k, v in self.a.items() if len(v) != n]
         if bad:
             raise ValueError(f'FrameDirectory: {bad} do not have the {n} rows of image')
+        # physics_labels.npz (force_optim.py --frame_source DIR): is_grasped and force_local come from it, force_contact rides along
+        self.labels = None
+        side = os.path.join(self.path, LABEL_FILE)
+        if os.path.exists(side):
+            with np.load(side, allow_pickle=False) as z:
+                self.labels = {k: z[k] for k in LABEL_KEYS}
+            bad = [k for k, v in self.labels.items() if len(v) != n]
+            if bad:
+                raise ValueError(f'FrameDirectory: {side} has {len(self.labels[bad[0]])} rows of {bad[0]}, annotations.npz has {n} frames')
 
     def __len__(self):
         return len(self.a['image'])
@@ -516,6 +538,8 @@ class FrameDirectory:
         if frame.dtype != np.uint8 or frame.ndim != 3 or frame.shape[2] != 3:
             raise ValueError(f'FrameDirectory: {name} holds {frame.dtype} {frame.shape}, expected uint8 (H, W, 3)')
         rec = {k: self.a[k][i] for k in RECORD_KEYS + OPTIONAL_KEYS if k in self.a}
+        if self.labels is not None:
+            rec.update({k: self.labels[k][i] for k in LABEL_KEYS})
         rec['index'] = int(i)
         return frame, rec
 

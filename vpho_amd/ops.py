@@ -839,6 +839,67 @@ class AnchorTables(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ('face_idx', 'anchor_weight', 'vert2joint', 'skeleton')]
 
 
+class HandSurfaceTable(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ('faces', 'csr_offset', 'csr_entry', 'links', 'alpha')] + [('V', I), ('F', I), ('L', I)]
+
+
+class HandSurface:
+    """Vertex normals of a posed hand mesh + the finger-gap fill (csrc/hand_surface.hip; base.py:887-891, hand_fn.py:294-384).
+
+    ``HandSurface(faces, links, alpha, device, n_verts=None)``: faces (F,3), links (L,2) integer arrays, alpha (L,) float64; ``n_verts``
+    (default: the largest index + 1) lets a mesh end in unreferenced vertices.  Every index is validated HERE, once: the kernel trusts the
+    table.  ``fill(verts (n,V,3)) -> verts_filled, normals_filled (n,V+L,3)``."""
+    MAX_V, MAX_F, MAX_L = 1024, 2048, 1024
+
+    def __init__(self, faces, links, alpha, device, n_verts=None):
+        import numpy as np
+        faces = np.asarray(faces).reshape(-1, 3)
+        links = np.asarray(links).reshape(-1, 2)
+        alpha = np.asarray(alpha, np.float64).reshape(-1)
+        if faces.dtype.kind not in 'iu' or links.dtype.kind not in 'iu':
+            raise VphoError(f'HandSurface: faces and links must be integer arrays, got {faces.dtype} and {links.dtype}')
+        faces, links = faces.astype(np.int64), links.astype(np.int64)
+        top = max(int(faces.max()) if faces.size else -1, int(links.max()) if links.size else -1)
+        V = int(n_verts) if n_verts is not None else top + 1
+        Fn, L = len(faces), len(links)
+        if not 1 <= V <= self.MAX_V:
+            raise VphoError(f'HandSurface: {V} vertices, the kernel takes 1 .. {self.MAX_V}')
+        if Fn > self.MAX_F:
+            raise VphoError(f'HandSurface: {Fn} faces, the kernel takes at most {self.MAX_F}')
+        if L > self.MAX_L:
+            raise VphoError(f'HandSurface: {L} links, the kernel takes at most {self.MAX_L}')
+        if len(alpha) != L:
+            raise VphoError(f'HandSurface: {L} links with {len(alpha)} weights')
+        for name, a in (('face', faces), ('link', links)):
+            if a.size and (a.min() < 0 or a.max() >= V):
+                bad = int(np.flatnonzero(((a < 0) | (a >= V)).any(1))[0])
+                raise VphoError(f'HandSurface: {name} {bad} = {a[bad].tolist()} indexes outside the {V} vertices')
+        if not np.isfinite(alpha).all():
+            raise VphoError('HandSurface: a link weight is not finite')
+        # vertex -> (face, corner), the faces of a vertex in ascending index (a stable sort of the face-major corner list)
+        flat = faces.reshape(-1)
+        order = np.argsort(flat, kind='stable')
+        entry = (order // 3) * 4 + order % 3
+        offset = np.concatenate([[0], np.cumsum(np.bincount(flat, minlength=V))])
+        dev = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a).astype(dt)).to(device).contiguous()
+        # an empty array still needs an address the structure can hold
+        self.faces, self.csr_offset, self.csr_entry = dev(faces, np.int32), dev(offset, np.int32), dev(entry, np.int32)
+        self.links, self.alpha = dev(links, np.int32), dev(alpha, np.float64)
+        self.V, self.F, self.L, self.device = V, Fn, L, device
+        self.table = HandSurfaceTable(*[t.data_ptr() if t.numel() else None for t in (self.faces, self.csr_offset, self.csr_entry, self.links, self.alpha)],
+                                      V, Fn, L)
+
+    def fill(self, verts, out=None):
+        if verts.dim() != 3 or tuple(verts.shape[1:]) != (self.V, 3):
+            raise VphoError(f'HandSurface.fill: verts of shape {tuple(verts.shape)}, the table was built for (n, {self.V}, 3)')
+        n = verts.shape[0]
+        vf, nf = out if out is not None else (_new((n, self.V + self.L, 3), verts), _new((n, self.V + self.L, 3), verts))
+        if any(tuple(t.shape) != (n, self.V + self.L, 3) for t in (vf, nf)):
+            raise VphoError(f'HandSurface.fill: outputs of shape {tuple(vf.shape)} and {tuple(nf.shape)}, expected {(n, self.V + self.L, 3)}')
+        _call('vpho_hand_surface_f32', C.byref(self.table), _f32(verts), I(n), _f32(vf), _f32(nf))
+        return vf, nf
+
+
 def _ids_to_device(ids, device):
     host = torch.tensor(ids, dtype=torch.int32).pin_memory()        # the caching host allocator keeps the block until the copy's event
     return host.to(device, non_blocking=True)
@@ -960,6 +1021,15 @@ class Aggregation:
         _call('vpho_contact_detect_f32', _f32(hand_verts), _f32(hand_normals), _f32(obj_verts), I(n), I(nh), I(no), *args, _f32(hc), None)
         _call('vpho_contact_detect_f32', _f32(obj_verts), _f32(obj_normals), _f32(hand_verts), I(n), I(no), I(nh), *args, _f32(oc), _i32(o2h))
         return hc, oc, o2h
+
+    def hand_contact(self, hand_verts, hand_normals, obj_verts, normal_thresh=(-0.015, 0.01), vertical_thresh=0.01, decay=(-0.005, 0.005)):
+        """the hand -> object half of detect_hand_and_object_contact, all that get_hand_contact keeps (base.py:898-911): (n,Nh,3), (n,Nh,3),
+        (n,No,3) -> hand_contact (n,Nh); one launch, no object normals"""
+        n, nh, _ = hand_verts.shape
+        hc = _new((n, nh), hand_verts)
+        _call('vpho_contact_detect_f32', _f32(hand_verts), _f32(hand_normals), _f32(obj_verts), I(n), I(nh), I(obj_verts.shape[1]),
+              F(normal_thresh[0]), F(normal_thresh[1]), F(vertical_thresh), F(decay[0]), F(decay[1]), _f32(hc), None)
+        return hc
 
     def force_contact(self, hand_contact, thresh=0.0):
         """ForceAnchor.get_force_contact + check_is_grasped (physics_fn.py:201-221): (n, >=778) -> (n,32), (n,) uint8"""
