@@ -14,8 +14,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # SPATIAL_BWD_KERNELS below).
 EXCEPTIONS = {
     'vpho_conv3x3_winograd_gate_nhwc_f32': 'gated Winograd input gradient of the training blocks: compared through the bottleneck / FPN / encoder training goldens only',
-    'vpho_mha_f32': 'alias of vpho_mha_dropout_f32 without a mask (no wrapper): that entry point is tested directly in test_gpu_train_physics.py',
-    'vpho_mha_bwd_f32': 'alias of vpho_mha_bwd_ws_f32 for short sequences (no wrapper): that entry point is tested directly in test_gpu_train_physics.py',
+    'vpho_mha_f32': 'alias of vpho_mha_dropout_f32 without a mask (no wrapper): called through ops._call in test_gpu_attention.py, every forward form, the bits of ops.mha',
+    'vpho_mha_bwd_f32': 'alias of vpho_mha_bwd_ws_f32 for short sequences (no wrapper): called through ops._call in test_gpu_attention.py, the bits of ops.mha_bwd and its S <= 64 refusal',
 }
 
 # the glue and training leaf kernels that tests/test_gpu_leaf_forward.py / test_gpu_leaf_train.py cover one by one

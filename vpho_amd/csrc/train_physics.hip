@@ -446,7 +446,8 @@ extern "C" long long vpho_mha_bwd_workspace_bytes(int S, int B, int nhead) {
 
 extern "C" int vpho_mha_bwd_ws_f32(const float* qkv, const float* d_out, int S, int B, int E, int nhead, const float* drop_mask, float* dqkv,
                                    void* workspace, void* stream) {
-    VPHO_REQUIRE(qkv && d_out && dqkv && S > 0 && B > 0 && nhead > 0 && E % nhead == 0 && (E / nhead) % 4 == 0, "vpho_mha_bwd_f32: bad argument");
+    VPHO_REQUIRE(qkv && d_out && dqkv && S > 0 && B > 0 && nhead > 0 && E % nhead == 0, "vpho_mha_bwd_f32: bad argument");
+    VPHO_REQUIRE((E / nhead) % 4 == 0, "vpho_mha_bwd_f32: head_dim %d is not a multiple of 4 (the kernels load four feature columns at a time)", E / nhead);
     VPHO_REQUIRE(S <= MB_S_MAX, "vpho_mha_bwd_f32: sequence (= batch, quirk Q3) of %d exceeds the %d positions of the attention kernels", S, MB_S_MAX);
     hipStream_t s = (hipStream_t)stream;
     if (S <= MB_S) {
