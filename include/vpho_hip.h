@@ -852,6 +852,63 @@ VPHO_API int vpho_frame_patch_f32(const unsigned char* frames, int n, int H, int
 VPHO_API int vpho_heatmap_targets_f32(const double* pts, const double* box, const int* res, const unsigned char* left, const float* g, int G, double sigma,
                              double gmin, int n, int J, int S, int adaptive, float* out, void* stream);
 
+/* ---- predictions to pixels (raster.hip, appended within ABI version 13): a batched, deterministic triangle rasteriser and the overlay
+ * compositor.  They stand in for the reference's pytorch3d renderer, lib/utils/render_fn.py, and what lib/dataset/base.py:472-500,632-688
+ * does with it (get_obj_front_and_back_depth_map and the rendered overlays).  Nothing here is compared with pytorch3d: the rules below are
+ * this project's own, chosen to be exact and watertight.
+ * Table (device arrays, built and VALIDATED once per asset set by the caller; the kernels trust every index): the meshes' triangles
+ * concatenated, faces [sum F][3] with vertex indices local to their mesh, face_offset [M + 1], vert_count [M].
+ * vpho_mesh_raster_f32: n images of H x W pixels, 1 <= H, W <= 2048 (larger sizes are refused), one mesh each -- a mixed batch is ONE launch.
+ * verts [n][Vmax][3] fp32, camera frame, metres; mesh_id [n]; K [n][3][3] fp64 (upper triangular, the skew entry K01 is honoured);
+ * face_stride >= the face count of every mesh the batch uses (faces beyond it are not drawn); workspace of vpho_mesh_raster_bytes(n,
+ * face_stride) bytes (-1 = bad argument).  Outputs [n][H][W], any of them may be NULL: depth_front / depth_back fp32 metres, 0 where nothing
+ * covers the pixel; face_front / face_back int32, the face index WITHIN the mesh, -1 where nothing covers the pixel.  n == 0: success
+ * without a launch.  An image whose mesh_id lies outside the table comes back empty.
+ * Projection, fp64 from the fp32 inputs, every operation rounded once and none contracted:
+ *     u = (K00 * X + K01 * Y) / Z + K02        v = (K11 * Y) / Z + K12
+ * then each coordinate is snapped to a 1/256-pixel lattice: rint(u * 256), rint(v * 256), ties to even, as 64-bit integers.
+ * Dropped faces (documented behaviour, counted nowhere; there is no clipping): a face with any vertex at Z <= z_near (compared in fp64) is
+ * dropped whole; so is a face with a snapped coordinate of magnitude above 2^30, a face of zero integer (doubled) area A = (x1 - x0)
+ * (y2 - y0) - (y1 - y0)(x2 - x0), and a face with a NaN or an infinity in one of its vertices -- that face and nothing else.
+ * Coverage: both windings count (no back-face culling); a face with A < 0 has its corners 1 and 2 exchanged, so A > 0 below.  The centre
+ * c = (256 x + 128, 256 y + 128) of pixel (x, y) is tested in exact 64-bit integer edge functions of the snapped corners,
+ *     E0 = (x2 - x1)(cy - y1) - (y2 - y1)(cx - x1),  E1 = (x0 - x2)(cy - y2) - (y0 - y2)(cx - x2),  E2 = (x1 - x0)(cy - y0) - (y1 - y0)(cx - x0)
+ * (E0 + E1 + E2 = A).  Top-left fill rule, y downwards: the centre is covered when every E_i > 0, or E_i == 0 on an edge (dx, dy) with
+ * dy < 0 (a left edge) or dy == 0 and dx > 0 (a top edge).  A centre on an edge shared by two faces of a planar patch belongs to exactly
+ * one of them, a centre on a shared vertex to exactly one face of the fan.
+ * Depth at a covered centre is perspective-correct, in fp64: w_i = E_i / A (both integers converted to fp64 first),
+ *     1 / z = (w0 / z0 + w1 / z1) + w2 / z2,      z = 1 / that sum, rounded to fp32 once on store.
+ * Front = the covering face of smallest fp64 z, back = the one of largest; among equal fp64 values the smaller face index wins in both.
+ * Bit-reproducible from run to run and independent of the batch composition and the launch geometry: one lane owns a pixel from the first
+ * face to the last, faces are visited in ascending index, there are no atomics and nothing depends on the order of the workgroups. */
+typedef struct {
+    const int* faces; const int* face_offset; const int* vert_count;
+    int M;
+} vpho_mesh_table;
+VPHO_API long long vpho_mesh_raster_bytes(int n, int face_stride);
+VPHO_API int vpho_mesh_raster_f32(const vpho_mesh_table* t, const float* verts, int Vmax, const int* mesh_id, const double* K, int n, int H, int W,
+                         int face_stride, double z_near, float* depth_front, float* depth_back, int* face_front, int* face_back,
+                         void* workspace, void* stream);
+/* vpho_render_overlay_u8: composites up to two rasterised layers (hand, object; either may be NULL = absent) over image [n][3][H][W] fp32,
+ * the network's normalised input -> out [n][H][W][3] uint8.  A layer = the depth_front / face_front maps of vpho_mesh_raster_f32 with the
+ * verts, mesh_id and table (faces, face_offset, M) they were made from, a colour on the 0 .. 255 scale and an opacity in [0, 1].
+ * mean_host / std_host: 3 floats each, HOST arrays.  Per pixel, in fp64:
+ *     background_c = (image_c * std_c + mean_c) * 255;
+ *     the nearer of the two front layers wins (their fp32 depths compared), the hand wins an exact tie;
+ *     n = cross(v1 - v0, v2 - v0) of the winning face's camera-space corners, d = K^-1 (x + 0.5, y + 0.5, 1) for the upper-triangular K:
+ *         dy = ((y + 0.5) - K12) / K11,  dx = (((x + 0.5) - K02) - K01 * dy) / K00,  dz = 1;
+ *     shade = ambient + (1 - ambient) * (|n . d| / (sqrt(n . n) * sqrt(d . d))), sums as (a + b) + c; a zero normal gets the ambient term only;
+ *     out_c = (opacity * shade) * colour_c + (1 - opacity) * background_c, clamped to [0, 255], rounded half to even (a NaN gives 0).
+ * Where neither layer covers the pixel, out_c = background_c clamped and rounded the same way.  n == 0: success without a launch. */
+typedef struct {
+    const float* depth_front; const int* face_front; const float* verts; const int* mesh_id;
+    const int* faces; const int* face_offset;
+    int Vmax, M;
+    float red, green, blue, opacity;
+} vpho_render_layer;
+VPHO_API int vpho_render_overlay_u8(const float* image, const float* mean_host, const float* std_host, const double* K, const vpho_render_layer* hand,
+                           const vpho_render_layer* obj, float ambient, int n, int H, int W, unsigned char* out, void* stream);
+
 /* ---- physics branch of the training step (lib/model/VPHO.py:170-172,205-212 under loss.backward()) -------------------------------
  * backward of vpho_cross_tokens_f32 (cross_module.py:125-133: .view(bs,32,-1) of the projected maps, cat, + positional code):
  * dtok [bs][65][512] -> d_proj_hand / d_proj_obj [bs][8][8][256] NHWC (NULL for the stream the reference detaches, VPHO.py:170-171)

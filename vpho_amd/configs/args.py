@@ -101,6 +101,7 @@ class Config:
         self.contact_normal_distance_thresh = (-0.01, 0.01)
         self.contact_vertical_distance_thresh = 0.005
         self.frame_contact = False    # FramePipeline also emits hand_contact / force_contact and takes is_grasped from them
+        self.infer_render = 0         # --mode infer: each rank also renders its first N images to <save_dir>/render/<index>.png (vpho_amd/render.py)
         self.cross_dropout = 0.1      # the reference's nn.TransformerEncoderLayer / PositionalEncoding default (cross_module.py:64,104-107)
 
 
@@ -187,6 +188,7 @@ def _parser():
     p.add_argument('--contact_normal_distance_thresh', type=float, nargs=2, default=(-0.01, 0.01))
     p.add_argument('--contact_vertical_distance_thresh', type=float, default=0.005)
     p.add_argument('--frame_contact', action='store_true')
+    p.add_argument('--infer_render', type=int, default=0)
     return p
 
 

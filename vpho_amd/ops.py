@@ -1969,6 +1969,149 @@ def heatmap_targets(pts, box, g, sigma, gmin, size, res=None, left=None, out=Non
     return out
 
 
+# ----------------------------------------------------------------------------------------------- predictions to pixels (raster.hip)
+class MeshTable(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ('faces', 'face_offset', 'vert_count')] + [('M', I)]
+
+
+class RenderLayer(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ('depth_front', 'face_front', 'verts', 'mesh_id', 'faces', 'face_offset')] + [('Vmax', I), ('M', I)] + \
+               [(k, F) for k in ('red', 'green', 'blue', 'opacity')]
+
+
+lib.vpho_mesh_raster_bytes.restype = C.c_longlong
+
+
+class MeshRaster:
+    """Triangle meshes to depth and face maps, and the overlay compositor (csrc/raster.hip; the rules are in include/vpho_hip.h).
+
+    ``MeshRaster(meshes, device)``: ``meshes`` is a list of ``(verts_count, faces)``, faces (F,3) integer arrays with indices local to
+    their mesh.  Every index is validated HERE, once: the kernels trust the table.  ``raster(verts, mesh_id, K, H, W)`` draws n images
+    of one mesh each in ONE launch pair; ``overlay(image, K, hand=..., obj=...)`` composites up to two rasterised layers."""
+    MAX_SIDE, MAX_VERTS, MAX_FACES, MAX_MESHES = 2048, 1 << 22, 1 << 24, 1 << 16
+
+    def __init__(self, meshes, device):
+        import numpy as np
+        meshes = list(meshes)
+        if not 1 <= len(meshes) <= self.MAX_MESHES:
+            raise VphoError(f'MeshRaster: {len(meshes)} meshes, the table takes 1 .. {self.MAX_MESHES}')
+        all_faces, counts, nverts = [], [], []
+        for i, (V, faces) in enumerate(meshes):
+            faces = np.asarray(faces)
+            if faces.dtype.kind not in 'iu':
+                raise VphoError(f'MeshRaster: mesh {i}: faces must be an integer array, got {faces.dtype}')
+            if faces.ndim != 2 or faces.shape[1] != 3 or faces.shape[0] < 1:
+                raise VphoError(f'MeshRaster: mesh {i}: faces of shape {faces.shape}, expected (F, 3) with F >= 1')
+            V = int(V)
+            if not 1 <= V <= self.MAX_VERTS:
+                raise VphoError(f'MeshRaster: mesh {i}: {V} vertices, the table takes 1 .. {self.MAX_VERTS}')
+            faces = faces.astype(np.int64)
+            if faces.min() < 0 or faces.max() >= V:
+                bad = int(np.flatnonzero(((faces < 0) | (faces >= V)).any(1))[0])
+                raise VphoError(f'MeshRaster: mesh {i}: face {bad} = {faces[bad].tolist()} indexes outside the {V} vertices')
+            all_faces.append(faces)
+            counts.append(len(faces))
+            nverts.append(V)
+        if sum(counts) > self.MAX_FACES:
+            raise VphoError(f'MeshRaster: {sum(counts)} faces in all, the table takes at most {self.MAX_FACES}')
+        dev = lambda a: torch.as_tensor(np.ascontiguousarray(a).astype(np.int32)).to(device).contiguous()
+        self.face_counts, self.vert_counts, self.M, self.device = counts, nverts, len(meshes), torch.device(device)
+        self.faces, self.face_offset, self.vert_count = dev(np.concatenate(all_faces)), dev(np.concatenate([[0], np.cumsum(counts)])), dev(nverts)
+        self.table = MeshTable(self.faces.data_ptr(), self.face_offset.data_ptr(), self.vert_count.data_ptr(), self.M)
+
+    def mesh_ids(self, mesh_id, n=None):
+        """ids as a HOST list (checked against the table) and as an int32 device tensor.  A device tensor is read back (one wait): pass a
+        list, a numpy array or a CPU tensor to stay asynchronous."""
+        dev_ids = mesh_id if torch.is_tensor(mesh_id) and mesh_id.is_cuda else None
+        host = [int(i) for i in (mesh_id.reshape(-1).tolist() if hasattr(mesh_id, 'reshape') else list(mesh_id))]
+        if n is not None and len(host) != n:
+            raise VphoError(f'MeshRaster: {len(host)} mesh ids for {n} images')
+        bad = [i for i in host if not 0 <= i < self.M]
+        if bad:
+            raise VphoError(f'MeshRaster: mesh_id {bad[0]} lies outside the table of {self.M} meshes')
+        if dev_ids is None or dev_ids.dtype != torch.int32 or dev_ids.dim() != 1 or not dev_ids.is_contiguous():
+            dev_ids = _ids_to_device(host, self.device)
+        return host, dev_ids
+
+    def _check_size(self, who, H, W):
+        if not (1 <= int(H) <= self.MAX_SIDE and 1 <= int(W) <= self.MAX_SIDE):
+            raise VphoError(f'MeshRaster.{who}: {H} x {W} pixels, the kernels take sides of 1 .. {self.MAX_SIDE}')
+
+    def raster(self, verts, mesh_id, K, H, W, z_near=0.01, back=True):
+        """verts (n,Vmax,3) fp32 camera-frame metres, mesh_id n ids into the table, K (n,3,3) -> dict of depth_front, face_front (n,H,W) fp32 /
+        int32 and, with ``back``, depth_back, face_back; 'verts', 'mesh_id' and 'K' ride along for ``overlay``.  vpho_mesh_raster_f32."""
+        self._check_size('raster', H, W)
+        if verts.dim() != 3 or verts.shape[2] != 3 or verts.shape[1] < 1:
+            raise VphoError(f'MeshRaster.raster: verts of shape {tuple(verts.shape)}, expected (n, Vmax, 3)')
+        n, Vmax = verts.shape[0], verts.shape[1]
+        if tuple(K.shape) != (n, 3, 3):
+            raise VphoError(f'MeshRaster.raster: K of shape {tuple(K.shape)}, expected {(n, 3, 3)}')
+        if not (z_near > 0.0 and z_near < 1e30):
+            raise VphoError(f'MeshRaster.raster: z_near = {z_near}, expected a positive finite distance')
+        host, ids = self.mesh_ids(mesh_id, n)
+        for i in set(host):
+            if self.vert_counts[i] > Vmax:
+                raise VphoError(f'MeshRaster.raster: mesh {i} has {self.vert_counts[i]} vertices, verts holds {Vmax} per image')
+        verts, K = verts.float().contiguous(), K.double().contiguous()
+        stride = max([self.face_counts[i] for i in host], default=0)
+        size = lib.vpho_mesh_raster_bytes(I(n), I(stride))
+        if size < 0:
+            raise VphoError(f'vpho_mesh_raster_bytes: n = {n}, face_stride = {stride}')
+        ws = torch.empty(max(size, 16), dtype=torch.uint8, device=verts.device)
+        df, ff = _new((n, H, W), verts), _new((n, H, W), verts, torch.int32)
+        db, fb = (_new((n, H, W), verts), _new((n, H, W), verts, torch.int32)) if back else (None, None)
+        _call('vpho_mesh_raster_f32', C.byref(self.table), _f32(verts), I(Vmax), _i32(ids), _f64(K), I(n), I(H), I(W), I(stride), C.c_double(z_near),
+              _f32(df), _f32(db), _i32(ff), _i32(fb), _ptr(ws))
+        out = dict(depth_front=df, face_front=ff, verts=verts, mesh_id=ids, mesh_id_host=host, K=K)
+        if back:
+            out.update(depth_back=db, face_back=fb)
+        return out
+
+    def _layer(self, who, layer, n, H, W):
+        if layer is None:
+            return None, None
+        df, ff, verts, ids = layer['depth_front'], layer['face_front'], layer['verts'], layer['mesh_id']
+        if tuple(df.shape) != (n, H, W) or tuple(ff.shape) != (n, H, W) or verts.dim() != 3 or verts.shape[0] != n or tuple(ids.shape) != (n,):
+            raise VphoError(f'MeshRaster.overlay: the {who} layer has maps {tuple(df.shape)} / {tuple(ff.shape)}, verts {tuple(verts.shape)}, '
+                            f'mesh_id {tuple(ids.shape)} for {n} images of {H} x {W}')
+        # the face maps name vertices of these meshes: the ids are checked on the host again (a layer built by hand brings them as a list)
+        host = layer['mesh_id_host'] if 'mesh_id_host' in layer else self.mesh_ids(ids, n)[0]
+        for i in set(host):
+            if not 0 <= i < self.M or self.vert_counts[i] > verts.shape[1]:
+                raise VphoError(f'MeshRaster.overlay: the {who} layer names mesh {i}, which the table or verts {tuple(verts.shape)} cannot hold')
+        r, g, b = [float(c) for c in layer.get('colour', (200.0, 200.0, 200.0))]
+        op = float(layer.get('opacity', 1.0))
+        if not 0.0 <= op <= 1.0:
+            raise VphoError(f'MeshRaster.overlay: the {who} layer has opacity {op}, expected 0 .. 1')
+        keep = (df, ff, verts, ids)
+        return RenderLayer(_f32(df).value, _i32(ff).value, _f32(verts).value, _i32(ids).value, self.faces.data_ptr(), self.face_offset.data_ptr(), verts.shape[1], self.M,
+                           r, g, b, op), keep
+
+    def overlay(self, image, K, hand=None, obj=None, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), ambient=0.3, out=None):
+        """image (n,3,H,W) fp32 normalised, K (n,3,3); ``hand`` / ``obj``: a dict of ``raster`` (its depth_front, face_front, verts, mesh_id)
+        with 'colour' (r, g, b on the 0 .. 255 scale) and 'opacity', or None -> (n,H,W,3) uint8.  vpho_render_overlay_u8."""
+        if image.dim() != 4 or image.shape[1] != 3:
+            raise VphoError(f'MeshRaster.overlay: image of shape {tuple(image.shape)}, expected (n, 3, H, W)')
+        n, _, H, W = image.shape
+        self._check_size('overlay', H, W)
+        if tuple(K.shape) != (n, 3, 3):
+            raise VphoError(f'MeshRaster.overlay: K of shape {tuple(K.shape)}, expected {(n, 3, 3)}')
+        if not 0.0 <= float(ambient) <= 1.0:
+            raise VphoError(f'MeshRaster.overlay: ambient = {ambient}, expected 0 .. 1')
+        image, K = image.float().contiguous(), K.double().contiguous()
+        lh, keep_h = self._layer('hand', hand, n, H, W)
+        lo, keep_o = self._layer('object', obj, n, H, W)
+        if out is None:
+            out = _new((n, H, W, 3), image, torch.uint8)
+        elif tuple(out.shape) != (n, H, W, 3) or out.dtype != torch.uint8:
+            raise VphoError(f'MeshRaster.overlay: out of shape {tuple(out.shape)} / {out.dtype}, expected {(n, H, W, 3)} uint8')
+        mean3, std3 = (C.c_float * 3)(*[float(v) for v in mean]), (C.c_float * 3)(*[float(v) for v in std])
+        _call('vpho_render_overlay_u8', _f32(image), mean3, std3, _f64(K), None if lh is None else C.byref(lh), None if lo is None else C.byref(lo),
+              F(ambient), I(n), I(H), I(W), _u8(out))
+        del keep_h, keep_o
+        return out
+
+
 # ----------------------------------------------------------------------------------------------- physics branch (training)
 def cross_tokens_bwd(dtok, want_hand=True, want_obj=True):
     bs = dtok.shape[0]

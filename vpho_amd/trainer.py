@@ -424,7 +424,9 @@ class Trainer:
         them out.  Every rank writes a shard, rank 0 merges and writes under ``save_dir`` (default
         ``<output_dir>/<timestamp>_<mark>_infer_<model>``, base_trainer.py:52-63) ``submit/hand_reg.zip``, ``submit/hand_diff.zip`` and
         ``my-prediction_align-<clean_data_mode>.pkl`` (vpho_amd/infer.py), prints the object table of the aggregated
-        pose when the batches carry its ground truth, and one ``INFER_JSON`` line.  Returns that line's dict on rank 0, None elsewhere."""
+        pose when the batches carry its ground truth, and one ``INFER_JSON`` line.  Returns that line's dict on rank 0, None elsewhere.
+        With ``cfg.infer_render`` = N > 0 each rank also renders the first N images it sees to ``<save_dir>/render/<index:08d>.png``
+        (vpho_amd/render.py, csrc/raster.hip) and the line gains ``render: {dir, images}``; at 0 nothing of that is imported or run."""
         import json
         import queue
         import threading
@@ -442,17 +444,29 @@ class Trainer:
         packer = ops.InferPacker(self.device, max_batch=cfg.eval_batch_size, slots=pipe.depth)
         free = [threading.Semaphore(1) for _ in range(pipe.depth)]       # a slot's pinned buffer is refilled only after the host took its records
         todo, recs, objs, errors = queue.Queue(), [], [], []
+        # --infer_render N: this rank's first N images as overlays (vpho_amd/render.py, imported only here).  Per batch two raster launches,
+        # one overlay launch and one asynchronous copy into the slot's pinned buffer, all on the slot's stream inside `post`; the host thread
+        # below encodes the PNGs once the slot's event (recorded behind them by packer.pack) has passed
+        n_render = max(int(getattr(cfg, 'infer_render', 0) or 0), 0)
+        render_dir, rendered, render_skipped, render_host = os.path.join(save_dir, 'render'), [0, 0], [0], [None] * pipe.depth
+        if n_render:
+            from . import render as RND
+            renderer = RND.MeshRenderer(self.assets, self.device, getattr(cfg, 'asset_root', 'asset'))
+            os.makedirs(render_dir, exist_ok=True)
 
         def consume():
             while True:
                 item = todo.get()
                 if item is None:
                     return
-                fut, slot = item
+                fut, slot, shots = item
                 try:
                     obj = fut.result()
                     recs.append(packer.collect(slot).copy())
                     objs.append(obj)
+                    for i, image_index in enumerate(shots):
+                        RND.write_png(os.path.join(render_dir, f'{int(image_index):08d}.png'), render_host[slot][i].numpy())
+                        rendered[1] += 1
                 except BaseException as e:          # noqa: B036  (kept for the submitting thread; the slot is released either way)
                     errors.append(e)
                 finally:
@@ -491,12 +505,24 @@ class Trainer:
                 skipped_obj += 0 if want_obj else 1
                 slot = pipe.n % pipe.depth
                 free[slot].acquire()
+                take = min(n, n_render - rendered[0]) if n_render else 0
+                if take > 0 and not all(k in b for k in ('cam_intr_crop_flip', 'obj_name')):
+                    render_skipped[0] += 1
+                    take = 0
+                shots = [int(i) for i in index[-1][:take]]
+                rendered[0] += take
+                if take > 0 and (render_host[slot] is None or tuple(render_host[slot].shape[1:3]) != tuple(b['rgb'].shape[2:])):
+                    render_host[slot] = torch.empty((packer.max_batch,) + tuple(b['rgb'].shape[2:]) + (3,), dtype=torch.uint8, pin_memory=True)
 
-                def post(out, batch, eng, slot=slot, want_obj=want_obj):
+                def post(out, batch, eng, slot=slot, want_obj=want_obj, take=take):
+                    if take > 0:
+                        cut = lambda v: v[:take] if torch.is_tensor(v) or isinstance(v, (list, tuple)) else v
+                        img = renderer.overlay({k: cut(v) for k, v in batch.items()}, {k: cut(out[k]) for k in ('agg_hand_vert', 'agg_obj_6d')})
+                        render_host[slot][:take].copy_(img, non_blocking=True)
                     packer.pack(out, batch, slot=slot)                      # on the slot's stream: kernel + copy + event
                     return E.object_metric_block(out, batch, self.assets).float() if want_obj else None
 
-                todo.put((pipe.submit(b, post), slot))
+                todo.put((pipe.submit(b, post), slot, shots))
                 item = gen.send(None)
         except StopIteration:
             pass
@@ -519,8 +545,9 @@ class Trainer:
         if self.world > 1:
             INF.write_shard(save_dir, self.rank, mine, mine['index'], paths, sizes, any_index)
             flags = [None] * self.world
-            dist.all_gather_object(flags, (with_obj, seen))
+            dist.all_gather_object(flags, (with_obj, seen, rendered[1], render_skipped[0]))
             with_obj = all(f[0] or f[1] == 0 for f in flags)
+            rendered[1], render_skipped[0] = sum(f[2] for f in flags), sum(f[3] for f in flags)
             rows = E.gather_rows(rows)
             dist.barrier()                               # every shard is complete on disk
         res = None
@@ -545,6 +572,11 @@ class Trainer:
                 print("Object Evaluation: skipped (the batches carry no 'gt_obj_rt' / 'gt_obj', 'cam_intr', 'obj_name')")
             res = {'images': N, 'world': self.world, 'files': files, 'object': table, 'images_per_s': N / t_collected,
                    'images_per_s_with_files': N / t_files, 'missing_indices': int(gaps.size), 'save_dir': save_dir}
+            if n_render:
+                if render_skipped[0]:
+                    print(f"Render: {render_skipped[0]} batch(es) skipped (they carry no 'cam_intr_crop_flip' / 'obj_name')")
+                print(f'  render: {rendered[1]} overlay(s) under {render_dir}')
+                res['render'] = {'dir': render_dir, 'images': int(rendered[1])}
             print('INFER_JSON ' + json.dumps(res))
         if self.world > 1:
             dist.barrier()
