@@ -496,6 +496,36 @@ VPHO_API int vpho_hand_bench_multi_f32(const float* pd, const float* gt, const f
                               int n_thresh, int with_fscore, double* values, int* counts, void* stream);
 VPHO_API int vpho_hand_bench_table_f64(const double* per, int n_img, int n_hyp, double* one, double* best, double* mean, void* stream);
 
+/* Symmetry-aware object errors for every sampled hypothesis (--eval_symmetric), appended within ABI version 13.
+ * vpho_obj_symmetry_multi_f64 replaces TesterObject.criterion_SMCE (lib/engine/test.py:377-398; its call at :258 is commented out as
+ *   "very slow") over the padded symmetry table of TesterObject.__init__ (:204-226; get_symmetry_transformations :103-150,
+ *   rotation_matrix :59-100 -- vpho_amd/symmetry.py builds it on the host), and adds the BOP toolkit's MSSD over the same table and the
+ *   sampled vertices of criterion_ADD_REP (:425-458).  With S_k = (sym_R[k] | sym_t[k]), P = pd_rt[b][s], G = gt_rt[b] and
+ *   D_k = P - G S_k (one 3x4 affine map per (hypothesis, k)):
+ *     SMCE = min_k mean_c |D_k c| over the 8 corners bbox3d;  MSSD = min_k max_v |D_k v| over verts_sampled (any n_sampled >= 1).
+ *   Every one of the K rows of the object's table takes part, the identity pads included (the reference indexes all of them too).
+ *   per [n_img][n_hyp][3] = SMCE (m), MSSD (m), MSSD < 0.1 * diameter (0 / 1).  prune != 0 lets a lane abandon a symmetry once its
+ *   running maximum reaches the smallest completed maximum of an earlier round of 256 symmetries; prune == 0 runs every pair in full;
+ *   both return the same bits.  A hypothesis or ground truth with a non-finite entry, or an obj_id outside [0, n_obj), gives NaN, NaN, 0.
+ *   1 <= K <= 4096, n_img * n_hyp <= 2^31 - 1: anything else is an error before any launch.
+ * vpho_obj_symmetry_table_f64 (TesterObject.postprocess, test.py:522-567): per [n_img][n_hyp][3] -> one [n_img][3] (hypothesis 0), best
+ *   [n_img][3] (min of SMCE and MSSD, max of the hit), mean [n_img][3] (fp64 sum in ascending hypothesis order / n_hyp).  NaN rows as in
+ *   vpho_obj_metrics_multi_f64: best starts from hypothesis 0 and takes a later value only where `v < best` (`v > best` for the hit)
+ *   holds, so a NaN hypothesis 0 gives NaN and a later NaN hypothesis is passed over; mean is NaN as soon as one hypothesis is (the
+ *   hit of such a hypothesis is 0 and counts as a miss).
+ * Deterministic: fixed reduction orders, no atomics, nothing depends on the order of the workgroups. */
+typedef struct vpho_obj_symmetry_tables {
+    const double* sym_R;           /* [n_obj][K][3][3] */
+    const double* sym_t;           /* [n_obj][K][3], metres */
+    const double* bbox3d;          /* [n_obj][8][3] */
+    const double* verts_sampled;   /* [n_obj][n_sampled][3] */
+    const double* diameter;        /* [n_obj] */
+    int K, n_obj, n_sampled;
+} vpho_obj_symmetry_tables;
+VPHO_API int vpho_obj_symmetry_multi_f64(const vpho_obj_symmetry_tables* t, const double* pd_rt, const double* gt_rt, const int* obj_id,
+                                int n_img, int n_hyp, int prune, double* per, void* stream);
+VPHO_API int vpho_obj_symmetry_table_f64(const double* per, int n_img, int n_hyp, double* one, double* best, double* mean, void* stream);
+
 /* Prediction records of --mode infer (Trainer.infer, lib/engine/train_diff_hand_obj.py:359-444): ONE launch turns the predict outputs of a
  * batch into fixed-layout per-image records, and ONE hipMemcpyAsync ships them to the host.  Replaces, per batch, the postprocess of
  * the four hand arrays (__postprocess_hand_vert, :598-602: x negated where !is_right, then + root_joint; one sign flip and one fp32 add

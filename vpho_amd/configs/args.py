@@ -25,6 +25,8 @@ class Config:
         self.eval_volume = False      # also report the hand-object intersection volume; independent of eval_physics
         self.physics_voxel_pitch = 0.005      # its voxel pitch (m): the 0.5 cm of the ObMan / GraspTTA evaluations
         self.eval_hand_bench = False  # also report the hand F@5 / F@15 and PCK AUC of the HO3D / FreiHAND leaderboards
+        self.eval_symmetric = False   # also report the symmetry-aware object errors SMCE / MSSD / MSSD01d
+        self.max_sym_disc_step = 0.01         # discretisation of a continuous symmetry: the reference's constant (test.py:205)
         self.mark = ''
         self.random_seed = 0
         self.output_dir = 'output'
@@ -115,6 +117,8 @@ def _parser():
     p.add_argument('--eval_volume', action='store_true')
     p.add_argument('--physics_voxel_pitch', type=float, default=0.005)
     p.add_argument('--eval_hand_bench', action='store_true')
+    p.add_argument('--eval_symmetric', action='store_true')
+    p.add_argument('--max_sym_disc_step', type=float, default=0.01)
     p.add_argument('--mark', type=str, default='')
     p.add_argument('--random_seed', type=int, default=0)
     p.add_argument('--output_dir', type=str, default='output')

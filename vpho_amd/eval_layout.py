@@ -16,9 +16,15 @@ BLOCKS = (('base', None, 28, N.BASE_COLUMNS),
           ('volume', 'eval_volume', 4, N.VOLUME_COLUMNS),
           ('hand_bench', 'eval_hand_bench', 16, N.HAND_BENCH_COLUMNS),
           ('hand_bench_multi', 'hand_bench_multi', 24, N.HAND_BENCH_MULTI_COLUMNS))
-assert all(len(cols) == w for _, _, w, cols in BLOCKS)
+# blocks added after BLOCKS was pinned to its eight entries (tests/test_eval_layout_cpu.py): they follow it, in this order; _spans, width and
+# columns walk ALL_BLOCKS
+BLOCKS_ADDED = (('symmetric', 'eval_symmetric', 3, N.SYM_COLUMNS),
+                ('symmetric_multi', 'symmetric_multi', 9, N.SYM_MULTI_COLUMNS))
+ALL_BLOCKS = BLOCKS + BLOCKS_ADDED
+assert all(len(cols) == w for _, _, w, cols in ALL_BLOCKS)
 # each *_multi block (every sampled hypothesis) needs eval_best and the flag of its single-pose block
-MULTI_NEEDS = {'physics_multi': 'eval_physics', 'volume_multi': 'eval_volume', 'hand_bench_multi': 'eval_hand_bench'}
+MULTI_NEEDS = {'physics_multi': 'eval_physics', 'volume_multi': 'eval_volume', 'hand_bench_multi': 'eval_hand_bench',
+               'symmetric_multi': 'eval_symmetric'}
 
 
 @dataclass(frozen=True)
@@ -31,14 +37,17 @@ class RowLayout:
     volume_multi: bool = False
     eval_hand_bench: bool = False
     hand_bench_multi: bool = False
+    eval_symmetric: bool = False
+    symmetric_multi: bool = False
 
     @classmethod
     def resolve(cls, eval_best=False, eval_physics=False, physics_multi=False, eval_volume=False, volume_multi=False, eval_hand_bench=False,
-                hand_bench_multi=False):
-        """The layout of the seven flags.  None means 'follow the configuration': cfg.eval_best / eval_physics / eval_volume /
-        eval_hand_bench for those four, and for a *_multi flag 'both command-line flags', cfg.eval_best and cfg.eval_<its block>, so
+                hand_bench_multi=False, eval_symmetric=False, symmetric_multi=False):
+        """The layout of the nine flags.  None means 'follow the configuration': cfg.eval_best / eval_physics / eval_volume /
+        eval_hand_bench / eval_symmetric for those five, and for a *_multi flag 'both command-line flags', cfg.eval_best and cfg.eval_<its block>, so
         that a caller who passes the older flags itself gets the rows it always got."""
-        f = dict(zip(cls.__dataclass_fields__, (eval_best, eval_physics, physics_multi, eval_volume, volume_multi, eval_hand_bench, hand_bench_multi)))
+        f = dict(zip(cls.__dataclass_fields__, (eval_best, eval_physics, physics_multi, eval_volume, volume_multi, eval_hand_bench, hand_bench_multi,
+                                                     eval_symmetric, symmetric_multi)))
         if None in f.values():
             from .configs.args import cfg
             for k in [k for k, v in f.items() if v is None]:
@@ -49,7 +58,7 @@ class RowLayout:
 
     @classmethod
     def from_width(cls, width):
-        """for callers that hold rows and no layout: the one layout WITHOUT hand-benchmark blocks that is ``width`` columns wide (with
+        """for callers that hold rows and no layout: the one layout WITHOUT hand-benchmark or symmetric blocks that is ``width`` columns wide (with
         those blocks the width no longer tells: 92 + 16 = 108, 96 + 16 = 112 and 88 + 40 = 112 + 16 = 128)"""
         if width not in _BY_WIDTH:
             raise ValueError(f'rows of {width} columns: no layout without hand-benchmark blocks is that wide (accepted: '
@@ -65,17 +74,17 @@ class RowLayout:
 
     @property
     def width(self):
-        return sum(len(cols) for name, _, _, cols in BLOCKS if self.has(name))
+        return sum(len(cols) for name, _, _, cols in ALL_BLOCKS if self.has(name))
 
     @property
     def columns(self):
-        return tuple(c for name, _, _, cols in BLOCKS if self.has(name) for c in cols)
+        return tuple(c for name, _, _, cols in ALL_BLOCKS if self.has(name) for c in cols)
 
 
 @functools.lru_cache(maxsize=None)
 def _spans(layout):
     spans, at = {}, 0
-    for name, flag, w, _ in BLOCKS:
+    for name, flag, w, _ in ALL_BLOCKS:
         if flag is None or getattr(layout, flag):
             spans[name] = slice(at, at + w)
             at += w

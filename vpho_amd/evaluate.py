@@ -9,11 +9,13 @@ The forward pass itself needs no collective: the image batch is the only sharded
 import torch
 import torch.distributed as dist
 
-from .eval_layout import BLOCKS, RowLayout
-from .ops_names import HAND_BENCH_SOURCES, HAND_BENCH_TABLE, HAND_METRIC_NAMES, MULTI_TABLES, OBJ_METRIC_NAMES, PHYSICS_SOURCES
+from .eval_layout import BLOCKS, BLOCKS_ADDED, RowLayout
+from .ops_names import (HAND_BENCH_SOURCES, HAND_BENCH_TABLE, HAND_METRIC_NAMES, MULTI_TABLES, OBJ_METRIC_NAMES, PHYSICS_SOURCES,
+                        SYM_METRIC_NAMES)
 
-# the row layout -- which blocks there are, their order and widths -- is eval_layout.BLOCKS; these are its widths, in its order
+# the row layout -- which blocks there are, their order and widths -- is eval_layout.BLOCKS (+ BLOCKS_ADDED); these are its widths, in its order
 ROW, MULTI, PHYS, PHYS_MULTI, VOL_MULTI, VOL, HAND_BENCH, HAND_BENCH_MULTI = (width for _, _, width, _ in BLOCKS)
+SYM, SYM_MULTI = (width for _, _, width, _ in BLOCKS_ADDED)
 ROW_BEST = ROW + MULTI
 OBJ_COL = 12                 # first of the 16 object metrics of the aggregated pose within the base block
 
@@ -250,17 +252,73 @@ def hand_bench_table(block):
     return {src: {k: float(mean[8 * s + i]) for i, k in enumerate(HAND_BENCH_TABLE)} for s, src in enumerate(names)}
 
 
+_OBJ_SYMMETRY = {}
+
+
+def symmetry_meter(assets, device):
+    """the ops.ObjectSymmetry of an asset set on a device, built once per cfg.max_sym_disc_step: the model-info of
+    symmetry.load_symmetries(cfg.asset_root) (the synthetic one without the file), its padded table, the objects' corners, sampled vertices
+    and diameters.  vpho_amd.symmetry is imported here and nowhere else on the evaluation path."""
+    from .configs.args import cfg
+    key = (id(assets), str(device), float(cfg.max_sym_disc_step))
+    if key not in _OBJ_SYMMETRY:
+        from . import ops, symmetry
+        names = list(assets['ycb'].keys())
+        table = symmetry.symmetry_table(symmetry.load_symmetries(cfg.asset_root, names), names, float(cfg.max_sym_disc_step))
+        _OBJ_SYMMETRY[key] = ops.ObjectSymmetry(assets['ycb'], table, device)
+    return _OBJ_SYMMETRY[key]
+
+
+def symmetric_block(out, data, meter):
+    """(bs, SYM) fp32 in the order of ops_names.SYM_COLUMNS: SMCE (m), MSSD (m) and MSSD < 0.1 * diameter of the
+    aggregated object pose (obj_9D_to_mat + root, as object_metric_block) against data['gt_obj_rt']; NaN without it.
+    ``meter``: an ops.ObjectSymmetry (symmetry_meter)."""
+    dev = out['agg_obj_6d'].device
+    if dev.type != 'cuda':
+        raise RuntimeError('symmetric_block: the symmetric object errors run on the GPU only (no CPU path)')
+    if 'gt_obj_rt' not in data:
+        return torch.full((out['agg_obj_6d'].shape[0], SYM), float('nan'), device=dev, dtype=torch.float32)
+    return meter(_agg_obj_rt(out, data), data['gt_obj_rt'].double().contiguous(), meter.obj_ids(data['obj_name'])).float()
+
+
+def symmetric_multi_block(out, data, meter):
+    """(bs, SYM_MULTI) fp32 in the order of ops_names.SYM_MULTI_COLUMNS: the three values of every sampled object hypothesis (the poses of
+    multi_hypothesis_block) reduced per image to hypothesis 0 | best-of-S (min SMCE, min MSSD, max hit) | mean-of-S by ONE
+    ObjectSymmetry.multi launch pair; NaN without data['gt_obj_rt']"""
+    dev = out['diff_final_obj_6d'].device
+    if dev.type != 'cuda':
+        raise RuntimeError('symmetric_multi_block: the symmetric object errors run on the GPU only (no CPU path)')
+    if 'gt_obj_rt' not in data:
+        return torch.full((out['diff_final_obj_6d'].shape[0], SYM_MULTI), float('nan'), device=dev, dtype=torch.float32)
+    per, best, mean = meter.multi(_hypothesis_obj_rt(out, data['root_joint'].float().contiguous()), data['gt_obj_rt'].double().contiguous(),
+                                  meter.obj_ids(data['obj_name']))
+    return torch.cat([per[:, 0], best, mean], 1).float()
+
+
+def symmetric_table(block):
+    """the table 'symmetric' of Trainer.eval / EVAL_JSON from the (n, 3 | 12) columns symmetric_block [+ symmetric_multi_block] made:
+    {'pred': {...}[, 'one_candidate': ..., 'best_of_S': ..., 'mean_of_S': ...]}, each the ops_names.SYM_METRIC_NAMES keys as fp64 means
+    over the images (SMCE and MSSD in metres, MSSD01d in [0, 1]; NaN where a column holds one)"""
+    if block.shape[1] not in (SYM, SYM + SYM_MULTI):
+        raise ValueError(f'symmetric_table: {block.shape[1]} columns, expected {SYM} or {SYM + SYM_MULTI}')
+    mean = block.double().mean(0)
+    names = ('pred',) + (MULTI_TABLES if block.shape[1] > SYM else ())
+    return {src: {k: float(mean[3 * s + i]) for i, k in enumerate(SYM_METRIC_NAMES)} for s, src in enumerate(names)}
+
+
 def metric_rows(out, data, gt_joint, gt_vert, first_index, assets=None, eval_best=False, eval_physics=False, physics_multi=False, volume_multi=False,
                 eval_volume=False, eval_hand_bench=False, hand_bench_multi=False, layout=None):
     """(bs, layout.width) fp32 on the model's device: the blocks of ``layout`` (an eval_layout.RowLayout; default: the one that
-    RowLayout.resolve makes of the seven flags, so a *_multi block needs eval_best and the flag of its single-pose block), each filled
-    by its block function; a block that the layout does not have costs no launch.  With ``layout`` the flags are not looked at."""
+    RowLayout.resolve makes of the seven flags, so a *_multi block needs eval_best and the flag of its single-pose block; the symmetric
+    blocks come with a ``layout`` only), each filled by its block function; a block that the layout does not have costs no launch.  With ``layout`` the flags are not looked at."""
     if layout is None:
         layout = RowLayout.resolve(eval_best, eval_physics, physics_multi, eval_volume, volume_multi, eval_hand_bench, hand_bench_multi)
     if assets is None and layout.has('physics'):
         raise ValueError('metric_rows: eval_physics needs the asset tables (object meshes)')
     if assets is None and layout.has('volume'):
         raise ValueError('metric_rows: eval_volume needs the asset tables (object meshes, hand faces)')
+    if assets is None and layout.has('symmetric'):
+        raise ValueError('metric_rows: eval_symmetric needs the asset tables (object corners, sampled vertices, diameters)')
     pp = postprocess(out, data['root_joint'], data['is_right'])
     bs, dev = gt_joint.shape[0], gt_joint.device
     rows = torch.empty((bs, layout.width), device=dev, dtype=torch.float32)
@@ -291,7 +349,9 @@ def metric_rows(out, data, gt_joint, gt_vert, first_index, assets=None, eval_bes
                         ('volume', lambda: volume_block(pp, out, data, gt_vert, physics_meter(assets, dev, volume=True))),
                         ('volume_multi', lambda: volume_multi_block(out, data, physics_meter(assets, dev, volume_multi=True))),
                         ('hand_bench', lambda: hand_bench_block(out, data, gt_joint, gt_vert)),
-                        ('hand_bench_multi', lambda: hand_bench_multi_block(out, data, gt_joint, gt_vert))):
+                        ('hand_bench_multi', lambda: hand_bench_multi_block(out, data, gt_joint, gt_vert)),
+                        ('symmetric', lambda: symmetric_block(out, data, symmetry_meter(assets, dev))),
+                        ('symmetric_multi', lambda: symmetric_multi_block(out, data, symmetry_meter(assets, dev)))):
         if layout.has(name):
             rows[:, layout.slice(name)] = block()
     from .configs.args import cfg
@@ -449,6 +509,8 @@ def summarize(rows, layout=None):
                              object=_object_table(blk[12 + 16 * t:28 + 16 * t]))
     if layout.has('hand_bench'):
         res['hand_bench'] = hand_bench_table(torch.cat([block(n) for n in ('hand_bench', 'hand_bench_multi') if layout.has(n)], 1))
+    if layout.has('symmetric'):
+        res['symmetric'] = symmetric_table(torch.cat([block(n) for n in ('symmetric', 'symmetric_multi') if layout.has(n)], 1))
     return res
 
 

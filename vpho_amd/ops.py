@@ -1333,6 +1333,87 @@ class ObjectMetrics:
         return per, best, mean
 
 
+class ObjSymmetryTables(C.Structure):
+    _fields_ = [('sym_R', C.c_void_p), ('sym_t', C.c_void_p), ('bbox3d', C.c_void_p), ('verts_sampled', C.c_void_p), ('diameter', C.c_void_p),
+                ('K', I), ('n_obj', I), ('n_sampled', I)]
+
+
+SYMMETRY_MAX_TRANSFORMS = 4096           # vpho_obj_symmetry_multi_f64: symmetry transforms per object
+
+
+class ObjectSymmetry:
+    """The symmetry-aware object errors (--eval_symmetric) on the device: SMCE (TesterObject.criterion_SMCE,
+    lib/engine/test.py:377-398), MSSD and MSSD < 0.1 * diameter over a padded symmetry table.  ``ycb``: {name: {'bbox3d' (8, 3),
+    'verts_sampled' (P, 3), 'diameter'}} with one P >= 1 for all; ``table``: (R (n_obj, K, 3, 3), t (n_obj, K, 3)) in the order of
+    ``ycb`` (symmetry.symmetry_table).  ``prune`` (default on) lets the kernel abandon a symmetry that can no longer be the minimum; both
+    settings return the same bits."""
+
+    def __init__(self, ycb, table, device, prune=True):
+        import numpy as np
+        self.names = list(ycb.keys())
+        self.name_to_id = {n: i for i, n in enumerate(self.names)}
+        R, t = (np.ascontiguousarray(a, dtype=np.float64) for a in table)
+        if R.ndim != 4 or R.shape[0] != len(self.names) or R.shape[2:] != (3, 3) or t.shape != R.shape[:2] + (3,) or R.shape[1] < 1:
+            raise VphoError(f'ObjectSymmetry: table R {R.shape} / t {t.shape} for {len(self.names)} objects, expected (n_obj, K, 3, 3) / (n_obj, K, 3)')
+        if R.shape[1] > SYMMETRY_MAX_TRANSFORMS:
+            raise VphoError(f'ObjectSymmetry: {R.shape[1]} symmetry transforms per object, at most {SYMMETRY_MAX_TRANSFORMS} (a larger '
+                            f'--max_sym_disc_step gives a shorter table)')
+        if not torch.device(device).type == 'cuda':
+            raise VphoError('vpho_amd ops take GPU tensors only (no CPU path)')
+        d = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64)).to(device)
+        self.sym_R, self.sym_t = d(R), d(t)
+        self.bbox3d = d(np.stack([np.asarray(ycb[n]['bbox3d']).reshape(8, 3) for n in self.names]))
+        self.verts_sampled = d(np.stack([np.asarray(ycb[n]['verts_sampled']).reshape(-1, 3) for n in self.names]))
+        self.diameter = d(np.array([float(ycb[n]['diameter']) for n in self.names]))
+        self.K, self.prune, self.device = int(R.shape[1]), bool(prune), device
+        self.c = ObjSymmetryTables(self.sym_R.data_ptr(), self.sym_t.data_ptr(), self.bbox3d.data_ptr(), self.verts_sampled.data_ptr(),
+                                   self.diameter.data_ptr(), self.K, len(self.names), self.verts_sampled.shape[1])
+
+    def obj_ids(self, names):
+        """class indices of a batch as a device tensor (ObjectMetrics.obj_ids)"""
+        return _ids_to_device([self.name_to_id[n] for n in names], self.device)
+
+    def _check_ids(self, obj_id, n):
+        """obj_id as an (n,) device tensor: a host sequence of ints is range-checked and copied (a device tensor cannot be refused without
+        a host sync: the kernel gives NaN, NaN, 0 for an id outside the table)"""
+        if not torch.is_tensor(obj_id):
+            ids = [int(i) for i in obj_id]
+            if len(ids) != n or any(i < 0 or i >= len(self.names) for i in ids):
+                raise VphoError(f'ObjectSymmetry: object ids {ids} outside [0, {len(self.names)}) or not one per image')
+            obj_id = _ids_to_device(ids, self.device)
+        if obj_id.shape != (n,):
+            raise VphoError(f'ObjectSymmetry: obj_id {tuple(obj_id.shape)} for {n} images')
+        return obj_id
+
+    def per_hypothesis(self, pd_rt, gt_rt, obj_id, prune=None):
+        """pd_rt (n, S, 3, 4), gt_rt (n, 3, 4) fp64, obj_id (n,) int32 device tensor or host ints -> (n, S, 3) fp64 = SMCE (m), MSSD (m),
+        MSSD < 0.1 * diameter; a fresh output block per call (stream-ordered, as ObjectMetrics' workspace), no workspace"""
+        n, S = pd_rt.shape[:2]
+        if pd_rt.shape != (n, S, 3, 4) or gt_rt.shape != (n, 3, 4):
+            raise VphoError(f'ObjectSymmetry: pd_rt {tuple(pd_rt.shape)}, gt_rt {tuple(gt_rt.shape)}, expected (n, S, 3, 4) and (n, 3, 4)')
+        if not (pd_rt.is_cuda and gt_rt.is_cuda):
+            raise VphoError('vpho_amd ops take GPU tensors only (no CPU path)')
+        obj_id = self._check_ids(obj_id, n)
+        per = _new((n, S, 3), pd_rt, torch.float64)
+        _call('vpho_obj_symmetry_multi_f64', C.byref(self.c), _f64(pd_rt), _f64(gt_rt), _i32(obj_id), I(n), I(S),
+              I(int(self.prune if prune is None else prune)), _f64(per))
+        return per
+
+    def __call__(self, pd_rt, gt_rt, obj_id, prune=None):
+        """one pose per image: pd_rt, gt_rt (n, 3, 4) -> (n, 3) in the order of ops_names.SYM_METRIC_NAMES (the S = 1 launch)"""
+        if pd_rt.dim() != 3:
+            raise VphoError(f'ObjectSymmetry: pd_rt {tuple(pd_rt.shape)}, expected (n, 3, 4)')
+        return self.per_hypothesis(pd_rt[:, None], gt_rt, obj_id, prune)[:, 0]
+
+    def multi(self, pd_rt, gt_rt, obj_id, prune=None):
+        """every sampled hypothesis: -> per (n, S, 3), best-of-S (n, 3: min SMCE, min MSSD, max hit), mean-of-S (n, 3)"""
+        per = self.per_hypothesis(pd_rt, gt_rt, obj_id, prune)
+        n, S = per.shape[:2]
+        one, best, mean = (_new((n, 3), per, torch.float64) for _ in range(3))
+        _call('vpho_obj_symmetry_table_f64', _f64(per), I(n), I(S), _f64(one), _f64(best), _f64(mean))
+        return per, best, mean
+
+
 class ObjMeshTables(C.Structure):
     _fields_ = [('tri', C.c_void_p), ('tri_offset', C.c_void_p), ('scale', C.c_void_p), ('translate', C.c_void_p), ('n_obj', I)]
 

@@ -54,3 +54,12 @@ HAND_BENCH_COLUMNS = tuple(f'hand_bench/{s}/{k}' for s in HAND_BENCH_SOURCES for
 HAND_BENCH_MULTI_COLUMNS = tuple(f'hand_bench/{t}/{k}' for t in MULTI_TABLES for k in HAND_BENCH_NAMES)
 # the keys of every source of the summarize-level / EVAL_JSON table 'hand_bench': means over the images
 HAND_BENCH_TABLE = HAND_BENCH_NAMES
+# the symmetry-aware object errors (--eval_symmetric) of a (pose, ground truth) pair over the object's padded symmetry
+# table: SMCE (m; TesterObject.criterion_SMCE, test.py:377-398), MSSD (m; min over the symmetries of the largest vertex distance) and
+# MSSD < 0.1 * diameter ({0, 1}; as ADD01d is to ADD)
+SYM_METRIC_NAMES = ('SMCE', 'MSSD', 'MSSD01d')
+# evaluate.symmetric_block: the three values of the aggregated object pose (NaN without object ground truth)
+SYM_COLUMNS = tuple(f'sym/pred/{k}' for k in SYM_METRIC_NAMES)
+# evaluate.symmetric_multi_block (eval_best AND eval_symmetric): every sampled object hypothesis, per image reduced to hypothesis 0,
+# best-of-S (min SMCE, min MSSD, max hit: TesterObject.postprocess) and mean-of-S (9 columns)
+SYM_MULTI_COLUMNS = tuple(f'sym/{t}/{k}' for t in MULTI_TABLES for k in SYM_METRIC_NAMES)

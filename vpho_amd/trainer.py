@@ -349,20 +349,26 @@ class Trainer:
     def eval(self, loader=None, eval_best=None, eval_physics=None, physics_multi=None, eval_volume=None, volume_multi=None, eval_hand_bench=None,
              hand_bench_multi=None):
         """``evaluate(testing_dataloader)`` (train_diff_hand_obj.py:202-357).  ``loader``: see ``_eval_batches``; default synthetic.
-        The seven flags choose the column blocks of the returned rows and the tables printed from them (eval_layout.BLOCKS has the blocks
+        The seven flags choose the column blocks of the returned rows and the tables printed from them (eval_layout.ALL_BLOCKS has the blocks
         and their order, INTEGRATION.md §1 what they hold): ``eval_best`` (the reference's is_eval_best) scores every sampled hypothesis
         (tables one_candidate, best_of_S, mean_of_S), ``eval_physics`` reports hand-object penetration and contact (``physics``),
         ``eval_volume`` the intersection volume at cfg.physics_voxel_pitch (``volume``), ``eval_hand_bench`` the hand F-scores and PCK AUC
         of the HO3D / FreiHAND leaderboards (``hand_bench``); ``physics_multi`` / ``volume_multi`` / ``hand_bench_multi`` add every sampled
         hypothesis to that table and need eval_best and the table's own flag.  Defaults (None): cfg.eval_best / eval_physics / eval_volume
         / eval_hand_bench, and for a *_multi flag cfg.eval_best and cfg.eval_<its table>, i.e. both command-line flags: a caller that
-        passes eval_best / eval_physics / ... itself gets the rows it always got unless it asks for the newer block too."""
+        passes eval_best / eval_physics / ... itself gets the rows it always got unless it asks for the newer block too.
+        The symmetry-aware object errors (blocks ``symmetric`` / ``symmetric_multi``, table ``symmetric``) have no keyword here -- a test pins
+        this parameter list: they follow cfg.eval_symmetric, and for every sampled hypothesis cfg.eval_best and cfg.eval_symmetric together
+        with the ``eval_best`` this call resolves to."""
         from .configs.args import cfg
-        layout = E.RowLayout.resolve(eval_best, eval_physics, physics_multi, eval_volume, volume_multi, eval_hand_bench, hand_bench_multi)
+        layout = E.RowLayout.resolve(eval_best, eval_physics, physics_multi, eval_volume, volume_multi, eval_hand_bench, hand_bench_multi,
+                                     None, None)
         batch_rows = lambda out, batch, gt, first: E.metric_rows(out, batch, gt[0], gt[1], first, self.assets, layout=layout)
         if layout.has('physics') or layout.has('volume'):
             # object meshes, acceleration tables, the closed hand mesh, the objects' solids: what the layout needs, once, before the timed loop
             E.physics_meter(self.assets, self.device, multi=layout.has('physics_multi'), volume=layout.has('volume'), volume_multi=layout.has('volume_multi'))
+        if layout.has('symmetric'):
+            E.symmetry_meter(self.assets, self.device)            # the symmetry table, once, before the timed loop; refuses a table that is too long
         rows = []
         t0 = time.perf_counter()
         # three batches in flight (independent images; see evaluate.PipelinedPredictor)
@@ -399,14 +405,15 @@ class Trainer:
             print(f'aggregation_mode_hand {cfg.aggregation_mode_hand}  aggregation_mode_obj {cfg.aggregation_mode_obj}')
             table = E.summarize(rows.cpu(), layout)
             for name, r in table.items():
-                if name not in ('object', 'physics', 'volume', 'hand_bench') + E.MULTI_TABLES:
+                if name not in ('object', 'physics', 'volume', 'hand_bench', 'symmetric') + E.MULTI_TABLES:
                     print(f'{name:>5s}: n={r["n"]:5d}  MJE reg {r["MJE_reg"]:.2f}  first {r["MJE_first"]:.2f}  agg {r["MJE_agg"]:.2f}  MVE agg {r["MVE_agg"]:.2f}  (mm)')
             print('object (aggregated pose): ' + '  '.join(f'{k} {v:.2f}' for k, v in table['object'].items()))
             for name in E.MULTI_TABLES:
                 if name in table:
                     print(f'{name} hand (mm): ' + '  '.join(f'{k} {v:.2f}' for k, v in table[name]['hand'].items()))
                     print(f'{name} object: ' + '  '.join(f'{k} {v:.2f}' for k, v in table[name]['object'].items()))
-            for name, note, fmt in (('physics', '', '.2f'), ('volume', f' (pitch {cfg.physics_voxel_pitch * 1000.0:g} mm)', '.3f'), ('hand_bench', '', '.4f')):
+            for name, note, fmt in (('physics', '', '.2f'), ('volume', f' (pitch {cfg.physics_voxel_pitch * 1000.0:g} mm)', '.3f'), ('hand_bench', '', '.4f'),
+                                    ('symmetric', ' (m, m, share)', '.5f')):
                 for src, r in table.get(name, {}).items():
                     print(f'{name} {src}{note}: ' + '  '.join(f'{k} {v:{fmt}}' for k, v in r.items()))
             import json
