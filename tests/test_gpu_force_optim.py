@@ -117,3 +117,165 @@ def _inputs8(assets, B, seed):
     fc = torch.rand(B, 32, generator=g)
     grasped = torch.rand(B, generator=g) < 0.8
     return v.contiguous(), grav.contiguous(), com.contiguous(), fc.contiguous(), grasped
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# The kernel against the float64 reference (tests/_force_fp64.py) at the workgroup shapes, the phase and report edges, the
+# bias-correction table's refills and in its exact form.
+#
+# Every bound is k * max(noise, floor) per output (scale, weight, force_local, force_global and each of the four losses) of EVERY
+# batch: `noise` is the reference's own float32 run against its float64 run of that batch, computed here from the case's inputs; `floor`
+# is 4 float32 ulps of the output's largest magnitude (for cases like iters = 1, where noise is 1e-9).  k was set once from a run on the
+# MI355X that printed error / max(noise, floor) for every case and output (docs/LOG.md has the table): the next power of two above the
+# worst ratio, never a number taken from a failing assertion.
+K_FAST = 32       # the default form (1-ulp v_rcp / v_sqrt / v_exp / v_log): worst 16.7 (loss_dist, B = 4 x 2); the table cases 0.95 .. 4.6
+K_EXACT = 16      # VPHO_FORCE_EXACT=1 (correctly rounded division, sqrtf, expf, logf): worst 12.4 (loss_gravity, degenerate B = 17 x 3)
+K_FRAMES = 2      # anchor_frames_kernel: worst 1.18 (frames, one hand)
+# tests/test_force_fp64_cpu.py holds, on the reference alone, that a wrong step count, a missing moment reset or a stale table shifts
+# every long case by at least 10 units (measured: 277 to 193 000), and docs/LOG.md lists which of these tests failed for each of six
+# deliberately wrong builds of the kernel.  One sample of the degenerate rows is ill-conditioned in the reference itself (the 1e3
+# contact value: its neighbours' scales are driven through zero, noise 8e-3 in `scale` after 80 phase-2 steps); it loosens the
+# `scale` bound of the batch it sits in, and of no other batch.
+
+
+def _agg(assets):
+    from vpho_amd import ops
+    from vpho_amd.assets import ANCHOR_SKELETON
+    return ops.Aggregation(assets, ANCHOR_SKELETON, 'cuda')
+
+
+def _check(label, got, ins, ref64, ref32, k):
+    """every output of every batch within k units of float64 (k = K_FAST = 32 or K_EXACT = 16: measured worst 16.7 and 12.4); exact
+    zeros for un-grasped samples.  Prints the ratios before asserting."""
+    from tests import _force_fp64 as R
+    ratio = R.ratios(got, ref64, ref32)
+    print(label, {o: round(r, 3) for o, r in ratio.items()})
+    for o in R.OUTPUTS:
+        assert np.isfinite(got[o]).all(), (label, o)
+        assert got[o].shape == ref64[o].shape, (label, o)
+    grasped = ins[4].numpy()
+    for o in ('force_local', 'force_global'):
+        assert (got[o][~grasped] == 0).all(), (label, o)
+        assert (ref64[o][~grasped] == 0).all()
+    assert all(r <= k for r in ratio.values()), (label, ratio)
+    return ratio
+
+
+def _run_case(assets, kind, B, n_batches, iters, phase1, lr, k=None):
+    from tests import _force_fp64 as R
+    from tests._force_exact_driver import launch
+    ins, ref64, ref32 = R.case(kind, B, n_batches, iters, phase1, lr, R.SEED)
+    got = launch(_agg(assets), ins, B, iters, phase1, lr)
+    _check(f'{kind} B={B}x{n_batches} iters={iters} phase1={phase1} lr={lr}:', got, ins, ref64, ref32, K_FAST if k is None else k)
+    return ins, got, ref64
+
+
+def _cases(name):
+    from tests import _force_fp64 as R
+    return [(kind,) + s for s in R.SHAPES for kind in ('plain', 'degenerate')] if name == 'shapes' else list(getattr(R, name))
+
+
+@pytest.mark.parametrize('kind,B,n_batches,iters,phase1', _cases('shapes'))
+def test_workgroup_shapes_match_fp64(assets, kind, B, n_batches, iters, phase1):
+    """B = 64 (all 1024 threads valid, the production batch), 63 (one idle row), 17 (B % 4 != 0: the float4 read of the batch mean
+    crosses into rows past B, three batches in flight), 4 and 1, on the plain recipe and on the degenerate rows (no contact anchor, one
+    contact anchor, values at and next to the 0.1 threshold, all 32 equal, one huge value, zero gravity; batches un-grasped throughout)."""
+    from tests import _force_fp64 as R
+    ins, got, ref64 = _run_case(assets, kind, B, n_batches, iters, phase1, 1e-3)
+    if kind == 'degenerate':
+        grasped = ins[4].numpy()
+        assert grasped[:B].all() and (n_batches == 1 or not grasped[B:2 * B].any())
+    out = ~R.contact_mask(ins[3]).numpy()
+    assert (got['weight'][out] == 0).all()
+
+
+def test_middle_batch_of_three_is_its_own_launch(assets):
+    """B = 17, three batches in one launch: the middle one equals a launch of that batch alone, bit for bit, in every output"""
+    from tests import _force_fp64 as R
+    from tests._force_exact_driver import launch
+    B, n_batches, iters, phase1 = 17, 3, 120, 40
+    agg = _agg(assets)
+    for kind in ('plain', 'degenerate'):
+        ins = R.build(kind, B, n_batches, R.SEED)
+        three = launch(agg, ins, B, iters, phase1, 1e-3)
+        alone = launch(agg, tuple(t[B:2 * B].contiguous() for t in ins), B, iters, phase1, 1e-3)
+        for o in R.OUTPUTS:
+            rows = slice(1, 2) if o.startswith('loss_') else slice(B, 2 * B)
+            assert np.array_equal(three[o][rows], alone[o]), (kind, o)
+
+
+@pytest.mark.parametrize('B', _cases('PHASE_B'))
+@pytest.mark.parametrize('iters,phase1', _cases('PHASE_EDGES'))
+def test_phase_and_report_edges_match_fp64(assets, B, iters, phase1):
+    """iters = 1 (the report comes before the first update, in either phase), phase1 = iters - 1 (the report lands in the iteration that
+    zeroes the moments), phase1 >= iters (phase 2 never entered), phase1 = 0 (phase 1 never entered).  Besides the float64 comparison,
+    the invariants of an anchor out of contact (tests/test_force_fp64_cpu.py) on the kernel's own outputs: its weight row is exactly 0,
+    its scale is 0.05 * (1 - lr * 0.01) ** n after n = max(0, iters - phase1) phase-2 steps -- to (2 n + 1) * 2^-24 relative: float32(0.05)
+    and float32(1 - 1e-5) are each rounded once (2^-25, 2^-24 of the decay per step) and each product once (2^-24) -- and with
+    phase1 >= iters every scale is float32(0.05) to the bit."""
+    from tests import _force_fp64 as R
+    lr = 1e-3
+    ins, got, ref64 = _run_case(assets, 'plain' if B == 5 else 'degenerate', B, 1, iters, phase1, lr)
+    out = ~R.contact_mask(ins[3]).numpy()
+    assert out.any() and not out.all()
+    assert (got['weight'][out] == 0).all()
+    n = max(0, iters - phase1)
+    err = np.abs(got['scale'][out].astype(np.float64) - R.masked_scale(iters, phase1, lr)).max()
+    print('masked scale err', err, 'steps', n)
+    assert err <= (2 * n + 1) * 2.0 ** -24 * 0.05
+    if phase1 >= iters:
+        assert (got['scale'] == np.float32(0.05)).all()
+
+
+@pytest.mark.parametrize('iters,phase1,lr', _cases('TABLE'))
+def test_table_refills_match_fp64(assets, iters, phase1, lr):
+    """The bias-correction table (1024 slots, refilled every 1024 iterations, the step count restarting with phase 2): slot 1023 as the
+    last one read, slot 0 of the second table, 76 iterations on it with the phase switch before it and inside it, a switch at the
+    refill, and two refills.  lr is small so that the float32 trajectory is still determined: noise about 5e-6 where the parameters
+    move about 1e-2."""
+    from tests import _force_fp64 as R
+    _run_case(assets, 'plain', R.TABLE_B, 1, iters, phase1, lr)
+
+
+def test_exact_form_matches_fp64(assets, tmp_path):
+    """VPHO_FORCE_EXACT=1 (force_optim_kernel<true>) in ONE fresh child process (the switch is read once per process): B = 64, the
+    degenerate B = 17 and the (1100, 1030) table case, against the same float64 references.  Its bound is no wider than the fast
+    form's, and its outputs are not the fast form's bits (the child did run the other instantiation)."""
+    import os
+    import subprocess
+    import sys
+    from tests import _force_fp64 as R
+    from tests._force_exact_driver import launch
+    assert K_EXACT <= K_FAST
+    path = str(tmp_path / 'exact.npz')
+    driver = os.path.join(os.path.dirname(os.path.abspath(__file__)), '_force_exact_driver.py')
+    r = subprocess.run([sys.executable, driver, path], env=dict(os.environ, VPHO_FORCE_EXACT='1'), capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
+    z = np.load(path)
+    agg, same = _agg(assets), True
+    for name, (kind, B, n_batches, iters, phase1, lr) in R.EXACT_CASES.items():
+        ins, ref64, ref32 = R.case(kind, B, n_batches, iters, phase1, lr, R.SEED)
+        exact = {o: z[f'{name}/{o}'] for o in R.OUTPUTS}
+        fast = launch(agg, ins, B, iters, phase1, lr)
+        print(name, 'fast ', {o: round(v, 3) for o, v in R.ratios(fast, ref64, ref32).items()})
+        _check(f'{name} exact', exact, ins, ref64, ref32, K_EXACT)
+        same = same and all(np.array_equal(exact[o], fast[o]) for o in ('scale', 'weight'))
+    assert not same
+
+
+@pytest.mark.parametrize('n_hands', [1, 70])
+def test_anchor_frames_match_fp64(assets, n_hands):
+    """Aggregation.anchor_frames against vert2anchor in float64, one hand and 70 (more blocks than one wave of them); the unit is the
+    float32 oracle's own distance to float64, or 4 float32 ulps of the output's magnitude"""
+    from oracle.aggregation import vert2anchor
+    from tests import _force_fp64 as R
+    from vpho_amd.assets import ANCHOR_SKELETON
+    v = R.inputs(assets, n_hands, seed=3)[0]
+    p64, f64 = vert2anchor(assets['anchor'], ANCHOR_SKELETON, v.double())
+    p32, f32 = vert2anchor(assets['anchor'], ANCHOR_SKELETON, v)
+    p, f = _agg(assets).anchor_frames(v.cuda())
+    for name, got, r64, r32 in (('points', p, p64, p32), ('frames', f, f64, f32)):
+        unit = max((r32.double() - r64).abs().max().item(), R.FLOOR_ULPS * R.EPS32 * r64.abs().max().item())
+        err = (got.cpu().double() - r64).abs().max().item()
+        print(n_hands, name, 'err', err, 'unit', unit, 'ratio', err / unit)
+        assert err <= K_FRAMES * unit, (name, err, unit)
