@@ -699,6 +699,48 @@ typedef struct {
 } vpho_hand_surface_table;
 VPHO_API int vpho_hand_surface_f32(const vpho_hand_surface_table* t, const float* verts, int n, float* verts_filled, float* normals_filled,
                           void* stream);
+/* The hand contact map of EVERY sampled hypothesis and its agreement with the annotation's (--eval_grasp), appended
+ * within ABI version 13.  vpho_contact_multi_f32 is the hand -> object direction of vpho_contact_detect_f32 for n * S (hand hypothesis s,
+ * object hypothesis s) pairs in the object's MODEL frame: no posed object vertex is written, and the nearest vertex comes from a pruned
+ * walk that returns the index of the scan of all vertices (csrc/contact_multi.hip has the argument).
+ * vpho_obj_vertex_accel (built on the host, vpho_amd/grasp_eval.py: vertex_accel), objects concatenated, none padded: vert, the FULL
+ * vertices of every object in Morton order (fp64, model frame), index, each one's ORIGINAL index within its object; object o owns the
+ * clusters [clu_offset[o], clu_offset[o + 1]), cluster k the rows [clu_start[k], clu_start[k + 1]) of vert / index (32 rows, fewer in
+ * an object's last cluster; the kernel takes any tiling), clu_sphere[k] = (centre xyz, radius): the centre of the rows' bounding box and
+ * their largest distance from it, enlarged on the host by (1 + 2^-30) and by 2^-30 of the object's bounding-box diagonal.
+ * hand_verts, hand_normals [n][S][Nh][3] fp32: the filled hand surface of vpho_hand_surface_f32 in ITS frame (flipped to a right hand,
+ * relative to the root joint); root [n][3] fp64, is_right [n], obj_rt [n][S][3][4] fp64 [R | t] (model -> camera), obj_id [n].  All in
+ * fp64: c = (sg h_x, h_y, h_z) + root with sg = +1 / -1 for a right / left hand, p = R^T (c - t), m = R^T (sg n_x, n_y, n_z); v* = the
+ * vertex with the smallest |p - v|^2, the smaller original index on an exact tie; nd = (p - v*) . m, vd = |(p - v*) - nd m|; contact iff
+ * normal_lo < nd < normal_hi and vd < vertical_thresh (the fp32 gates widened to fp64).  weight [n][S][Nh] = the double-sigmoid weight of
+ * vpho_contact_detect_f32 at nd, over its value at 0, clamped to [0, 1], rounded to fp32; 0 without contact.  nn_index (optional)
+ * [n][S][Nh] = v*'s original index where in contact, else -1; nd, vd (optional) [n][S][Nh] fp64, of every vertex.  A pair with a
+ * non-finite pose, root, hand vertex or normal, an obj_id outside [0, n_obj) or an object without vertices: NaN in weight, nd and vd and
+ * -1 in nn_index for the whole pair, nothing out of bounds is read.  One workgroup per pair on grid.x: n * S <= 2147483647.  The
+ * thresholds must satisfy normal_lo < decay_lo < decay_hi < normal_hi; n == 0 is a no-op.  Deterministic.
+ * vpho_contact_agreement_f32: weight [n][S][Nh] against weight_gt [n][Nh], with c = weight > 0 and g = weight_gt > 0; force_contact
+ * [n][S][32] / is_grasped [n][S] (vpho_force_contact_f32 over the n * S maps) against force_contact_gt [n][32] / is_grasped_gt [n].
+ * counts [n][S][3] = TP, P, G (|c & g|, |c|, |g|); values [n][S][8] fp64 = IoU = TP / (P + G - TP), precision = TP / P, recall = TP / G,
+ * F1 = 2 TP / (P + G) (each NaN when its denominator is 0), MAE = mean |weight - weight_gt| over Nh, anchor_agree = the share of the 32
+ * anchors with equal (force_contact > 0), grasped = is_grasped, grasp_agree = (is_grasped == is_grasped_gt).  A pair with a NaN in either
+ * map: NaN values, zero counts.  table [n][24] = the values of hypothesis 0 | best-of-S (each value's maximum on its own, MAE's minimum)
+ * | mean-of-S (sum in ascending s over how many), both over the hypotheses where the value is not NaN, NaN where it never is.
+ * n == 0 is a no-op.  Deterministic (fixed summation order, no atomics). */
+typedef struct vpho_obj_vertex_accel {
+    const double* vert;            /* [clu_start[clu_offset[n_obj]]][3] */
+    const int* index;              /* [clu_start[clu_offset[n_obj]]] */
+    const int* clu_offset;         /* [n_obj + 1] */
+    const int* clu_start;          /* [clu_offset[n_obj] + 1] */
+    const double* clu_sphere;      /* [clu_offset[n_obj]][4] */
+    int n_obj;
+} vpho_obj_vertex_accel;
+VPHO_API int vpho_contact_multi_f32(const vpho_obj_vertex_accel* acc, const float* hand_verts, const float* hand_normals, int n, int S, int Nh,
+                           const double* root, const unsigned char* is_right, const double* obj_rt, const int* obj_id,
+                           float normal_lo, float normal_hi, float vertical_thresh, float decay_lo, float decay_hi,
+                           float* weight, int* nn_index, double* nd, double* vd, void* stream);
+VPHO_API int vpho_contact_agreement_f32(const float* weight, const float* weight_gt, const float* force_contact, const unsigned char* is_grasped,
+                               const float* force_contact_gt, const unsigned char* is_grasped_gt, int n, int S, int Nh,
+                               int* counts, double* values, double* table, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Training of the score networks (first slice): the denoising-score-matching step of

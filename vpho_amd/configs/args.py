@@ -27,6 +27,7 @@ class Config:
         self.eval_hand_bench = False  # also report the hand F@5 / F@15 and PCK AUC of the HO3D / FreiHAND leaderboards
         self.eval_symmetric = False   # also report the symmetry-aware object errors SMCE / MSSD / MSSD01d
         self.max_sym_disc_step = 0.01         # discretisation of a continuous symmetry: the reference's constant (test.py:205)
+        self.eval_grasp = False       # also report the contact-map and grasp agreement with the annotation; gates: contact_*
         self.mark = ''
         self.random_seed = 0
         self.output_dir = 'output'
@@ -119,6 +120,7 @@ def _parser():
     p.add_argument('--eval_hand_bench', action='store_true')
     p.add_argument('--eval_symmetric', action='store_true')
     p.add_argument('--max_sym_disc_step', type=float, default=0.01)
+    p.add_argument('--eval_grasp', action='store_true')
     p.add_argument('--mark', type=str, default='')
     p.add_argument('--random_seed', type=int, default=0)
     p.add_argument('--output_dir', type=str, default='output')

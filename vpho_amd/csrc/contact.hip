@@ -5,6 +5,7 @@
 // evaluations, 12*(nq+nt) B algorithmic traffic per sample).  Ties: smaller target index.
 #include "common.h"
 #include "../../include/vpho_hip.h"
+#include "contact_common.h"
 
 namespace {
 
@@ -18,13 +19,6 @@ struct ContactArgs {
     float* weight;      // (n, nq)
     int* nn_index;      // (n, nq) or NULL: index of the nearest target where in contact, else -1
 };
-
-__device__ inline double contact_weight(double x, double mid1, double mid2) {
-    const double m1 = 1.0 + exp(-1600.0 * (x - mid1));
-    const double m2 = 1.0 + exp(1600.0 * (x - mid2));
-    if (!isfinite(m1) || !isfinite(m2)) return 0.0;
-    return 1.0 / (m1 * m2 + 1e-10);
-}
 
 __global__ __launch_bounds__(256) void contact_kernel(const ContactArgs a) {
     __shared__ float tile[CT_TILE * 3];

@@ -20,11 +20,14 @@ BLOCKS = (('base', None, 28, N.BASE_COLUMNS),
 # columns walk ALL_BLOCKS
 BLOCKS_ADDED = (('symmetric', 'eval_symmetric', 3, N.SYM_COLUMNS),
                 ('symmetric_multi', 'symmetric_multi', 9, N.SYM_MULTI_COLUMNS))
-ALL_BLOCKS = BLOCKS + BLOCKS_ADDED
+# ... and BLOCKS_ADDED was pinned to its two entries in turn (tests/test_symmetry_cpu.py): the blocks of --eval_grasp follow it
+BLOCKS_GRASP = (('grasp', 'eval_grasp', 8, N.GRASP_COLUMNS),
+                ('grasp_multi', 'grasp_multi', 24, N.GRASP_MULTI_COLUMNS))
+ALL_BLOCKS = BLOCKS + BLOCKS_ADDED + BLOCKS_GRASP
 assert all(len(cols) == w for _, _, w, cols in ALL_BLOCKS)
 # each *_multi block (every sampled hypothesis) needs eval_best and the flag of its single-pose block
 MULTI_NEEDS = {'physics_multi': 'eval_physics', 'volume_multi': 'eval_volume', 'hand_bench_multi': 'eval_hand_bench',
-               'symmetric_multi': 'eval_symmetric'}
+               'symmetric_multi': 'eval_symmetric', 'grasp_multi': 'eval_grasp'}
 
 
 @dataclass(frozen=True)
@@ -37,6 +40,8 @@ class RowLayout:
     volume_multi: bool = False
     eval_hand_bench: bool = False
     hand_bench_multi: bool = False
+    eval_grasp: bool = False                 # set by with_grasp; the last two fields and resolve's last two parameters are pinned by a test
+    grasp_multi: bool = False
     eval_symmetric: bool = False
     symmetric_multi: bool = False
 
@@ -45,20 +50,29 @@ class RowLayout:
                 hand_bench_multi=False, eval_symmetric=False, symmetric_multi=False):
         """The layout of the nine flags.  None means 'follow the configuration': cfg.eval_best / eval_physics / eval_volume /
         eval_hand_bench / eval_symmetric for those five, and for a *_multi flag 'both command-line flags', cfg.eval_best and cfg.eval_<its block>, so
-        that a caller who passes the older flags itself gets the rows it always got."""
-        f = dict(zip(cls.__dataclass_fields__, (eval_best, eval_physics, physics_multi, eval_volume, volume_multi, eval_hand_bench, hand_bench_multi,
-                                                     eval_symmetric, symmetric_multi)))
+        that a caller who passes the older flags itself gets the rows it always got.  The grasp blocks: ``with_grasp`` on the result."""
+        return cls._settle(dict(eval_best=eval_best, eval_physics=eval_physics, physics_multi=physics_multi, eval_volume=eval_volume,
+                                volume_multi=volume_multi, eval_hand_bench=eval_hand_bench, hand_bench_multi=hand_bench_multi,
+                                eval_symmetric=eval_symmetric, symmetric_multi=symmetric_multi))
+
+    def with_grasp(self, eval_grasp=False, grasp_multi=False):
+        """this layout with the blocks of --eval_grasp behind the others: ``eval_grasp`` / ``grasp_multi`` by resolve's rules (None: cfg.eval_grasp /
+        cfg.eval_best and cfg.eval_grasp; grasp_multi needs this layout's eval_best and eval_grasp)"""
+        return self._settle({**{k: getattr(self, k) for k in self.__dataclass_fields__}, 'eval_grasp': eval_grasp, 'grasp_multi': grasp_multi})
+
+    @classmethod
+    def _settle(cls, f):
         if None in f.values():
             from .configs.args import cfg
             for k in [k for k, v in f.items() if v is None]:
                 f[k] = (cfg.eval_best and getattr(cfg, MULTI_NEEDS[k])) if k in MULTI_NEEDS else getattr(cfg, k)
         for k, single in MULTI_NEEDS.items():
-            f[k] = f[k] and f['eval_best'] and f[single]
+            f[k] = f.get(k, False) and f['eval_best'] and f.get(single, False)
         return cls(**{k: bool(v) for k, v in f.items()})
 
     @classmethod
     def from_width(cls, width):
-        """for callers that hold rows and no layout: the one layout WITHOUT hand-benchmark or symmetric blocks that is ``width`` columns wide (with
+        """for callers that hold rows and no layout: the one layout WITHOUT hand-benchmark, symmetric or grasp blocks that is ``width`` columns wide (with
         those blocks the width no longer tells: 92 + 16 = 108, 96 + 16 = 112 and 88 + 40 = 112 + 16 = 128)"""
         if width not in _BY_WIDTH:
             raise ValueError(f'rows of {width} columns: no layout without hand-benchmark blocks is that wide (accepted: '

@@ -9,13 +9,14 @@ The forward pass itself needs no collective: the image batch is the only sharded
 import torch
 import torch.distributed as dist
 
-from .eval_layout import BLOCKS, BLOCKS_ADDED, RowLayout
-from .ops_names import (HAND_BENCH_SOURCES, HAND_BENCH_TABLE, HAND_METRIC_NAMES, MULTI_TABLES, OBJ_METRIC_NAMES, PHYSICS_SOURCES,
-                        SYM_METRIC_NAMES)
+from .eval_layout import BLOCKS, BLOCKS_ADDED, BLOCKS_GRASP, RowLayout
+from .ops_names import (GRASP_METRIC_NAMES, HAND_BENCH_SOURCES, HAND_BENCH_TABLE, HAND_METRIC_NAMES, MULTI_TABLES, OBJ_METRIC_NAMES,
+                        PHYSICS_SOURCES, SYM_METRIC_NAMES)
 
 # the row layout -- which blocks there are, their order and widths -- is eval_layout.BLOCKS (+ BLOCKS_ADDED); these are its widths, in its order
 ROW, MULTI, PHYS, PHYS_MULTI, VOL_MULTI, VOL, HAND_BENCH, HAND_BENCH_MULTI = (width for _, _, width, _ in BLOCKS)
 SYM, SYM_MULTI = (width for _, _, width, _ in BLOCKS_ADDED)
+GRASP, GRASP_MULTI = (width for _, _, width, _ in BLOCKS_GRASP)
 ROW_BEST = ROW + MULTI
 OBJ_COL = 12                 # first of the 16 object metrics of the aggregated pose within the base block
 
@@ -306,11 +307,81 @@ def symmetric_table(block):
     return {src: {k: float(mean[3 * s + i]) for i, k in enumerate(SYM_METRIC_NAMES)} for s, src in enumerate(names)}
 
 
+_GRASP = {}
+
+
+def grasp_meter(assets, device):
+    """the grasp_eval.GraspMeter of an asset set on a device, built once per set of contact gates: the hand surface fill, the anchor tables
+    and the objects' vertex tables.  vpho_amd.grasp_eval is imported here and nowhere else on the evaluation path."""
+    from .configs.args import cfg
+    key = (id(assets), str(device), tuple(float(x) for x in cfg.contact_normal_distance_thresh), float(cfg.contact_vertical_distance_thresh))
+    if key not in _GRASP:
+        from .grasp_eval import GraspMeter
+        _GRASP[key] = GraspMeter(cfg, assets, device)
+    return _GRASP[key]
+
+
+def _gt_hand_vert_flip(data, gt_vert):
+    """(bs, 778, 3) fp32: the annotated hand in the flipped, root-relative frame of the fill: data['gt_hand_vert_flip'] where the batch
+    carries it, else the camera-frame gt_vert minus the root joint with a left hand's x negated"""
+    if data.get('gt_hand_vert_flip') is not None:
+        return data['gt_hand_vert_flip'].to(gt_vert.device, torch.float32)
+    v = gt_vert.float() - data['root_joint'].float()[:, None]
+    v[..., 0] = v[..., 0] * torch.where(data['is_right'].bool(), 1.0, -1.0).to(v.dtype)[:, None]
+    return v
+
+
+def _grasp_against_gt(hand_vert_flip, pd_rt, data, gt_vert, meter):
+    """GraspMeter.score of (bs, S, 778, 3) model-frame hands with (bs, S, 3, 4) camera-frame object poses against the annotated pair
+    (the annotation's map comes from the same kernel, S = 1) -> counts, values (bs, S, 8), table (bs, 24)"""
+    return meter.score(hand_vert_flip.float(), pd_rt, _gt_hand_vert_flip(data, gt_vert), data['gt_obj_rt'].double().contiguous(),
+                       data['root_joint'], data['is_right'], meter.obj_ids(data['obj_name']))
+
+
+def grasp_block(out, data, gt_vert, meter):
+    """(bs, GRASP) fp32 in the order of ops_names.GRASP_COLUMNS: contact-map and grasp agreement of the aggregated
+    hand (out['agg_hand_vert']: flipped and root-relative, the frame of the fill) with the aggregated object pose, the pair of
+    physics_block, against the annotated pair; NaN without data['gt_obj_rt'].  ``meter``: a grasp_eval.GraspMeter (grasp_meter)."""
+    if not gt_vert.is_cuda:
+        raise RuntimeError('grasp_block: the contact agreement runs on the GPU only (no CPU path)')
+    if 'gt_obj_rt' not in data:
+        return torch.full((gt_vert.shape[0], GRASP), float('nan'), device=gt_vert.device, dtype=torch.float32)
+    _, values, _ = _grasp_against_gt(out['agg_hand_vert'][:, None], _agg_obj_rt(out, data)[:, None].contiguous(), data, gt_vert, meter)
+    return values[:, 0].float()
+
+
+def grasp_multi_block(out, data, gt_vert, meter):
+    """(bs, GRASP_MULTI) fp32 in the order of ops_names.GRASP_MULTI_COLUMNS: the eight values of every sampled hypothesis -- the pairs of
+    _hypothesis_pairs, the fill run on out['diff_final_hand_vert'] as it is (flipped and root-relative already) -- reduced per image to
+    hypothesis 0 | best-of-S | mean-of-S by the agreement kernel; NaN without data['gt_obj_rt']"""
+    if not gt_vert.is_cuda:
+        raise RuntimeError('grasp_multi_block: the contact agreement runs on the GPU only (no CPU path)')
+    if 'gt_obj_rt' not in data:
+        return torch.full((gt_vert.shape[0], GRASP_MULTI), float('nan'), device=gt_vert.device, dtype=torch.float32)
+    pd_rt = _hypothesis_obj_rt(out, data['root_joint'].float().contiguous())
+    return _grasp_against_gt(out['diff_final_hand_vert'], pd_rt, data, gt_vert, meter)[2].float()
+
+
+def grasp_table(block):
+    """the table 'grasp' of Trainer.eval / EVAL_JSON from the (n, 8 | 32) columns grasp_block [+ grasp_multi_block] made:
+    {'pred': {...}[, 'one_candidate': ..., 'best_of_S': ..., 'mean_of_S': ...]}, each the ops_names.GRASP_TABLE keys: the fp64 mean of
+    every value over the images where it is defined (NaN where it never is), then IoU_defined, the share of images with an IoU"""
+    if block.shape[1] not in (GRASP, GRASP + GRASP_MULTI):
+        raise ValueError(f'grasp_table: {block.shape[1]} columns, expected {GRASP} or {GRASP + GRASP_MULTI}')
+    blk = block.double()
+    ok = ~blk.isnan()
+    mean = torch.where(ok, blk, torch.zeros_like(blk)).sum(0) / ok.sum(0)                # 0 / 0 = NaN: never defined
+    share = ok.double().mean(0)
+    names = ('pred',) + (MULTI_TABLES if block.shape[1] > GRASP else ())
+    return {src: dict({k: float(mean[8 * s + i]) for i, k in enumerate(GRASP_METRIC_NAMES)}, IoU_defined=float(share[8 * s]))
+            for s, src in enumerate(names)}
+
+
 def metric_rows(out, data, gt_joint, gt_vert, first_index, assets=None, eval_best=False, eval_physics=False, physics_multi=False, volume_multi=False,
                 eval_volume=False, eval_hand_bench=False, hand_bench_multi=False, layout=None):
     """(bs, layout.width) fp32 on the model's device: the blocks of ``layout`` (an eval_layout.RowLayout; default: the one that
     RowLayout.resolve makes of the seven flags, so a *_multi block needs eval_best and the flag of its single-pose block; the symmetric
-    blocks come with a ``layout`` only), each filled by its block function; a block that the layout does not have costs no launch.  With ``layout`` the flags are not looked at."""
+    and grasp blocks come with a ``layout`` only), each filled by its block function; a block that the layout does not have costs no launch.  With ``layout`` the flags are not looked at."""
     if layout is None:
         layout = RowLayout.resolve(eval_best, eval_physics, physics_multi, eval_volume, volume_multi, eval_hand_bench, hand_bench_multi)
     if assets is None and layout.has('physics'):
@@ -319,6 +390,8 @@ def metric_rows(out, data, gt_joint, gt_vert, first_index, assets=None, eval_bes
         raise ValueError('metric_rows: eval_volume needs the asset tables (object meshes, hand faces)')
     if assets is None and layout.has('symmetric'):
         raise ValueError('metric_rows: eval_symmetric needs the asset tables (object corners, sampled vertices, diameters)')
+    if assets is None and layout.has('grasp'):
+        raise ValueError('metric_rows: eval_grasp needs the asset tables (hand faces, anchors, object vertices)')
     pp = postprocess(out, data['root_joint'], data['is_right'])
     bs, dev = gt_joint.shape[0], gt_joint.device
     rows = torch.empty((bs, layout.width), device=dev, dtype=torch.float32)
@@ -351,7 +424,9 @@ def metric_rows(out, data, gt_joint, gt_vert, first_index, assets=None, eval_bes
                         ('hand_bench', lambda: hand_bench_block(out, data, gt_joint, gt_vert)),
                         ('hand_bench_multi', lambda: hand_bench_multi_block(out, data, gt_joint, gt_vert)),
                         ('symmetric', lambda: symmetric_block(out, data, symmetry_meter(assets, dev))),
-                        ('symmetric_multi', lambda: symmetric_multi_block(out, data, symmetry_meter(assets, dev)))):
+                        ('symmetric_multi', lambda: symmetric_multi_block(out, data, symmetry_meter(assets, dev))),
+                        ('grasp', lambda: grasp_block(out, data, gt_vert, grasp_meter(assets, dev))),
+                        ('grasp_multi', lambda: grasp_multi_block(out, data, gt_vert, grasp_meter(assets, dev)))):
         if layout.has(name):
             rows[:, layout.slice(name)] = block()
     from .configs.args import cfg
@@ -363,6 +438,8 @@ def metric_rows(out, data, gt_joint, gt_vert, first_index, assets=None, eval_bes
             rows[:, layout.slice('physics')][:, 0:4] = float('nan')
         if layout.has('volume'):
             rows[:, layout.slice('volume')][:, 0:2] = float('nan')
+        if layout.has('grasp'):
+            rows[:, layout.slice('grasp')] = float('nan')
     return rows
 
 
@@ -511,6 +588,8 @@ def summarize(rows, layout=None):
         res['hand_bench'] = hand_bench_table(torch.cat([block(n) for n in ('hand_bench', 'hand_bench_multi') if layout.has(n)], 1))
     if layout.has('symmetric'):
         res['symmetric'] = symmetric_table(torch.cat([block(n) for n in ('symmetric', 'symmetric_multi') if layout.has(n)], 1))
+    if layout.has('grasp'):
+        res['grasp'] = grasp_table(torch.cat([block(n) for n in ('grasp', 'grasp_multi') if layout.has(n)], 1))
     return res
 
 

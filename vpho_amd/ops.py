@@ -1675,6 +1675,65 @@ class HandObjectPenetration:
         return (table, per, sd, inside) if per_vertex else (table, per)
 
 
+class ObjVertexAccel(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ('vert', 'index', 'clu_offset', 'clu_start', 'clu_sphere')] + [('n_obj', I)]
+
+
+class ContactMulti:
+    """The hand contact map of every sampled hypothesis (--eval_grasp; csrc/contact_multi.hip): the hand -> object
+    half of detect_hand_and_object_contact for n x S pairs in the object's model frame.  ``tables``: the host arrays of
+    grasp_eval.vertex_accel_tables (vpho_obj_vertex_accel of all objects, in the order of the object ids), kept on the device here."""
+
+    def __init__(self, tables, device):
+        import numpy as np
+        if not torch.device(device).type == 'cuda':
+            raise VphoError('vpho_amd ops take GPU tensors only (no CPU path)')
+        dev = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a, dtype=dt)).to(device)
+        self.vert, self.sphere = dev(tables['vert'], np.float64), dev(tables['clu_sphere'], np.float64)
+        self.index, self.clu_offset, self.clu_start = (dev(tables[k], np.int32) for k in ('index', 'clu_offset', 'clu_start'))
+        self.n_obj, self.device = len(tables['clu_offset']) - 1, device
+        if self.n_obj < 1 or self.vert.shape[0] < 1 or self.vert.shape != (self.index.shape[0], 3) or self.sphere.shape != (self.clu_start.shape[0] - 1, 4):
+            raise VphoError(f'ContactMulti: tables of {self.n_obj} objects, vert {tuple(self.vert.shape)}, index {tuple(self.index.shape)}, '
+                            f'clu_sphere {tuple(self.sphere.shape)}, clu_start {tuple(self.clu_start.shape)}')
+        self.c = ObjVertexAccel(self.vert.data_ptr(), self.index.data_ptr(), self.clu_offset.data_ptr(), self.clu_start.data_ptr(),
+                                self.sphere.data_ptr(), self.n_obj)
+
+    def __call__(self, hand_verts, hand_normals, root, is_right, obj_rt, obj_id, normal_thresh=(-0.015, 0.01), vertical_thresh=0.01,
+                 decay=(-0.005, 0.005), per_vertex=False):
+        """hand_verts, hand_normals (n,S,Nh,3) fp32: the filled surface of HandSurface.fill in its flipped, root-relative frame; root (n,3)
+        fp64, is_right (n,) uint8, obj_rt (n,S,3,4) fp64 in the camera frame, obj_id (n,) int32 device tensor (an id outside the table
+        gives NaN rows: it cannot be refused without a host sync).  -> weight (n,S,Nh) fp32 in [0, 1]; with per_vertex also nn_index
+        (n,S,Nh) int32 (-1 without contact) and nd, vd (n,S,Nh) fp64."""
+        n, S, Nh = hand_verts.shape[:3]
+        if hand_verts.shape != (n, S, Nh, 3) or hand_normals.shape != hand_verts.shape or obj_rt.shape != (n, S, 3, 4) or root.shape != (n, 3) \
+                or is_right.shape != (n,) or obj_id.shape != (n,):
+            raise VphoError(f'ContactMulti: hand_verts {tuple(hand_verts.shape)}, hand_normals {tuple(hand_normals.shape)}, root {tuple(root.shape)}, '
+                            f'is_right {tuple(is_right.shape)}, obj_rt {tuple(obj_rt.shape)}, obj_id {tuple(obj_id.shape)}')
+        w = _new((n, S, Nh), hand_verts)
+        nn = _new((n, S, Nh), hand_verts, torch.int32) if per_vertex else None
+        nd, vd = (_new((n, S, Nh), hand_verts, torch.float64) for _ in range(2)) if per_vertex else (None, None)
+        _call('vpho_contact_multi_f32', C.byref(self.c), _f32(hand_verts), _f32(hand_normals), I(n), I(S), I(Nh), _f64(root), _u8(is_right),
+              _f64(obj_rt), _i32(obj_id), F(normal_thresh[0]), F(normal_thresh[1]), F(vertical_thresh), F(decay[0]), F(decay[1]),
+              _f32(w), None if nn is None else _i32(nn), _f64(nd), _f64(vd))
+        return (w, nn, nd, vd) if per_vertex else w
+
+
+def contact_agreement(weight, weight_gt, force_contact, is_grasped, force_contact_gt, is_grasped_gt):
+    """vpho_contact_agreement_f32: weight (n,S,Nh) against weight_gt (n,Nh) fp32, force_contact (n,S,32) fp32 / is_grasped (n,S) uint8
+    against their (n,32) / (n,) counterparts -> counts (n,S,3) int32 = TP, P, G; values (n,S,8) fp64 in the order of
+    ops_names.GRASP_METRIC_NAMES; table (n,24) fp64 = hypothesis 0 | best-of-S | mean-of-S"""
+    n, S, Nh = weight.shape
+    if weight_gt.shape != (n, Nh) or force_contact.shape != (n, S, 32) or is_grasped.shape != (n, S) or force_contact_gt.shape != (n, 32) \
+            or is_grasped_gt.shape != (n,):
+        raise VphoError(f'contact_agreement: weight {tuple(weight.shape)}, weight_gt {tuple(weight_gt.shape)}, force_contact {tuple(force_contact.shape)}, '
+                        f'is_grasped {tuple(is_grasped.shape)}, force_contact_gt {tuple(force_contact_gt.shape)}, is_grasped_gt {tuple(is_grasped_gt.shape)}')
+    counts = _new((n, S, 3), weight, torch.int32)
+    values, table = _new((n, S, 8), weight, torch.float64), _new((n, 24), weight, torch.float64)
+    _call('vpho_contact_agreement_f32', _f32(weight), _f32(weight_gt), _f32(force_contact), _u8(is_grasped), _f32(force_contact_gt),
+          _u8(is_grasped_gt), I(n), I(S), I(Nh), _i32(counts), _f64(values), _f64(table))
+    return counts, values, table
+
+
 # ----------------------------------------------------------------------------------------------- score-network training
 def _at(t, off=0):
     """device address of element `off` of a contiguous fp32 tensor"""

@@ -63,3 +63,16 @@ SYM_COLUMNS = tuple(f'sym/pred/{k}' for k in SYM_METRIC_NAMES)
 # evaluate.symmetric_multi_block (eval_best AND eval_symmetric): every sampled object hypothesis, per image reduced to hypothesis 0,
 # best-of-S (min SMCE, min MSSD, max hit: TesterObject.postprocess) and mean-of-S (9 columns)
 SYM_MULTI_COLUMNS = tuple(f'sym/{t}/{k}' for t in MULTI_TABLES for k in SYM_METRIC_NAMES)
+# the contact-map and grasp agreement (--eval_grasp) of a (hand, object pose) pair with the annotated pair, both hand
+# contact maps made by the same kernel: with c = (weight > 0) and g = (annotation's weight > 0) over the filled hand vertices IoU,
+# precision, recall and F1 of c against g (NaN where the denominator is 0), MAE = mean |weight - annotation's weight|, anchor_agree = the
+# share of the 32 anchors with equal pooled contact state, grasped = the pair's own is_grasped, grasp_agree = (is_grasped == annotation's)
+GRASP_METRIC_NAMES = ('IoU', 'precision', 'recall', 'F1', 'MAE', 'anchor_agree', 'grasped', 'grasp_agree')
+# evaluate.grasp_block: the eight values of the aggregated hand with the aggregated object pose (NaN without object ground truth)
+GRASP_COLUMNS = tuple(f'grasp/pred/{k}' for k in GRASP_METRIC_NAMES)
+# evaluate.grasp_multi_block (eval_best AND eval_grasp): every sampled hypothesis (hand candidate s with object candidate s), per image
+# reduced to hypothesis 0, best-of-S (each value's maximum on its own, MAE's minimum) and mean-of-S, NaN hypotheses left out (24 columns)
+GRASP_MULTI_COLUMNS = tuple(f'grasp/{t}/{k}' for t in MULTI_TABLES for k in GRASP_METRIC_NAMES)
+# the keys of every source of the summarize-level / EVAL_JSON table 'grasp': each value's mean over the images where it is defined (NaN
+# where it never is), then the share of images where IoU is defined
+GRASP_TABLE = GRASP_METRIC_NAMES + ('IoU_defined',)

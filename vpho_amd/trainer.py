@@ -359,16 +359,19 @@ class Trainer:
         passes eval_best / eval_physics / ... itself gets the rows it always got unless it asks for the newer block too.
         The symmetry-aware object errors (blocks ``symmetric`` / ``symmetric_multi``, table ``symmetric``) have no keyword here -- a test pins
         this parameter list: they follow cfg.eval_symmetric, and for every sampled hypothesis cfg.eval_best and cfg.eval_symmetric together
-        with the ``eval_best`` this call resolves to."""
+        with the ``eval_best`` this call resolves to.  The contact-map and grasp agreement (blocks ``grasp`` / ``grasp_multi``, table
+        ``grasp``) follows cfg.eval_grasp in the same way (RowLayout.with_grasp)."""
         from .configs.args import cfg
         layout = E.RowLayout.resolve(eval_best, eval_physics, physics_multi, eval_volume, volume_multi, eval_hand_bench, hand_bench_multi,
-                                     None, None)
+                                     None, None).with_grasp(None, None)
         batch_rows = lambda out, batch, gt, first: E.metric_rows(out, batch, gt[0], gt[1], first, self.assets, layout=layout)
         if layout.has('physics') or layout.has('volume'):
             # object meshes, acceleration tables, the closed hand mesh, the objects' solids: what the layout needs, once, before the timed loop
             E.physics_meter(self.assets, self.device, multi=layout.has('physics_multi'), volume=layout.has('volume'), volume_multi=layout.has('volume_multi'))
         if layout.has('symmetric'):
             E.symmetry_meter(self.assets, self.device)            # the symmetry table, once, before the timed loop; refuses a table that is too long
+        if layout.has('grasp'):
+            E.grasp_meter(self.assets, self.device)               # the hand surface, anchor and object vertex tables, once, before the timed loop
         rows = []
         t0 = time.perf_counter()
         # three batches in flight (independent images; see evaluate.PipelinedPredictor)
@@ -405,7 +408,7 @@ class Trainer:
             print(f'aggregation_mode_hand {cfg.aggregation_mode_hand}  aggregation_mode_obj {cfg.aggregation_mode_obj}')
             table = E.summarize(rows.cpu(), layout)
             for name, r in table.items():
-                if name not in ('object', 'physics', 'volume', 'hand_bench', 'symmetric') + E.MULTI_TABLES:
+                if name not in ('object', 'physics', 'volume', 'hand_bench', 'symmetric', 'grasp') + E.MULTI_TABLES:
                     print(f'{name:>5s}: n={r["n"]:5d}  MJE reg {r["MJE_reg"]:.2f}  first {r["MJE_first"]:.2f}  agg {r["MJE_agg"]:.2f}  MVE agg {r["MVE_agg"]:.2f}  (mm)')
             print('object (aggregated pose): ' + '  '.join(f'{k} {v:.2f}' for k, v in table['object'].items()))
             for name in E.MULTI_TABLES:
@@ -413,7 +416,7 @@ class Trainer:
                     print(f'{name} hand (mm): ' + '  '.join(f'{k} {v:.2f}' for k, v in table[name]['hand'].items()))
                     print(f'{name} object: ' + '  '.join(f'{k} {v:.2f}' for k, v in table[name]['object'].items()))
             for name, note, fmt in (('physics', '', '.2f'), ('volume', f' (pitch {cfg.physics_voxel_pitch * 1000.0:g} mm)', '.3f'), ('hand_bench', '', '.4f'),
-                                    ('symmetric', ' (m, m, share)', '.5f')):
+                                    ('symmetric', ' (m, m, share)', '.5f'), ('grasp', '', '.4f')):
                 for src, r in table.get(name, {}).items():
                     print(f'{name} {src}{note}: ' + '  '.join(f'{k} {v:{fmt}}' for k, v in r.items()))
             import json
