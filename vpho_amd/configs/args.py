@@ -100,6 +100,18 @@ class Config:
         self.random_erasing_max_count = 1
         self.heatmap_hand_sigma = 2.0
         self.heatmap_obj_sigma = 2.0
+        # photometric augmentation on the device (vpho_amd/photo.py; base.py:349-397): every gate is off by default, the reference's values
+        # are PHOTO_REFERENCE below (--photo_aug reference).  Contrast and hue ride under color_jitter_prob, like brightness and saturation
+        self.photo_aug = 'none'       # none | reference: the five switches below at the reference's values; explicit flags win
+        self.clahe_p = 0.0
+        self.clahe_clip_limit = (1.0, 4.0)
+        self.jitter_contrast = (1.0, 1.0)
+        self.jitter_hue = (0.0, 0.0)
+        self.blur_p = 0.0
+        self.blur_limit = (3, 7)
+        self.sigma_limit = (0.2, 2.0)
+        self.motion_blur_p = 0.0
+        self.motion_blur_limit = (3, 7)
         # physics labels from annotations (vpho_amd/physics_labels.py): the gates of get_hand_contact (lib/configs/args.py:44-45)
         self.contact_normal_distance_thresh = (-0.01, 0.01)
         self.contact_vertical_distance_thresh = 0.005
@@ -108,8 +120,31 @@ class Config:
         self.cross_dropout = 0.1      # the reference's nn.TransformerEncoderLayer / PositionalEncoding default (cross_module.py:64,104-107)
 
 
+# what --photo_aug reference stands for: A.CLAHE(p=0.5), A.ColorJitter(contrast=(0.6, 1.3), hue=(-0.15, 0.15)), A.AdvancedBlur(p=0.5),
+# A.MotionBlur(p=0.5) of base.py:349-397
+PHOTO_REFERENCE = dict(clahe_p=0.5, jitter_contrast=(0.6, 1.3), jitter_hue=(-0.15, 0.15), blur_p=0.5, motion_blur_p=0.5)
+
+
+class _Explicit(argparse.Action):
+    """stores the value and notes that the flag was given, so that --photo_aug leaves it alone"""
+    def __call__(self, parser, namespace, values, option_string=None):
+        setattr(namespace, self.dest, values)
+        namespace._explicit = getattr(namespace, '_explicit', ()) + (self.dest,)
+
+
+class _Parser(argparse.ArgumentParser):
+    def parse_known_args(self, args=None, namespace=None):
+        ns, rest = super().parse_known_args(args, namespace)
+        explicit = ns.__dict__.pop('_explicit', ())
+        if getattr(ns, 'photo_aug', 'none') == 'reference':
+            for k, v in PHOTO_REFERENCE.items():
+                if k not in explicit:
+                    setattr(ns, k, v)
+        return ns, rest
+
+
 def _parser():
-    p = argparse.ArgumentParser(description='Hand-Object Pose Estimation (MI355X hot path)')
+    p = _Parser(description='Hand-Object Pose Estimation (MI355X hot path)')
     p.add_argument('--mode', type=str, default='train', choices=['train', 'eval', 'infer'])
     p.add_argument('--eval_full', action='store_true')
     p.add_argument('--eval_best', action='store_true')
@@ -191,6 +226,16 @@ def _parser():
     p.add_argument('--random_erasing_max_count', type=int, default=1)
     p.add_argument('--heatmap_hand_sigma', type=float, default=2.0)
     p.add_argument('--heatmap_obj_sigma', type=float, default=2.0)
+    p.add_argument('--photo_aug', type=str, default='none', choices=['none', 'reference'])
+    p.add_argument('--clahe_p', type=float, default=0.0, action=_Explicit)
+    p.add_argument('--clahe_clip_limit', type=float, nargs=2, default=(1.0, 4.0))
+    p.add_argument('--jitter_contrast', type=float, nargs=2, default=(1.0, 1.0), action=_Explicit)
+    p.add_argument('--jitter_hue', type=float, nargs=2, default=(0.0, 0.0), action=_Explicit)
+    p.add_argument('--blur_p', type=float, default=0.0, action=_Explicit)
+    p.add_argument('--blur_limit', type=int, nargs=2, default=(3, 7))
+    p.add_argument('--sigma_limit', type=float, nargs=2, default=(0.2, 2.0))
+    p.add_argument('--motion_blur_p', type=float, default=0.0, action=_Explicit)
+    p.add_argument('--motion_blur_limit', type=int, nargs=2, default=(3, 7))
     p.add_argument('--contact_normal_distance_thresh', type=float, nargs=2, default=(-0.01, 0.01))
     p.add_argument('--contact_vertical_distance_thresh', type=float, default=0.005)
     p.add_argument('--frame_contact', action='store_true')

@@ -65,9 +65,10 @@ def sample_draws(cfg, seed, epoch, index, train, patch):
     3 scale U(0,1), 4 rotation gate U(0,1), 5 rotation U(-1,1), 6 RGB-shift gate, 7-9 dr dg db U(shift_limit), 10 colour-jitter gate,
     11 brightness, 12 saturation, 13 erasing gate, 14-15 the two words of the Philox key, then per rectangle and attempt area,
     log-aspect and -- when the rectangle fits -- top, left.  Draws 1-15 are always taken, whatever the gates say, so the position of each
-    in the stream is fixed.  Evaluation (``train`` False) draws nothing: zeros, 1 and 0, no colour change, no erasing."""
+    in the stream is fixed.  Evaluation (``train`` False) draws nothing: zeros, 1 and 0, no colour change, no erasing.  ``jitter_gate``
+    tells whether draw 10 fired: the contrast and hue of vpho_amd/photo.py (a second generator, its own order) ride under that gate."""
     out = dict(jitter=np.zeros(2), scale=1.0, rot=0.0, colour=np.array([0, 0, 0, 1, 1], np.float32), erase=np.zeros((MAX_ERASE, 4), np.int32),
-               key=np.zeros(2, np.uint32))
+               key=np.zeros(2, np.uint32), jitter_gate=False)
     if not train:
         return out
     r = np.random.default_rng((int(seed), int(epoch), int(index)))
@@ -81,6 +82,7 @@ def sample_draws(cfg, seed, epoch, index, train, patch):
     gate, b, s = r.uniform(0, 1), r.uniform(*cfg.brightness), r.uniform(*cfg.saturation)
     if gate < cfg.color_jitter_prob:
         out['colour'][3:] = (b, s)
+        out['jitter_gate'] = True
     gate = r.uniform(0, 1)
     out['key'] = r.integers(0, 2 ** 32, 2, dtype=np.uint64).astype(np.uint32)
     count = int(cfg.random_erasing_max_count)
@@ -286,6 +288,14 @@ def adaptive_res(bbox, size):
 
 
 # ------------------------------------------------------------------------------------------------------------------ pipeline
+def photo_can_fire(cfg):
+    """True when a flag lets CLAHE, contrast, hue or one of the two blurs fire (vpho_amd/photo.py, csrc/photo.hip): the training crop
+    then takes the ``ops.photo_*`` launches for the whole batch.  With the default flags it is False and photo.py is never imported."""
+    g = lambda k, d: getattr(cfg, k, d)
+    return bool(g('clahe_p', 0) > 0 or tuple(g('jitter_contrast', (1, 1))) != (1, 1) or tuple(g('jitter_hue', (0, 0))) != (0, 0) or g('blur_p', 0) > 0
+                or g('motion_blur_p', 0) > 0)
+
+
 def _stack_records(records):
     if isinstance(records, dict):
         return records
@@ -298,7 +308,8 @@ class FramePipeline:
 
     frames_u8: (n,H,W,3) uint8 tensor (pinned host memory or already on the device); records: list of record dicts (module docstring) or
     a dict of stacked arrays.  Everything runs on the current stream: the host does the crop plan and the rigid labels, the device the
-    crops (``ops.frame_patch``), the adaptive hand maps on ``bbox_hand`` and the square object maps on ``bbox_obj_rect`` with is_right
+    crops (``ops.frame_patch``; in training with ``--clahe_p``, ``--jitter_contrast``, ``--jitter_hue``, ``--blur_p`` or ``--motion_blur_p``
+    able to fire, the ``ops.photo_*`` launches of vpho_amd/photo.py for the whole batch), the adaptive hand maps on ``bbox_hand`` and the square object maps on ``bbox_obj_rect`` with is_right
     (``ops.heatmap_targets``; dexycb6.py:435-437)."""
     def __init__(self, cfg, assets, device, train=False, seed=0):
         from . import ops                               # the HIP library: a missing kernel is an error, there is no host path
@@ -309,6 +320,13 @@ class FramePipeline:
             sigma = float(getattr(cfg, f'heatmap_{who}_sigma'))
             g, gmin = gauss_table(sigma)
             self.tables[who] = (torch.from_numpy(g).to(self.device), sigma, gmin)
+        self.photo = None
+        if self.train and photo_can_fire(cfg):          # CLAHE, contrast, hue, blurs: the training crop goes through ops.photo_*
+            from . import photo
+            if cfg.clahe_p > 0 and self.patch % photo.TILES:
+                raise ValueError(f'--clahe_p {cfg.clahe_p}: the {photo.TILES} x {photo.TILES} tile grid needs a patch size that is a multiple of {photo.TILES}, '
+                                 f'got {self.patch}')
+            self.photo = photo
         self.labeler = None
         if getattr(cfg, 'frame_contact', False):        # --frame_contact: contact labels from the annotations, on the device
             from .physics_labels import PhysicsLabeler
@@ -343,7 +361,12 @@ class FramePipeline:
             colour = self._dev(draws['colour'].astype(np.float32))
             if (draws['erase'][:, :, 2] > draws['erase'][:, :, 0]).any():
                 erase, key = self._dev(draws['erase'].astype(np.int32)), self._dev(draws['key'].astype(np.uint32).view(np.int32))
-        out = {'rgb': ops.frame_patch(frames, self._dev(plan['minv']), P, colour=colour, flip=flip, erase=erase, key=key)}
+        if self.photo is not None:
+            pd = [self.photo.photo_draws(cfg, self.seed, epoch, i, bool(d['jitter_gate'])) for i, d in zip(index, per)]
+            params = {k: np.stack([np.asarray(d[k]) for d in pd]) for k in pd[0]}
+            out = {'rgb': self.photo.photo_patch(ops, frames, self._dev(plan['minv']), P, colour, params, flip=flip, erase=erase, key=key)}
+        else:
+            out = {'rgb': ops.frame_patch(frames, self._dev(plan['minv']), P, colour=colour, flip=flip, erase=erase, key=key)}
         g, sigma, gmin = self.tables['hand']
         out['hm_hand'] = ops.heatmap_targets(self._dev(plan['gt_jt2d']), self._dev(np.concatenate([plan['bbox_hand'][:, :2], wh], -1)), g, sigma, gmin, S,
                                              res=self._dev(res))

@@ -2109,6 +2109,152 @@ def heatmap_targets(pts, box, g, sigma, gmin, size, res=None, left=None, out=Non
     return out
 
 
+# ----------------------------------------------------------------------------------------------- photometric augmentation (photo.hip)
+# A library of its own, libvpho_photo.so (include/vpho_photo.h): the ABI of include/vpho_hip.h is closed.  Loaded on first use -- a run that
+# never augments does not open it -- and, like the main library, there is nothing behind it: a missing library is an error.
+PHOTO_LIB_PATH = os.environ.get('VPHO_PHOTO_LIB') or os.path.join(_HERE, 'libvpho_photo.so')
+_photo_lib = None
+
+
+def photo_lib():
+    global _photo_lib
+    if _photo_lib is None:
+        if not os.path.exists(PHOTO_LIB_PATH):
+            raise ImportError(f'{PHOTO_LIB_PATH} is missing: build the HIP extension first (python -m vpho_amd.build or '
+                              f'__graft_entry__.build()); the photometric augmentation has no CPU fallback')
+        _photo_lib = C.CDLL(PHOTO_LIB_PATH)
+        _photo_lib.vpho_photo_last_error.restype = C.c_char_p
+    return _photo_lib
+
+
+def _photo_call(name, *args):
+    plib = photo_lib()
+    if getattr(plib, name)(*args, _stream()) != 0:
+        raise VphoError(plib.vpho_photo_last_error().decode())
+
+
+def _photo_levels(name, levels, clahe=False):
+    """the refusals every photo_* op shares, before any launch: (n, P, P, 3) uint8 on the device -> n, P"""
+    if not torch.is_tensor(levels) or levels.dim() != 4 or levels.shape[3] != 3 or levels.shape[1] != levels.shape[2] or levels.dtype != torch.uint8:
+        raise VphoError(f'{name}: levels must be a (n, P, P, 3) uint8 tensor, got {tuple(levels.shape) if torch.is_tensor(levels) else type(levels)}')
+    n, P = int(levels.shape[0]), int(levels.shape[1])
+    if n > 65535 or P < 1 or P > 16384:
+        raise VphoError(f'{name}: n {n} / P {P} beyond 65535 images of 16384 pixels a side')
+    if clahe and P % 8:
+        raise VphoError(f'{name}: the 8 x 8 tile grid of CLAHE needs a patch size that is a multiple of 8, got {P}')
+    return n, P
+
+
+def _photo_host_ints(name, what, v, n, ok, rule):
+    """a per-sample host parameter (sequence of n integers) checked here, then uploaded as int32"""
+    import numpy as np
+    a = np.asarray(v.cpu() if torch.is_tensor(v) else v)
+    if a.shape != (n,) or a.dtype.kind not in 'iu' or not all(ok(int(k)) for k in a):
+        raise VphoError(f'{name}: {what} must be {n} integers, each {rule}; got {a.tolist() if a.size <= 16 else a.shape}')
+    return torch.from_numpy(a.astype(np.int32))
+
+
+def _photo_out(name, out, shape, like, dtype):
+    if out is None:
+        return _new(shape, like, dtype)
+    if tuple(out.shape) != shape or out.dtype != dtype:
+        raise VphoError(f'{name}: out of shape {tuple(out.shape)} and dtype {out.dtype}, expected {shape} {dtype}')
+    return out
+
+
+def photo_levels(frames, minv, patch, out=None):
+    """(n,H,W,3) uint8 frames -> levels (n,patch,patch,3) uint8: the bicubic crop of ``frame_patch`` before any colour stage, not
+    mirrored (vpho_photo_levels_u8)."""
+    if frames.dim() != 4 or frames.shape[3] != 3:
+        raise VphoError(f'photo_levels: frames of shape {tuple(frames.shape)}, expected (n, H, W, 3)')
+    n, H, W, _ = frames.shape
+    if tuple(minv.shape) != (n, 6):
+        raise VphoError(f'photo_levels: minv of shape {tuple(minv.shape)}, expected {(n, 6)}')
+    patch = int(patch)
+    if n > 65535 or patch < 1 or patch > 16384:
+        raise VphoError(f'photo_levels: n {n} / patch {patch} beyond 65535 images of 16384 pixels a side')
+    out = _photo_out('photo_levels', out, (n, patch, patch, 3), frames, torch.uint8)
+    _photo_call('vpho_photo_levels_u8', _u8(frames), I(n), I(H), I(W), _f64(minv), I(patch), _u8(out))
+    return out
+
+
+def photo_clahe_lut(levels, clip):
+    """levels -> (l8 (n,P,P) uint8, lut (n,64,256) uint8) of vpho_photo_clahe_lut_u8.  ``clip``: n host integers, the clip COUNT of each
+    sample (``photo.clahe_clip``), 0 = the sample's gate is off and its rows of l8 / lut are left unwritten.  Returns clip on the device
+    as the third item."""
+    n, P = _photo_levels('photo_clahe_lut', levels, clahe=True)
+    clip = _photo_host_ints('photo_clahe_lut', 'clip', clip, n, lambda k: 0 <= k <= P * P, 'a clip count in 0 .. P * P').to(levels.device)
+    l8, lut = _new((n, P, P), levels, torch.uint8), _new((n, 64, 256), levels, torch.uint8)
+    _photo_call('vpho_photo_clahe_lut_u8', _u8(levels), _i32(clip), I(n), I(P), _u8(l8), _u8(lut))
+    return l8, lut, clip
+
+
+def photo_clahe_apply(levels, clip, l8, lut, out=None, want_l8=False):
+    """the interpolation between the tiles' LUTs and the return trip through Lab (vpho_photo_clahe_apply_u8): -> levels, or (levels, l8')
+    with ``want_l8``.  ``clip`` (n) int32 on the device, as ``photo_clahe_lut`` returned it.  ``out`` may be ``levels``."""
+    n, P = _photo_levels('photo_clahe_apply', levels, clahe=True)
+    for name, t, shape, dt in (('clip', clip, (n,), torch.int32), ('l8', l8, (n, P, P), torch.uint8), ('lut', lut, (n, 64, 256), torch.uint8)):
+        if not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dt:
+            raise VphoError(f'photo_clahe_apply: {name} must be {shape} {dt}')
+    out = _photo_out('photo_clahe_apply', out, (n, P, P, 3), levels, torch.uint8)
+    l8o = _new((n, P, P), levels, torch.uint8) if want_l8 else None
+    _photo_call('vpho_photo_clahe_apply_u8', _u8(levels), _i32(clip), _u8(l8), _u8(lut), I(n), I(P), _u8(out), _u8(l8o))
+    return (out, l8o) if want_l8 else out
+
+
+def _photo_rows(name, what, t, shape):
+    if t is not None and (not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != torch.float32):
+        raise VphoError(f'{name}: {what} must be a {shape} float32 tensor')
+
+
+def photo_grey_sum(levels, colour=None):
+    """(n) int64: the sum over each image of the grey level after the shift and brightness of ``colour`` (n,5) (vpho_photo_grey_sum_u8);
+    integer adds only, the same bits in every run"""
+    n, P = _photo_levels('photo_grey_sum', levels)
+    _photo_rows('photo_grey_sum', 'colour', colour, (n, 5))
+    sums = torch.zeros(n, dtype=torch.int64, device=levels.device)
+    _photo_call('vpho_photo_grey_sum_u8', _u8(levels), _f32(colour), I(n), I(P), _ptr(sums, torch.int64))
+    return sums
+
+
+def photo_colour(levels, colour=None, contrast=None, hue=None, sums=None, out=None):
+    """shift, brightness, contrast, saturation, hue on levels (vpho_photo_colour_u8).  ``colour`` (n,5) as ``frame_patch`` takes it,
+    ``contrast`` (n) factors with ``sums`` (n) int64 of ``photo_grey_sum(levels, colour)``, ``hue`` (n) shifts, 0 = skipped."""
+    n, P = _photo_levels('photo_colour', levels)
+    _photo_rows('photo_colour', 'colour', colour, (n, 5))
+    _photo_rows('photo_colour', 'contrast', contrast, (n,))
+    _photo_rows('photo_colour', 'hue', hue, (n,))
+    if contrast is not None and (sums is None or tuple(sums.shape) != (n,) or sums.dtype != torch.int64):
+        raise VphoError('photo_colour: contrast factors need the (n) int64 grey sums of photo_grey_sum')
+    out = _photo_out('photo_colour', out, (n, P, P, 3), levels, torch.uint8)
+    _photo_call('vpho_photo_colour_u8', _u8(levels), _f32(colour), _f32(contrast), _f32(hue), None if sums is None else _ptr(sums, torch.int64), I(n), I(P),
+          _u8(out))
+    return out
+
+
+def photo_filter(levels, k1, K1, k2, K2, flip=None, erase=None, key=None, out=None):
+    """two K x K filters with reflect-101 borders, then the mirror, normalisation and erasing of ``frame_patch`` -> (n,3,P,P) fp32
+    (vpho_photo_filter_f32).  ``k1``, ``k2`` (n,49) fp32 on the device, the K * K weights row-major in front; ``K1``, ``K2``: n host
+    integers, odd in 1..7 (anything else is refused here)."""
+    n, P = _photo_levels('photo_filter', levels)
+    _photo_rows('photo_filter', 'k1', k1, (n, 49))
+    _photo_rows('photo_filter', 'k2', k2, (n, 49))
+    if k1 is None or k2 is None:
+        raise VphoError('photo_filter: both kernels are needed (a gate that is off is the 1 x 1 kernel [1])')
+    odd = lambda k: 1 <= k <= 7 and k % 2 == 1
+    K1 = _photo_host_ints('photo_filter', 'K1', K1, n, odd, 'odd in 1..7').to(levels.device)
+    K2 = _photo_host_ints('photo_filter', 'K2', K2, n, odd, 'odd in 1..7').to(levels.device)
+    for name, t, shape in (('flip', flip, (n,)), ('erase', erase, (n, 4, 4)), ('key', key, (n, 2))):
+        if t is not None and tuple(t.shape) != shape:
+            raise VphoError(f'photo_filter: {name} of shape {tuple(t.shape)}, expected {shape}')
+    if erase is not None and key is None:
+        raise VphoError('photo_filter: erase rectangles need a Philox key')
+    out = _photo_out('photo_filter', out, (n, 3, P, P), levels, torch.float32)
+    _photo_call('vpho_photo_filter_f32', _u8(levels), _f32(k1), _i32(K1), _f32(k2), _i32(K2), _u8(flip), None if erase is None else _i32(erase),
+          None if key is None else _i32(key), I(n), I(P), _f32(out))
+    return out
+
+
 # ----------------------------------------------------------------------------------------------- predictions to pixels (raster.hip)
 class MeshTable(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ('faces', 'face_offset', 'vert_count')] + [('M', I)]
