@@ -104,37 +104,40 @@ def test_flag_and_config_default():
 
 def test_layout_with_the_flag():
     from vpho_amd import ops_names as N
-    from vpho_amd.eval_layout import ALL_BLOCKS, BLOCKS_GRASP, RowLayout
-    assert [b[:3] for b in BLOCKS_GRASP] == [('grasp', 'eval_grasp', 8), ('grasp_multi', 'grasp_multi', 24)] and ALL_BLOCKS[-2:] == BLOCKS_GRASP
-    a = RowLayout.resolve().with_grasp(True)
+    from vpho_amd.eval_layout import BLOCKS, RowLayout
+    assert [b[:3] for b in BLOCKS[-2:]] == [('grasp', 'eval_grasp', 8), ('grasp_multi', 'grasp_multi', 24)] and BLOCKS[-1].needs == 'eval_grasp'
+    a = RowLayout.resolve(eval_grasp=True)
     assert a.width == 28 + 8 and a.columns[-8:] == N.GRASP_COLUMNS and a.slice('grasp') == slice(28, 36) and not a.has('grasp_multi')
-    assert not RowLayout.resolve().with_grasp(True, True).has('grasp_multi')                      # needs eval_best
-    assert not RowLayout.resolve(eval_best=True).with_grasp(False, True).has('grasp_multi')       # ... and eval_grasp
-    b = RowLayout.resolve(eval_best=True).with_grasp(True, True)
+    assert not RowLayout.resolve(eval_grasp=True, grasp_multi=True).has('grasp_multi')                        # needs eval_best
+    assert not RowLayout.resolve(eval_best=True, eval_grasp=False, grasp_multi=True).has('grasp_multi')       # ... and eval_grasp
+    b = RowLayout.resolve(eval_best=True, eval_grasp=True, grasp_multi=True)
     assert b.width == 88 + 32 and b.columns[-32:] == N.GRASP_COLUMNS + N.GRASP_MULTI_COLUMNS and b.slice('grasp_multi') == slice(96, 120)
-    c = RowLayout.resolve(eval_best=True, eval_symmetric=True, symmetric_multi=True).with_grasp(True, True)
+    c = RowLayout.resolve(eval_best=True, eval_symmetric=True, symmetric_multi=True, eval_grasp=True, grasp_multi=True)
     assert c.width == 100 + 32 and c.slice('symmetric') == slice(88, 91) and c.slice('grasp') == slice(100, 108)
     assert N.GRASP_COLUMNS == tuple(f'grasp/pred/{k}' for k in N.GRASP_METRIC_NAMES) and len(N.GRASP_METRIC_NAMES) == 8
     assert N.GRASP_MULTI_COLUMNS[8:10] == ('grasp/best_of_S/IoU', 'grasp/best_of_S/precision')
-    assert len(set(c.columns)) == len(c.columns) and ALL_BLOCKS[-1][0] == 'grasp_multi'
+    assert len(set(c.columns)) == len(c.columns) and BLOCKS[-1][0] == 'grasp_multi'
 
 
 def test_layouts_without_the_flag_are_todays():
-    from vpho_amd.eval_layout import ALL_BLOCKS, MULTI_NEEDS, RowLayout
-    old = [b for b in ALL_BLOCKS if not b[0].startswith('grasp')]
+    from vpho_amd.eval_layout import BLOCKS, RowLayout
+    old = [b for b in BLOCKS if not b[0].startswith('grasp')]
     assert len(old) == 10
     names = ('eval_best', 'eval_physics', 'physics_multi', 'eval_volume', 'volume_multi', 'eval_hand_bench', 'hand_bench_multi', 'eval_symmetric',
              'symmetric_multi')
+    needs = dict(physics_multi='eval_physics', volume_multi='eval_volume', hand_bench_multi='eval_hand_bench', symmetric_multi='eval_symmetric')
     for flags in itertools.product((False, True), repeat=9):
-        lay = RowLayout.resolve(*flags)
         f = dict(zip(names, flags))
-        on = lambda flag: flag is None or (f[flag] and (flag not in MULTI_NEEDS or (f['eval_best'] and f[MULTI_NEEDS[flag]])))
-        want = tuple(c for name, flag, _, cols in old if on(flag) for c in cols)
+        lay = RowLayout.resolve(**f)
+        on = lambda flag: flag is None or (f[flag] and (flag not in needs or (f['eval_best'] and f[needs[flag]])))
+        want = tuple(c for b in old if on(b.flag) for c in b.columns)
         assert lay.columns == want and lay.width == len(want) and not lay.has('grasp') and not lay.has('grasp_multi')
-        assert lay == lay.with_grasp() == lay.with_grasp(False, True) and lay.with_grasp(True).columns[:lay.width] == lay.columns
-    assert RowLayout.resolve().width == 28 and RowLayout.resolve(True).width == 88 and RowLayout.resolve(True, True, True).width == 108
+        assert lay == RowLayout.resolve(eval_grasp=False, grasp_multi=False, **f) == RowLayout.resolve(eval_grasp=False, grasp_multi=True, **f)
+        assert RowLayout.resolve(eval_grasp=True, **f).columns[:lay.width] == lay.columns
+    assert RowLayout.resolve().width == 28 and RowLayout.resolve(eval_best=True).width == 88
+    assert RowLayout.resolve(eval_best=True, eval_physics=True, physics_multi=True).width == 108
     assert RowLayout.resolve(eval_best=True, eval_symmetric=True, symmetric_multi=True).width == 100
-    assert RowLayout.from_width(88) == RowLayout.resolve(True)
+    assert RowLayout.from_width(88) == RowLayout.resolve(eval_best=True)
 
 
 def test_header_prototypes_count_and_version():
@@ -181,14 +184,16 @@ def test_grasp_table_on_hand_made_rows():
     multi = torch.full((3, 24), nan)
     multi[:, 8:16] = pred
     multi[0, 16:24] = 0.25
-    t = E.grasp_table(torch.cat([pred, multi], 1))
+    t = E.grasp_table(pred, multi)
     assert list(t) == ['pred', 'one_candidate', 'best_of_S', 'mean_of_S']
     assert all(np.isnan(v) for k, v in t['one_candidate'].items() if k != 'IoU_defined') and t['one_candidate']['IoU_defined'] == 0.0   # all-NaN columns
     assert t['best_of_S'] == t['pred'] and t['mean_of_S']['F1'] == 0.25 and t['mean_of_S']['IoU_defined'] == pytest.approx(1 / 3)
     with pytest.raises(ValueError):
         E.grasp_table(torch.zeros(2, 24))
+    with pytest.raises(ValueError):
+        E.grasp_table(pred, multi[:, :8])
     # summarize finds the blocks by the layout
-    lay = RowLayout.resolve().with_grasp(True)
+    lay = RowLayout.resolve(eval_grasp=True)
     rows = torch.zeros(3, lay.width)
     rows[:, lay.slice('grasp')] = pred
     assert E.summarize(rows, lay)['grasp'] == E.grasp_table(pred) and 'grasp' not in E.summarize(torch.zeros(3, 28))

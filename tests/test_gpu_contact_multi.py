@@ -280,7 +280,7 @@ EVAL_ARGS = dict(sample_num=4, sampling_steps=5, topk_hand=8, topk_obj=3, sample
 
 
 def test_trainer_eval_end_to_end(capsys, monkeypatch):
-    """Trainer.eval with cfg.eval_best and cfg.eval_grasp (what --eval_best --eval_grasp set): the new blocks hold what a direct GraspMeter
+    """Trainer.eval with eval_best, eval_grasp and grasp_multi, by keyword and once through cfg (what --eval_best --eval_grasp set): the new blocks hold what a direct GraspMeter
     call gives on the outputs of each batch, every older block keeps its bits, and the EVAL_JSON table is summarize(rows, layout)"""
     from vpho_amd import evaluate as E
     from vpho_amd.configs.args import cfg
@@ -304,26 +304,29 @@ def test_trainer_eval_end_to_end(capsys, monkeypatch):
         t = Trainer(cfg)
         rng_state = torch.get_rng_state()
         capsys.readouterr()
-        cfg.eval_best = cfg.eval_grasp = True               # Trainer.eval's parameter list is pinned: the grasp blocks follow cfg
-        rows_new = t.eval(eval_best=True)
-        cfg.eval_grasp = False
+        rows_new = t.eval(eval_best=True, eval_grasp=True, grasp_multi=True)
         text = capsys.readouterr().out
         torch.set_rng_state(rng_state)
         batches = list(seen)
         rows_old = t.eval(eval_best=True)
-        capsys.readouterr()
         assert len(seen) == 2 * len(batches)
+        cfg.eval_best = cfg.eval_grasp = True               # not named, the grasp blocks follow cfg, as after --eval_best --eval_grasp
+        torch.set_rng_state(rng_state)
+        rows_cfg = t.eval()
+        cfg.eval_best = cfg.eval_grasp = False
+        capsys.readouterr()
         meter = E.grasp_meter(t.assets, t.device)
     finally:
         for k, v in saved.items():
             setattr(cfg, k, v)
     torch.cuda.synchronize()
     n = EVAL_ARGS['eval_batch_size'] * EVAL_ARGS['num_batches']
-    layout = RowLayout.resolve(eval_best=True).with_grasp(True, True)
+    layout = RowLayout.resolve(eval_best=True, eval_grasp=True, grasp_multi=True)
     assert rows_new.shape == (n, 120) == (n, layout.width) and rows_old.shape == (n, 88)
     order = lambda r: r[r[:, 0].argsort()]
     i32 = lambda x: x.contiguous().view(torch.int32)
     assert torch.equal(i32(order(rows_new)[:, :88]), i32(order(rows_old)))               # every older block keeps its bits
+    assert torch.equal(i32(order(rows_cfg)), i32(order(rows_new)))                       # the flags of cfg give the rows of the keywords
     assert len(batches) == EVAL_ARGS['num_batches'] and meter.Nh == NH
     for out, data, gt_vert, rows in batches:
         root, right = data['root_joint'], data['is_right']

@@ -294,7 +294,8 @@ def test_main_train_with_ema_rate_then_eval_with_use_ema(tmp_path):
     # the same rows from a model that was handed final_model_ema.pt itself
     with TF._Cfg(checkpoint=os.path.join(run, 'final_model_ema.pt'), mode='eval', num_batches=1, eval_batch_size=8, use_ema=False) as cfg:
         rows = Trainer(cfg).eval()
-    table = E.summarize(rows.cpu(), E.RowLayout.resolve(None, None, None, None, None, None, None))
+    table = E.summarize(rows.cpu(), E.RowLayout.resolve(eval_best=None, eval_physics=None, physics_multi=None, eval_volume=None, volume_multi=None,
+                                                          eval_hand_bench=None, hand_bench_multi=None))
     assert rows.shape[0] == 8 and canon(json.loads(json.dumps(table))) == canon(with_ema['table'])
     # --use_ema with the plain file: the error names the way out
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'main.py'), '--mode', 'eval', '--model', 'vpho_net', '--num_batches', '1', '--eval_batch_size', '8',

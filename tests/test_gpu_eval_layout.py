@@ -48,7 +48,7 @@ def test_three_layouts_of_the_same_images(capsys):
     assert rows158.shape == (n, 158) and rows118.shape == (n, 118) and rows44.shape == (n, 44)
     line = [l for l in text.splitlines() if l.startswith('EVAL_JSON ')]
     assert len(line) == 1, text[-2000:]
-    layout = RowLayout.resolve(*[True] * 7)
+    layout = RowLayout.resolve(eval_hand_bench=True, hand_bench_multi=True, **plain)
     # as text: key order and a NaN compare too, and a float's text gives the float back
     assert json.dumps(json.loads(line[0][len('EVAL_JSON '):])['table']) == json.dumps(E.summarize(rows158.cpu(), layout))
     rows158, rows118, rows44 = (_by_image(r) for r in (rows158, rows118, rows44))

@@ -248,8 +248,8 @@ def test_trainer_eval_physics_end_to_end(monkeypatch, capsys):
     assert torch.equal(again, res[False, False])
     for best in (False, True):
         plain, wide = res[best, False], res[best, True]
-        w = E.row_width(best)
-        assert plain.shape == (6, w) and wide.shape == (6, E.row_width(best, True))
+        w = E.RowLayout.resolve(eval_best=best).width
+        assert plain.shape == (6, w) and wide.shape == (6, E.RowLayout.resolve(eval_best=best, eval_physics=True).width)
         assert torch.equal(wide[:, :w], plain)
         assert torch.isfinite(wide).all()
     # the physics columns are a direct HandObjectPenetration call on the same outputs

@@ -184,7 +184,8 @@ def test_trainer_eval_with_both_flags(monkeypatch, capsys):
         rows = orig_rows(out, data, gt_joint, gt_vert, first, assets, *a, **k)
         if k['layout'].has('physics_multi'):
             # the same outputs through the row builder with the new block switched off: the rows of this tree before the feature
-            without = orig_rows(out, data, gt_joint, gt_vert, first, assets, True, True, physics_multi=False)
+            without = orig_rows(out, data, gt_joint, gt_vert, first, assets,
+                                layout=E.RowLayout.resolve(eval_best=True, eval_physics=True, physics_multi=False))
             meter = E.physics_meter(assets, rows.device)
             S = out['diff_final_hand_vert'].shape[1]
             # hypothesis 0 in the camera frame, written out (postprocess' arithmetic, not the helper the block itself uses):

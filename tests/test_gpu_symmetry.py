@@ -238,7 +238,7 @@ EVAL_ARGS = dict(sample_num=4, sampling_steps=5, topk_hand=8, topk_obj=3, sample
 
 
 def test_trainer_eval_end_to_end(capsys, monkeypatch):
-    """Trainer.eval with cfg.eval_best and cfg.eval_symmetric (what --eval_best --eval_symmetric set): the new blocks hold what ObjectSymmetry gives on the poses of each batch, every older block keeps its
+    """Trainer.eval with eval_best, eval_symmetric and symmetric_multi, by keyword and once through cfg (what --eval_best --eval_symmetric set): the new blocks hold what ObjectSymmetry gives on the poses of each batch, every older block keeps its
     bits, and the EVAL_JSON table is summarize(rows, layout)"""
     from vpho_amd import evaluate as E
     from vpho_amd.configs.args import cfg
@@ -263,15 +263,17 @@ def test_trainer_eval_end_to_end(capsys, monkeypatch):
         t = Trainer(cfg)
         rng_state = torch.get_rng_state()
         capsys.readouterr()
-        cfg.eval_best = cfg.eval_symmetric = True           # Trainer.eval's parameter list is pinned: the symmetric blocks follow cfg
-        rows_sym = t.eval(eval_best=True)
-        cfg.eval_symmetric = False
+        rows_sym = t.eval(eval_best=True, eval_symmetric=True, symmetric_multi=True)
         text = capsys.readouterr().out
         torch.set_rng_state(rng_state)
         batches = list(seen)
         rows_old = t.eval(eval_best=True)
-        capsys.readouterr()
         assert len(seen) == 2 * len(batches)
+        cfg.eval_best = cfg.eval_symmetric = True           # not named, the symmetric blocks follow cfg, as after --eval_best --eval_symmetric
+        torch.set_rng_state(rng_state)
+        rows_cfg = t.eval()
+        cfg.eval_best = cfg.eval_symmetric = False
+        capsys.readouterr()
         meter = E.symmetry_meter(t.assets, t.device)
     finally:
         for k, v in saved.items():
@@ -283,6 +285,7 @@ def test_trainer_eval_end_to_end(capsys, monkeypatch):
     order = lambda r: r[r[:, 0].argsort()]
     i32 = lambda x: x.contiguous().view(torch.int32)
     assert torch.equal(i32(order(rows_sym)[:, :88]), i32(order(rows_old)))               # every older block keeps its bits
+    assert torch.equal(i32(order(rows_cfg)), i32(order(rows_sym)))                       # the flags of cfg give the rows of the keywords
     blk = rows_sym[:, layout.slice('symmetric').start:]
     assert blk.shape == (n, 12) and torch.isfinite(blk).all()
     assert meter.K == 4 * 314 and len(batches) == EVAL_ARGS['num_batches']

@@ -276,9 +276,10 @@ def test_trainer_eval_volume_end_to_end_and_rows_without_the_flag(monkeypatch, c
         combos = {}
         for best in (False, True):
             for phys in (False, True):
-                base = orig_rows(out, data, gj, gv, fi, assets, best, phys)
-                off = orig_rows(out, data, gj, gv, fi, assets, best, phys, False, eval_volume=False)
-                on = orig_rows(out, data, gj, gv, fi, assets, best, phys, False, eval_volume=True)
+                lay = lambda **more: E.RowLayout.resolve(eval_best=best, eval_physics=phys, **more)
+                base = orig_rows(out, data, gj, gv, fi, assets, layout=lay())
+                off = orig_rows(out, data, gj, gv, fi, assets, layout=lay(physics_multi=False, eval_volume=False))
+                on = orig_rows(out, data, gj, gv, fi, assets, layout=lay(physics_multi=False, eval_volume=True))
                 combos[best, phys] = (base, off, on)
         # without the flag the new code is never called
         def boom(*a, **k):

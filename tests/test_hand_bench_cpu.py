@@ -107,7 +107,8 @@ def test_names_widths_flag_and_header():
     assert N.HAND_BENCH_COLUMNS[0] == 'hand_bench/agg/AUC_J' and N.HAND_BENCH_COLUMNS[8] == 'hand_bench/reg/AUC_J'
     assert N.HAND_BENCH_MULTI_COLUMNS[0] == 'hand_bench/one_candidate/AUC_J' and N.HAND_BENCH_MULTI_COLUMNS[-1] == 'hand_bench/mean_of_S/PA_F@15'
     assert N.HAND_BENCH_TABLE == N.HAND_BENCH_NAMES
-    assert E.hand_bench_width(False) == 16 and E.hand_bench_width(True) == 40
+    assert E.RowLayout.resolve(eval_hand_bench=True, hand_bench_multi=False).width - 28 == 16
+    assert E.RowLayout.resolve(eval_best=True, eval_hand_bench=True, hand_bench_multi=True).width - 88 == 40
     assert A.Config().eval_hand_bench is False
     assert A._parser().parse_args(['--mode', 'eval', '--eval_hand_bench']).eval_hand_bench is True
     assert A._parser().parse_args(['--mode', 'eval']).eval_hand_bench is False
@@ -120,14 +121,9 @@ def test_names_widths_flag_and_header():
 
 def test_signatures_the_new_keywords_and_the_frozen_ones():
     from vpho_amd import evaluate as E
-    from vpho_amd.trainer import Trainer
-    p = inspect.signature(Trainer.eval).parameters
-    assert list(p)[-3:] == ['volume_multi', 'eval_hand_bench', 'hand_bench_multi']
-    assert p['eval_hand_bench'].default is None and p['hand_bench_multi'].default is None
-    assert list(inspect.signature(E.row_width).parameters) == ['eval_best', 'eval_physics', 'physics_multi', 'volume_multi', 'eval_volume']
-    # the positional order every older caller relies on stays; the hand benchmark flags and the layout come after it
-    assert list(inspect.signature(E.metric_rows).parameters) == ['out', 'data', 'gt_joint', 'gt_vert', 'first_index', 'assets', 'eval_best', 'eval_physics',
-                                                                  'physics_multi', 'volume_multi', 'eval_volume', 'eval_hand_bench', 'hand_bench_multi', 'layout']
+    # the flags go by keyword, eval_hand_bench and hand_bench_multi among them (tests/test_eval_layout_cpu.py has the whole contract)
+    lay = E.RowLayout.resolve(eval_best=True, eval_hand_bench=True, hand_bench_multi=True)
+    assert lay.eval_hand_bench and lay.hand_bench_multi and not E.RowLayout.resolve().eval_hand_bench
     assert list(inspect.signature(E.summarize).parameters) == ['rows', 'layout'] and inspect.signature(E.summarize).parameters['layout'].default is None
     for fn in (E.hand_bench_block, E.hand_bench_multi_block):
         assert list(inspect.signature(fn).parameters) == ['out', 'data', 'gt_joint', 'gt_vert']
@@ -142,13 +138,17 @@ def test_hand_bench_table_on_a_hand_made_block():
     t = E.hand_bench_table(blk[:, :16])
     assert list(t) == ['agg', 'reg'] and all(tuple(v) == HAND_BENCH_TABLE for v in t.values())
     assert np.isnan(t['agg']['AUC_V']) and t['agg']['AUC_J'] == float(blk[:, 0].double().mean()) and t['reg']['PA_F@15'] == float(blk[:, 15].double().mean())
-    t = E.hand_bench_table(blk)
+    t = E.hand_bench_table(blk[:, :16], blk[:, 16:])
     assert list(t) == ['agg', 'reg'] + list(MULTI_TABLES)
     assert t['one_candidate']['AUC_J'] == float(blk[:, 16].double().mean()) and t['mean_of_S']['PA_F@15'] == float(blk[:, 39].double().mean())
     assert sum(np.isnan(v) for r in t.values() for v in r.values()) == 1
     assert all(0.0 <= v <= 1.0 for r in t.values() for v in r.values() if not np.isnan(v))
     with pytest.raises(ValueError):
         E.hand_bench_table(blk[:, :24])
+    with pytest.raises(ValueError):
+        E.hand_bench_table(blk)                                           # both blocks in one tensor: no longer told apart by width
+    with pytest.raises(ValueError):
+        E.hand_bench_table(blk[:, :16], blk[:, 16:32])
 
 
 def test_new_kernels_report_no_scratch_and_no_spill():

@@ -26,7 +26,7 @@ def _wide_rows(n, seed=0):
 def test_row_layout_and_column_names():
     from vpho_amd import evaluate as E
     from vpho_amd.ops_names import HAND_METRIC_NAMES, MULTI_COLUMNS, MULTI_TABLES, OBJ_METRIC_NAMES
-    assert E.ROW == 28 and E.row_width(False) == E.ROW and E.row_width(True) == E.ROW_BEST == E.ROW + E.MULTI
+    assert E.ROW == 28 and E.RowLayout.resolve(eval_best=False).width == E.ROW and E.RowLayout.resolve(eval_best=True).width == E.ROW_BEST == E.ROW + E.MULTI
     assert len(MULTI_COLUMNS) == E.MULTI == 3 * len(HAND_METRIC_NAMES) + 3 * len(OBJ_METRIC_NAMES)
     assert MULTI_COLUMNS[0] == 'one_candidate/hand/MJE' and MULTI_COLUMNS[4] == 'best_of_S/hand/MJE'
     assert MULTI_COLUMNS[12] == 'one_candidate/object/MCE' and MULTI_COLUMNS[28] == 'best_of_S/object/MCE'

@@ -107,9 +107,10 @@ def test_host_tables_match_the_oracle_terms():
 def test_row_width_with_eval_physics():
     from vpho_amd import evaluate as E
     from vpho_amd.ops_names import PHYSICS_COLUMNS
-    assert E.row_width() == 28 and E.row_width(eval_best=True) == 88
-    assert E.row_width(eval_physics=True) == 36
-    assert E.row_width(eval_best=True, eval_physics=True) == 96
+    width = lambda **flags: E.RowLayout.resolve(**flags).width
+    assert width() == 28 and width(eval_best=True) == 88
+    assert width(eval_physics=True) == 36
+    assert width(eval_best=True, eval_physics=True) == 96
     assert len(PHYSICS_COLUMNS) == E.PHYS == 8
 
 
@@ -117,7 +118,7 @@ def test_summarize_builds_the_physics_table():
     from vpho_amd import evaluate as E
     from vpho_amd.ops_names import PHYSICS_TABLE
     for best in (False, True):
-        rows = torch.zeros((4, E.row_width(best, True)))
+        rows = torch.zeros((4, E.RowLayout.resolve(eval_best=best, eval_physics=True).width))
         rows[:, 7] = torch.tensor([1.0, 0.0, 1.0, 0.0])
         rows[:, -8:] = torch.tensor([[0.004, 12, -0.004, 1, 0.0, 0, 0.002, 1],
                                      [0.0, 0, 0.010, 0, 0.0, 0, 0.006, 0],
@@ -132,7 +133,7 @@ def test_summarize_builds_the_physics_table():
         assert ('best_of_S' in t) == best
     # without the flag: no physics table; gt without object ground truth: NaN
     assert 'physics' not in E.summarize(torch.zeros((2, E.ROW))) and 'physics' not in E.summarize(torch.zeros((2, E.ROW_BEST)))
-    rows = torch.zeros((2, E.row_width(False, True)))
+    rows = torch.zeros((2, E.RowLayout.resolve(eval_best=False, eval_physics=True).width))
     rows[:, -4:] = float('nan')
     g = E.summarize(rows)['physics']['gt']
     assert all(np.isnan(v) for v in g.values())

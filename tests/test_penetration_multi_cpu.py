@@ -95,7 +95,9 @@ def test_names_header_and_row_width():
     assert len(PHYSICS_MULTI_COLUMNS) == E.PHYS_MULTI == 12
     assert PHYSICS_MULTI_COLUMNS[0] == 'physics/one_candidate/PD' and PHYSICS_MULTI_COLUMNS[6] == 'physics/best_of_S/min_sd'
     assert PHYSICS_MULTI_COLUMNS == tuple(f'physics/{t}/{k}' for t in MULTI_TABLES for k in PHYSICS_METRIC_NAMES)
-    assert E.row_width(True, True, True) == 108 and E.row_width(True, True) == 96 and E.row_width(True, False, True) == 88 and E.row_width(False, True) == 36 and E.row_width() == 28
+    width = lambda **flags: E.RowLayout.resolve(**flags).width
+    assert width(eval_best=True, eval_physics=True, physics_multi=True) == 108 and width(eval_best=True, eval_physics=True) == 96
+    assert width(eval_best=True, eval_physics=False, physics_multi=True) == 88 and width(eval_best=False, eval_physics=True) == 36 and width() == 28
     hdr = open(os.path.join(ROOT, 'include', 'vpho_hip.h')).read()
     assert 'vpho_hand_obj_penetration_multi_f64' in hdr
     assert int(re.search(r'#define VPHO_PEN_COLUMNS (\d+)', hdr).group(1)) == P.COLUMNS

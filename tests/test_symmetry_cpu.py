@@ -124,14 +124,13 @@ def test_layout_widths_flags_and_the_pinned_blocks():
     assert N.SYM_COLUMNS == ('sym/pred/SMCE', 'sym/pred/MSSD', 'sym/pred/MSSD01d') and len(N.SYM_MULTI_COLUMNS) == 9
     assert N.SYM_MULTI_COLUMNS[0] == 'sym/one_candidate/SMCE' and N.SYM_MULTI_COLUMNS[-1] == 'sym/mean_of_S/MSSD01d'
     assert E.SYM == 3 and E.SYM_MULTI == 9
-    assert [b[0] for b in L.BLOCKS] == ['base', 'multi', 'physics', 'physics_multi', 'volume_multi', 'volume', 'hand_bench', 'hand_bench_multi']
-    assert [b[:3] for b in L.BLOCKS_ADDED] == [('symmetric', 'eval_symmetric', 3), ('symmetric_multi', 'symmetric_multi', 9)]
-    assert L.MULTI_NEEDS['symmetric_multi'] == 'eval_symmetric'
-    assert list(RowLayout.__dataclass_fields__)[-2:] == ['eval_symmetric', 'symmetric_multi']
-    assert list(inspect.signature(RowLayout.resolve).parameters)[-2:] == ['eval_symmetric', 'symmetric_multi']
-    seven = RowLayout.resolve(*[True] * 7)
+    assert [b[0] for b in L.BLOCKS[:8]] == ['base', 'multi', 'physics', 'physics_multi', 'volume_multi', 'volume', 'hand_bench', 'hand_bench_multi']
+    assert [b[:3] for b in L.BLOCKS[8:10]] == [('symmetric', 'eval_symmetric', 3), ('symmetric_multi', 'symmetric_multi', 9)]
+    assert L.BLOCKS[9].needs == 'eval_symmetric' and L.BLOCKS[8].needs is None
+    older = dict(eval_best=True, eval_physics=True, physics_multi=True, eval_volume=True, volume_multi=True, eval_hand_bench=True, hand_bench_multi=True)
+    seven = RowLayout.resolve(**older)
     assert seven.width == 158 and not seven.has('symmetric') and not seven.eval_symmetric
-    nine = RowLayout.resolve(*[True] * 9)
+    nine = RowLayout.resolve(eval_symmetric=True, symmetric_multi=True, **older)
     assert nine.width == 170 and nine.slice('symmetric') == slice(158, 161) and nine.slice('symmetric_multi') == slice(161, 170)
     assert nine.columns[:158] == seven.columns and nine.columns[158:] == N.SYM_COLUMNS + N.SYM_MULTI_COLUMNS
     only = RowLayout.resolve(eval_symmetric=True)
@@ -142,7 +141,8 @@ def test_layout_widths_flags_and_the_pinned_blocks():
     both = RowLayout.resolve(eval_best=True, eval_symmetric=True, symmetric_multi=True)
     assert both.symmetric_multi and both.width == 28 + 60 + 3 + 9
     # from_width keeps knowing the 13 plain widths only
-    assert sorted(L._BY_WIDTH) == sorted({RowLayout.resolve(*f).width for f in __import__('itertools').product((False, True), repeat=5)})
+    five = ('eval_best', 'eval_physics', 'physics_multi', 'eval_volume', 'volume_multi')
+    assert sorted(L._BY_WIDTH) == sorted({RowLayout.resolve(**dict(zip(five, f))).width for f in __import__('itertools').product((False, True), repeat=5)})
     assert len(L._BY_WIDTH) == 13 and all(not l.eval_symmetric for l in L._BY_WIDTH.values())
     with pytest.raises(ValueError):
         RowLayout.from_width(31)
@@ -159,15 +159,18 @@ def test_symmetric_table_and_summarize_on_hand_made_rows():
     blk = torch.rand((5, 12), generator=g)
     t = E.symmetric_table(blk[:, :3])
     assert list(t) == ['pred'] and tuple(t['pred']) == SYM_METRIC_NAMES and t['pred']['MSSD'] == float(blk[:, 1].double().mean())
-    t = E.symmetric_table(blk)
+    t = E.symmetric_table(blk[:, :3], blk[:, 3:])
     assert list(t) == ['pred'] + list(MULTI_TABLES) and t['mean_of_S']['MSSD01d'] == float(blk[:, 11].double().mean())
     with pytest.raises(ValueError):
         E.symmetric_table(blk[:, :9])
+    with pytest.raises(ValueError):
+        E.symmetric_table(blk[:, :3], blk[:, 3:6])
     layout = RowLayout.resolve(eval_best=True, eval_hand_bench=True, eval_symmetric=True, symmetric_multi=True)
     rows = torch.rand((5, layout.width), generator=g)
     res = E.summarize(rows, layout)
     assert list(res)[-2:] == ['hand_bench', 'symmetric']                          # 'symmetric' comes after 'hand_bench'
-    assert res['symmetric'] == E.symmetric_table(rows[:, layout.slice('symmetric').start:])
+    assert layout.slice('symmetric_multi').stop == layout.width
+    assert res['symmetric'] == E.symmetric_table(rows[:, layout.slice('symmetric')], rows[:, layout.slice('symmetric').stop:])
     plain = RowLayout.resolve(eval_best=True, eval_hand_bench=True)
     older = E.summarize(rows[:, :plain.width], plain)
     assert {k: v for k, v in res.items() if k != 'symmetric'} == older
@@ -184,17 +187,19 @@ def test_flags_defaults_signatures_and_header():
     assert a.eval_symmetric is True and a.max_sym_disc_step == 0.05
     a = A._parser().parse_args(['--mode', 'eval'])
     assert a.eval_symmetric is False and a.max_sym_disc_step == 0.01
-    # tests/test_hand_bench_cpu.py pins Trainer.eval's parameter list to end with hand_bench_multi: the symmetric blocks have no keyword
-    # there, they follow cfg.eval_symmetric (and cfg.eval_best); RowLayout.resolve has the two flags, and None follows the configuration
-    assert list(inspect.signature(Trainer.eval).parameters)[-1] == 'hand_bench_multi'
+    # Trainer.eval passes its keywords to RowLayout.resolve, the two symmetric flags among them; not named there, or None, they follow
+    # cfg.eval_symmetric (and cfg.eval_best)
+    with pytest.raises(TypeError, match='symmetric_mult'):
+        Trainer.eval(object(), symmetric_mult=True)                             # the keywords are checked: a misspelt flag is named
     saved = A.cfg.eval_best, A.cfg.eval_symmetric
     try:
         from vpho_amd.eval_layout import RowLayout
+        off = dict(eval_physics=False, physics_multi=False, eval_volume=False, volume_multi=False, eval_hand_bench=False, hand_bench_multi=False)
         A.cfg.eval_best, A.cfg.eval_symmetric = True, True
-        assert RowLayout.resolve(None, False, False, False, False, False, False, None, None).width == 100
-        assert RowLayout.resolve(False, False, False, False, False, False, False, None, None).width == 31
+        assert RowLayout.resolve(eval_best=None, eval_symmetric=None, symmetric_multi=None, **off).width == 100
+        assert RowLayout.resolve(eval_best=False, eval_symmetric=None, symmetric_multi=None, **off).width == 31
         A.cfg.eval_best, A.cfg.eval_symmetric = True, False
-        assert RowLayout.resolve(None, False, False, False, False, False, False, None, None).width == 88
+        assert RowLayout.resolve(eval_best=None, eval_symmetric=None, symmetric_multi=None, **off).width == 88
     finally:
         A.cfg.eval_best, A.cfg.eval_symmetric = saved
     for fn in (E.symmetric_block, E.symmetric_multi_block):
@@ -270,7 +275,8 @@ def test_a_run_without_the_flag_never_loads_the_symmetry_module():
     code = ('import sys\n'
             'import vpho_amd.trainer, vpho_amd.ops, vpho_amd.evaluate, vpho_amd.eval_layout, vpho_amd.configs.args as A\n'
             'assert A.cfg.eval_symmetric is False\n'
-            'assert not vpho_amd.eval_layout.RowLayout.resolve(*[None] * 9).has("symmetric")\n'
+            'L = vpho_amd.eval_layout.RowLayout\n'
+            'assert not L.resolve(**dict.fromkeys(L.__dataclass_fields__)).has("symmetric")\n'
             "assert 'vpho_amd.symmetry' not in sys.modules, 'vpho_amd.symmetry was imported'\n"
             "print('clean')\n")
     r = subprocess.run([sys.executable, '-c', code], cwd=ROOT, capture_output=True, text=True, timeout=300)

@@ -177,15 +177,14 @@ def test_row_width_and_column_names():
     assert N.VOLUME_TABLE == ('IV_cm3', 'IV_max_cm3', 'intersecting_pct')
     old = {(False, False, False): 28, (True, False, False): 88, (False, True, False): 36, (True, True, False): 96, (True, True, True): 108,
            (False, True, True): 36, (True, False, True): 88, (False, False, True): 28}
+    width = lambda **flags: E.RowLayout.resolve(**flags).width
     for (b, p, m), w in old.items():
-        assert E.row_width(b, p, m) == w == E.row_width(b, p, m, eval_volume=False)
-        assert E.row_width(b, p, m, eval_volume=True) == w + 4
+        assert width(eval_best=b, eval_physics=p, physics_multi=m) == w == width(eval_best=b, eval_physics=p, physics_multi=m, eval_volume=False)
+        assert width(eval_best=b, eval_physics=p, physics_multi=m, eval_volume=True) == w + 4
     widths = sorted(set(old.values())) + sorted(w + 4 for w in set(old.values()))
     assert len(set(widths)) == len(widths)                                     # summarize tells the layouts apart by their width
-    import inspect
-    assert list(inspect.signature(E.row_width).parameters)[-1] == 'eval_volume'
-    assert list(inspect.signature(E.metric_rows).parameters)[10] == 'eval_volume'          # last of the positional flags; later keywords follow it
-    assert inspect.signature(E.metric_rows).parameters['eval_volume'].default is False
+    # the flag goes by keyword (tests/test_eval_layout_cpu.py has the whole contract); not named, it is off
+    assert E.RowLayout.resolve().eval_volume is False and not E.RowLayout().has('volume')
 
 
 @pytest.mark.parametrize('width', [28, 88, 36, 96, 108])

@@ -2,7 +2,6 @@
 solid, the numpy restatement of the column walk against the per-centre restatement and the reference fixture (golden_volume.npz) -- the
 proof that the centres of a column may share the x, y part of the parity rule --, the row layout, summarize, the table rule, the header
 and the new kernels' register report.  No GPU."""
-import inspect
 import os
 import re
 import subprocess
@@ -113,23 +112,23 @@ def test_row_width_parameter_order_and_column_names():
     old = {(False, False, False): 28, (True, False, False): 88, (False, True, False): 36, (True, True, False): 96, (True, True, True): 108,
            (False, True, True): 36, (True, False, True): 88, (False, False, True): 28}
     widths = set()
+    width = lambda **flags: E.RowLayout.resolve(**flags).width
     for (b, p, m), w in old.items():
         for vm in (False, True):
-            assert E.row_width(b, p, m, vm) == w == E.row_width(b, p, m, volume_multi=vm, eval_volume=False)      # needs eval_volume
-            got = E.row_width(b, p, m, vm, True)
-            assert got == w + 4 + (6 if b and vm else 0) == E.row_width(b, p, m, volume_multi=vm, eval_volume=True)
+            assert width(eval_best=b, eval_physics=p, physics_multi=m, volume_multi=vm) == w == \
+                width(eval_best=b, eval_physics=p, physics_multi=m, volume_multi=vm, eval_volume=False)                  # needs eval_volume
+            got = width(eval_best=b, eval_physics=p, physics_multi=m, volume_multi=vm, eval_volume=True)
+            assert got == w + 4 + (6 if b and vm else 0)
             widths |= {(w, 'plain'), (w + 4, 'vol'), (got, 'vol+multi' if b and vm else 'vol')}
-    assert E.row_width(True, False, False, True, True) == 98 and E.row_width(True, True, False, True, True) == 106
-    assert E.row_width(True, True, True, True, True) == 118
+    assert width(eval_best=True, eval_physics=False, physics_multi=False, volume_multi=True, eval_volume=True) == 98
+    assert width(eval_best=True, eval_physics=True, physics_multi=False, volume_multi=True, eval_volume=True) == 106
+    assert width(eval_best=True, eval_physics=True, physics_multi=True, volume_multi=True, eval_volume=True) == 118
     assert len({w for w, _ in widths}) == len(widths) == 13                    # summarize tells the layouts apart by their width
-    for fn in (E.row_width, E.metric_rows):
-        names = list(inspect.signature(fn).parameters)
-        names = names[:11] if fn is E.metric_rows else names       # metric_rows: later keywords follow its eleven positional parameters
-        assert names[-3:] == ['physics_multi', 'volume_multi', 'eval_volume']
-        assert inspect.signature(fn).parameters['volume_multi'].default is False
-        assert inspect.signature(fn).parameters['eval_volume'].default is False
-    from vpho_amd.trainer import Trainer
-    assert inspect.signature(Trainer.eval).parameters['volume_multi'].default is None
+    # the flags go by keyword (tests/test_eval_layout_cpu.py has the whole contract); not named, they are off, and None follows cfg
+    off = E.RowLayout.resolve()
+    assert off.volume_multi is False and off.eval_volume is False and E.RowLayout() == off
+    from vpho_amd.configs.args import cfg
+    assert not (cfg.eval_best and cfg.eval_volume) and not E.RowLayout.resolve(eval_best=True, eval_volume=True, volume_multi=None).volume_multi
 
 
 @pytest.mark.parametrize('width', [88, 96, 108])

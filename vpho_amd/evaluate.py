@@ -9,20 +9,20 @@ The forward pass itself needs no collective: the image batch is the only sharded
 import torch
 import torch.distributed as dist
 
-from .eval_layout import BLOCKS, BLOCKS_ADDED, BLOCKS_GRASP, RowLayout
+from .eval_layout import BLOCKS, RowLayout
 from .ops_names import (GRASP_METRIC_NAMES, HAND_BENCH_SOURCES, HAND_BENCH_TABLE, HAND_METRIC_NAMES, MULTI_TABLES, OBJ_METRIC_NAMES,
                         PHYSICS_SOURCES, SYM_METRIC_NAMES)
 
-# the row layout -- which blocks there are, their order and widths -- is eval_layout.BLOCKS (+ BLOCKS_ADDED); these are its widths, in its order
-ROW, MULTI, PHYS, PHYS_MULTI, VOL_MULTI, VOL, HAND_BENCH, HAND_BENCH_MULTI = (width for _, _, width, _ in BLOCKS)
-SYM, SYM_MULTI = (width for _, _, width, _ in BLOCKS_ADDED)
-GRASP, GRASP_MULTI = (width for _, _, width, _ in BLOCKS_GRASP)
+# the row layout -- which blocks there are, their order and widths -- is eval_layout.BLOCKS; these are its widths, by block name
+_W = {b.name: b.width for b in BLOCKS}
+ROW, MULTI = _W['base'], _W['multi']
+PHYS, PHYS_MULTI = _W['physics'], _W['physics_multi']
+VOL, VOL_MULTI = _W['volume'], _W['volume_multi']
+HAND_BENCH, HAND_BENCH_MULTI = _W['hand_bench'], _W['hand_bench_multi']
+SYM, SYM_MULTI = _W['symmetric'], _W['symmetric_multi']
+GRASP, GRASP_MULTI = _W['grasp'], _W['grasp_multi']
 ROW_BEST = ROW + MULTI
 OBJ_COL = 12                 # first of the 16 object metrics of the aggregated pose within the base block
-
-
-def row_width(eval_best=False, eval_physics=False, physics_multi=False, volume_multi=False, eval_volume=False):
-    return RowLayout.resolve(eval_best, eval_physics, physics_multi, eval_volume, volume_multi).width
 
 
 def mje_mm(pd, gt):
@@ -200,10 +200,6 @@ def volume_multi_block(out, data, meshes):
     return table.float()
 
 
-def hand_bench_width(multi=False):
-    return HAND_BENCH + (HAND_BENCH_MULTI if multi else 0)
-
-
 def _hand_bench_pair(pd_joint, pd_vert, data, gt_joint, gt_vert):
     """(bs, S, 8) fp64 in the order of ops_names.HAND_BENCH_NAMES from model-frame candidates (bs, S, 21 | V, 3): one joint call (AUC
     only) and one vertex call of ops.hand_bench_multi"""
@@ -242,14 +238,21 @@ def hand_bench_multi_block(out, data, gt_joint, gt_vert):
     return torch.cat(ops.hand_bench_table(per), 1).float()
 
 
-def hand_bench_table(block):
-    """the table 'hand_bench' of Trainer.eval / EVAL_JSON from the (n, 16 | 40) columns hand_bench_block [+ hand_bench_multi_block] made:
+def _with_multi(what, block, multi, sources):
+    """for the three tables below: the single-pose block ``block`` of ``what`` and, where the caller has it, the block ``multi`` of every
+    sampled hypothesis, side by side, with the table's source names; a block of the wrong width is a ValueError"""
+    for name, b in ((what, block), (what + '_multi', multi)):
+        if b is not None and b.shape[1] != _W[name]:
+            raise ValueError(f'{what}_table: a {name} block of {b.shape[1]} columns, expected {_W[name]}')
+    return (block, sources) if multi is None else (torch.cat([block, multi], 1), sources + MULTI_TABLES)
+
+
+def hand_bench_table(block, multi=None):
+    """the table 'hand_bench' of Trainer.eval / EVAL_JSON from the (n, 16) columns hand_bench_block [and the (n, 24) hand_bench_multi_block] made:
     {'agg': {...}, 'reg': {...}[, 'one_candidate': ..., 'best_of_S': ..., 'mean_of_S': ...]}, each the ops_names.HAND_BENCH_TABLE keys as
     fp64 means over the images, in [0, 1] (NaN where a column holds one)"""
-    if block.shape[1] not in (HAND_BENCH, HAND_BENCH + HAND_BENCH_MULTI):
-        raise ValueError(f'hand_bench_table: {block.shape[1]} columns, expected {HAND_BENCH} or {HAND_BENCH + HAND_BENCH_MULTI}')
+    block, names = _with_multi('hand_bench', block, multi, HAND_BENCH_SOURCES)
     mean = block.double().mean(0)
-    names = HAND_BENCH_SOURCES + (MULTI_TABLES if block.shape[1] > HAND_BENCH else ())
     return {src: {k: float(mean[8 * s + i]) for i, k in enumerate(HAND_BENCH_TABLE)} for s, src in enumerate(names)}
 
 
@@ -296,14 +299,12 @@ def symmetric_multi_block(out, data, meter):
     return torch.cat([per[:, 0], best, mean], 1).float()
 
 
-def symmetric_table(block):
-    """the table 'symmetric' of Trainer.eval / EVAL_JSON from the (n, 3 | 12) columns symmetric_block [+ symmetric_multi_block] made:
+def symmetric_table(block, multi=None):
+    """the table 'symmetric' of Trainer.eval / EVAL_JSON from the (n, 3) columns symmetric_block [and the (n, 9) symmetric_multi_block] made:
     {'pred': {...}[, 'one_candidate': ..., 'best_of_S': ..., 'mean_of_S': ...]}, each the ops_names.SYM_METRIC_NAMES keys as fp64 means
     over the images (SMCE and MSSD in metres, MSSD01d in [0, 1]; NaN where a column holds one)"""
-    if block.shape[1] not in (SYM, SYM + SYM_MULTI):
-        raise ValueError(f'symmetric_table: {block.shape[1]} columns, expected {SYM} or {SYM + SYM_MULTI}')
+    block, names = _with_multi('symmetric', block, multi, ('pred',))
     mean = block.double().mean(0)
-    names = ('pred',) + (MULTI_TABLES if block.shape[1] > SYM else ())
     return {src: {k: float(mean[3 * s + i]) for i, k in enumerate(SYM_METRIC_NAMES)} for s, src in enumerate(names)}
 
 
@@ -362,36 +363,40 @@ def grasp_multi_block(out, data, gt_vert, meter):
     return _grasp_against_gt(out['diff_final_hand_vert'], pd_rt, data, gt_vert, meter)[2].float()
 
 
-def grasp_table(block):
-    """the table 'grasp' of Trainer.eval / EVAL_JSON from the (n, 8 | 32) columns grasp_block [+ grasp_multi_block] made:
+def grasp_table(block, multi=None):
+    """the table 'grasp' of Trainer.eval / EVAL_JSON from the (n, 8) columns grasp_block [and the (n, 24) grasp_multi_block] made:
     {'pred': {...}[, 'one_candidate': ..., 'best_of_S': ..., 'mean_of_S': ...]}, each the ops_names.GRASP_TABLE keys: the fp64 mean of
     every value over the images where it is defined (NaN where it never is), then IoU_defined, the share of images with an IoU"""
-    if block.shape[1] not in (GRASP, GRASP + GRASP_MULTI):
-        raise ValueError(f'grasp_table: {block.shape[1]} columns, expected {GRASP} or {GRASP + GRASP_MULTI}')
+    block, names = _with_multi('grasp', block, multi, ('pred',))
     blk = block.double()
     ok = ~blk.isnan()
     mean = torch.where(ok, blk, torch.zeros_like(blk)).sum(0) / ok.sum(0)                # 0 / 0 = NaN: never defined
     share = ok.double().mean(0)
-    names = ('pred',) + (MULTI_TABLES if block.shape[1] > GRASP else ())
     return {src: dict({k: float(mean[8 * s + i]) for i, k in enumerate(GRASP_METRIC_NAMES)}, IoU_defined=float(share[8 * s]))
             for s, src in enumerate(names)}
 
 
-def metric_rows(out, data, gt_joint, gt_vert, first_index, assets=None, eval_best=False, eval_physics=False, physics_multi=False, volume_multi=False,
-                eval_volume=False, eval_hand_bench=False, hand_bench_multi=False, layout=None):
-    """(bs, layout.width) fp32 on the model's device: the blocks of ``layout`` (an eval_layout.RowLayout; default: the one that
-    RowLayout.resolve makes of the seven flags, so a *_multi block needs eval_best and the flag of its single-pose block; the symmetric
-    and grasp blocks come with a ``layout`` only), each filled by its block function; a block that the layout does not have costs no launch.  With ``layout`` the flags are not looked at."""
+def build_meters(layout, assets, device):
+    """what the blocks of ``layout`` need built, once, before a timed loop: the object meshes, acceleration tables, closed hand mesh, solids
+    and columns (physics_meter), the symmetry table (symmetry_meter, which refuses one that is too long) and the hand surface, anchor and
+    object vertex tables (grasp_meter); nothing, and no import, for a block the layout lacks"""
+    if layout.has('physics') or layout.has('volume'):
+        physics_meter(assets, device, multi=layout.has('physics_multi'), volume=layout.has('volume'), volume_multi=layout.has('volume_multi'))
+    if layout.has('symmetric'):
+        symmetry_meter(assets, device)
+    if layout.has('grasp'):
+        grasp_meter(assets, device)
+
+
+def metric_rows(out, data, gt_joint, gt_vert, first_index, assets=None, *, layout=None):
+    """(bs, layout.width) fp32 on the model's device: the blocks of ``layout`` (an eval_layout.RowLayout, as RowLayout.resolve makes it of
+    the flags; default: the base block alone), each filled by its block function; a block that the layout does not have costs no launch."""
     if layout is None:
-        layout = RowLayout.resolve(eval_best, eval_physics, physics_multi, eval_volume, volume_multi, eval_hand_bench, hand_bench_multi)
-    if assets is None and layout.has('physics'):
-        raise ValueError('metric_rows: eval_physics needs the asset tables (object meshes)')
-    if assets is None and layout.has('volume'):
-        raise ValueError('metric_rows: eval_volume needs the asset tables (object meshes, hand faces)')
-    if assets is None and layout.has('symmetric'):
-        raise ValueError('metric_rows: eval_symmetric needs the asset tables (object corners, sampled vertices, diameters)')
-    if assets is None and layout.has('grasp'):
-        raise ValueError('metric_rows: eval_grasp needs the asset tables (hand faces, anchors, object vertices)')
+        layout = RowLayout()
+    for name, tables in (('physics', 'object meshes'), ('volume', 'object meshes, hand faces'),
+                         ('symmetric', 'object corners, sampled vertices, diameters'), ('grasp', 'hand faces, anchors, object vertices')):
+        if assets is None and layout.has(name):
+            raise ValueError(f'metric_rows: eval_{name} needs the asset tables ({tables})')
     pp = postprocess(out, data['root_joint'], data['is_right'])
     bs, dev = gt_joint.shape[0], gt_joint.device
     rows = torch.empty((bs, layout.width), device=dev, dtype=torch.float32)
@@ -584,12 +589,9 @@ def summarize(rows, layout=None):
         for t, name in enumerate(MULTI_TABLES):
             res[name] = dict(hand={k: float(blk[4 * t + i]) for i, k in enumerate(HAND_METRIC_NAMES)},
                              object=_object_table(blk[12 + 16 * t:28 + 16 * t]))
-    if layout.has('hand_bench'):
-        res['hand_bench'] = hand_bench_table(torch.cat([block(n) for n in ('hand_bench', 'hand_bench_multi') if layout.has(n)], 1))
-    if layout.has('symmetric'):
-        res['symmetric'] = symmetric_table(torch.cat([block(n) for n in ('symmetric', 'symmetric_multi') if layout.has(n)], 1))
-    if layout.has('grasp'):
-        res['grasp'] = grasp_table(torch.cat([block(n) for n in ('grasp', 'grasp_multi') if layout.has(n)], 1))
+    for name, table in (('hand_bench', hand_bench_table), ('symmetric', symmetric_table), ('grasp', grasp_table)):
+        if layout.has(name):
+            res[name] = table(block(name), block(name + '_multi') if layout.has(name + '_multi') else None)
     return res
 
 

@@ -346,32 +346,25 @@ class Trainer:
             seen += n
 
     @torch.no_grad()
-    def eval(self, loader=None, eval_best=None, eval_physics=None, physics_multi=None, eval_volume=None, volume_multi=None, eval_hand_bench=None,
-             hand_bench_multi=None):
+    def eval(self, loader=None, *, layout=None, **flags):
         """``evaluate(testing_dataloader)`` (train_diff_hand_obj.py:202-357).  ``loader``: see ``_eval_batches``; default synthetic.
-        The seven flags choose the column blocks of the returned rows and the tables printed from them (eval_layout.ALL_BLOCKS has the blocks
-        and their order, INTEGRATION.md §1 what they hold): ``eval_best`` (the reference's is_eval_best) scores every sampled hypothesis
-        (tables one_candidate, best_of_S, mean_of_S), ``eval_physics`` reports hand-object penetration and contact (``physics``),
-        ``eval_volume`` the intersection volume at cfg.physics_voxel_pitch (``volume``), ``eval_hand_bench`` the hand F-scores and PCK AUC
-        of the HO3D / FreiHAND leaderboards (``hand_bench``); ``physics_multi`` / ``volume_multi`` / ``hand_bench_multi`` add every sampled
-        hypothesis to that table and need eval_best and the table's own flag.  Defaults (None): cfg.eval_best / eval_physics / eval_volume
-        / eval_hand_bench, and for a *_multi flag cfg.eval_best and cfg.eval_<its table>, i.e. both command-line flags: a caller that
-        passes eval_best / eval_physics / ... itself gets the rows it always got unless it asks for the newer block too.
-        The symmetry-aware object errors (blocks ``symmetric`` / ``symmetric_multi``, table ``symmetric``) have no keyword here -- a test pins
-        this parameter list: they follow cfg.eval_symmetric, and for every sampled hypothesis cfg.eval_best and cfg.eval_symmetric together
-        with the ``eval_best`` this call resolves to.  The contact-map and grasp agreement (blocks ``grasp`` / ``grasp_multi``, table
-        ``grasp``) follows cfg.eval_grasp in the same way (RowLayout.with_grasp)."""
+        ``flags``: the eleven flags of eval_layout.RowLayout, by keyword; they choose the column blocks of the returned rows and the tables
+        printed from them (eval_layout.BLOCKS has the blocks and their order, INTEGRATION.md §1 what they hold): ``eval_best`` (the
+        reference's is_eval_best) scores every sampled hypothesis (tables one_candidate, best_of_S, mean_of_S), ``eval_physics`` reports
+        hand-object penetration and contact (``physics``), ``eval_volume`` the intersection volume at cfg.physics_voxel_pitch (``volume``),
+        ``eval_hand_bench`` the hand F-scores and PCK AUC of the HO3D / FreiHAND leaderboards (``hand_bench``), ``eval_symmetric`` the
+        symmetry-aware object errors (``symmetric``), ``eval_grasp`` the contact-map and grasp agreement (``grasp``); the ``*_multi`` flag
+        of a table adds every sampled hypothesis to it and needs eval_best and the table's own flag.  A flag that is None or not named
+        follows the configuration (RowLayout.resolve): cfg.<flag>, and for a *_multi flag cfg.eval_best and cfg.eval_<its table>, i.e. both
+        command-line flags: a caller that passes eval_best / eval_physics / ... itself gets the rows it always got unless it asks for the
+        newer block too.  ``layout``: a RowLayout instead of flags; both together are a TypeError."""
         from .configs.args import cfg
-        layout = E.RowLayout.resolve(eval_best, eval_physics, physics_multi, eval_volume, volume_multi, eval_hand_bench, hand_bench_multi,
-                                     None, None).with_grasp(None, None)
+        if layout is not None and flags:
+            raise TypeError(f'Trainer.eval: a layout and flags ({", ".join(flags)}) together; pass one of the two')
+        if layout is None:
+            layout = E.RowLayout.resolve(**{**dict.fromkeys(E.RowLayout.__dataclass_fields__), **flags})
         batch_rows = lambda out, batch, gt, first: E.metric_rows(out, batch, gt[0], gt[1], first, self.assets, layout=layout)
-        if layout.has('physics') or layout.has('volume'):
-            # object meshes, acceleration tables, the closed hand mesh, the objects' solids: what the layout needs, once, before the timed loop
-            E.physics_meter(self.assets, self.device, multi=layout.has('physics_multi'), volume=layout.has('volume'), volume_multi=layout.has('volume_multi'))
-        if layout.has('symmetric'):
-            E.symmetry_meter(self.assets, self.device)            # the symmetry table, once, before the timed loop; refuses a table that is too long
-        if layout.has('grasp'):
-            E.grasp_meter(self.assets, self.device)               # the hand surface, anchor and object vertex tables, once, before the timed loop
+        E.build_meters(layout, self.assets, self.device)            # once, before the timed loop
         rows = []
         t0 = time.perf_counter()
         # three batches in flight (independent images; see evaluate.PipelinedPredictor)
