@@ -1,4 +1,7 @@
-"""CPU-side checks: the C-ABI library loads and exports every symbol include/vpho_hip.h declares; host-side packing."""
+"""CPU-side checks: the C-ABI library loads and exports every symbol include/vpho_hip.h declares; host-side packing.
+
+The ABI version and the number of entry points are spelled in this file and in no other test: a pull request that adds an entry point
+changes the two numbers below, the header, common.cpp, ops.py and the two documents, and nothing else that counts."""
 import ctypes
 import os
 import re
@@ -8,6 +11,8 @@ import torch
 import torch.nn.functional as F
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ABI_VERSION = 14
+ENTRY_POINTS = 134
 
 
 def _declared():
@@ -16,7 +21,7 @@ def _declared():
     return sorted(set(re.findall(r'\b(vpho_[a-z0-9_]+)\s*\(', src)))
 
 
-def test_library_exports_every_declared_symbol_at_abi_13():
+def test_library_exports_every_declared_symbol_at_the_pinned_abi_version():
     import __graft_entry__ as g
     g.build()
     lib = ctypes.CDLL(os.path.join(ROOT, 'vpho_amd', 'libvpho_hip.so'))
@@ -25,7 +30,38 @@ def test_library_exports_every_declared_symbol_at_abi_13():
     for n in names:
         assert hasattr(lib, n), f'{n} declared in include/vpho_hip.h but not exported'
     lib.vpho_abi_version.restype = ctypes.c_int
-    assert lib.vpho_abi_version() == 13
+    assert lib.vpho_abi_version() == ABI_VERSION
+
+
+def test_the_abi_version_is_one_number_in_the_header_the_library_and_the_binding():
+    """the header's comment, common.cpp, ops.ABI_VERSION and the library that ops loaded: a stale library is refused when ops is imported
+    (ops.py compares the two), not found out by a missing symbol halfway through a run"""
+    import __graft_entry__ as g
+    g.build()
+    hdr = open(os.path.join(ROOT, 'include', 'vpho_hip.h')).read()
+    m = re.search(r'vpho_abi_version\(void\);\s*/\* (\d+) \*/', hdr)
+    assert m and int(m.group(1)) == ABI_VERSION
+    src = open(os.path.join(ROOT, 'vpho_amd', 'csrc', 'common.cpp')).read()
+    m = re.search(r'vpho_abi_version\((void)?\)\s*\{\s*return (\d+);', src)
+    assert m and int(m.group(2)) == ABI_VERSION
+    from vpho_amd import ops
+    assert ops.ABI_VERSION == ABI_VERSION and ops.lib.vpho_abi_version() == ABI_VERSION
+    binding = open(os.path.join(ROOT, 'vpho_amd', 'ops.py')).read()
+    assert re.search(r'if lib\.vpho_abi_version\(\) != ABI_VERSION:\s*raise ImportError', binding)
+    for doc in ('README.md', 'INTEGRATION.md'):
+        assert re.search(r'version %d\b' % ABI_VERSION, open(os.path.join(ROOT, doc)).read()), doc
+
+
+def test_the_entry_point_count_is_one_number_in_the_header_the_library_and_the_documents():
+    import subprocess
+    import __graft_entry__ as g
+    g.build()
+    hdr = open(os.path.join(ROOT, 'include', 'vpho_hip.h')).read()
+    assert hdr.count('VPHO_API ') - 1 == ENTRY_POINTS == len(_declared())          # the #define aside: one per declaration
+    out = subprocess.run(['nm', '-D', '--defined-only', os.path.join(ROOT, 'vpho_amd', 'libvpho_hip.so')], capture_output=True, text=True, check=True).stdout
+    assert len([l for l in out.splitlines() if l.strip()]) == ENTRY_POINTS
+    assert f'{ENTRY_POINTS} entry points' in open(os.path.join(ROOT, 'README.md')).read()
+    assert f'exactly the {ENTRY_POINTS} `vpho_*` entry points' in open(os.path.join(ROOT, 'INTEGRATION.md')).read()
 
 
 def test_library_exports_nothing_but_the_header():
@@ -130,7 +166,12 @@ def test_ctypes_structures_mirror_the_header_field_for_field():
     hs = _header_structs()
     pairs = {'vpho_conv_desc': ops.ConvDesc, 'vpho_score_weights': ops.ScoreWeights, 'vpho_ode_stats': ops.OdeStats,
              'vpho_mano_tables': ops.ManoTables, 'vpho_obj_tables': ops.ObjTables, 'vpho_anchor_tables': ops.AnchorTables,
-             'vpho_obj_metric_tables': ops.ObjMetricTables}
+             'vpho_obj_metric_tables': ops.ObjMetricTables, 'vpho_obj_symmetry_tables': ops.ObjSymmetryTables,
+             'vpho_obj_mesh_tables': ops.ObjMeshTables, 'vpho_obj_mesh_accel': ops.ObjMeshAccel, 'vpho_obj_solids': ops.ObjSolids,
+             'vpho_obj_solid_columns': ops.ObjSolidColumns, 'vpho_hand_surface_table': ops.HandSurfaceTable,
+             'vpho_obj_vertex_accel': ops.ObjVertexAccel, 'vpho_mesh_table': ops.MeshTable, 'vpho_render_layer': ops.RenderLayer}
+    # every struct the header defines has its mirror here: a new one cannot be added without it
+    assert set(pairs) == set(hs) and len(hs) == 16, sorted(set(pairs) ^ set(hs))
     kind = {ctypes.c_void_p: 'ptr', ctypes.c_int: 'int', ctypes.c_float: 'float', ctypes.c_double: 'double', ctypes.c_longlong: 'longlong'}
     for name, cls in pairs.items():
         assert name in hs, name

@@ -146,9 +146,7 @@ def test_header_prototypes_count_and_version():
                      r'int n, int S, int Nh,[^;]*float\* weight, int\* nn_index, double\* nd, double\* vd, void\* stream\);', hdr)
     assert re.search(r'VPHO_API int vpho_contact_agreement_f32\(const float\* weight, const float\* weight_gt,[^;]*int\* counts, double\* values, '
                      r'double\* table, void\* stream\);', hdr)
-    assert re.search(r'vpho_abi_version\(void\);\s*\/\* 13 \*\/', hdr)
-    count = hdr.count('VPHO_API ') - 1
-    assert count == 128
+    count = hdr.count('VPHO_API ') - 1                              # the number itself is pinned in tests/test_abi.py
     for doc in ('README.md', 'INTEGRATION.md'):
         text = open(os.path.join(ROOT, doc)).read()
         assert (f'{count} entry points' in text or f'exactly the {count} ' in text) and 'contact_multi.hip' in text, doc

@@ -114,9 +114,9 @@ def test_names_widths_flag_and_header():
     assert A._parser().parse_args(['--mode', 'eval']).eval_hand_bench is False
     hdr = open(os.path.join(ROOT, 'include', 'vpho_hip.h')).read()
     assert re.search(r'VPHO_API int vpho_hand_bench_multi_f32\(', hdr) and re.search(r'VPHO_API int vpho_hand_bench_table_f64\(', hdr)
-    assert re.search(r'vpho_abi_version\(void\);\s*\/\* 13 \*\/', hdr)                     # additions only: the ABI stays 13
+    count = hdr.count('VPHO_API ') - 1                              # the documents say what the header says
     for doc in ('README.md', 'INTEGRATION.md'):
-        assert '111' in open(os.path.join(ROOT, doc)).read()
+        assert f'{count} ' in open(os.path.join(ROOT, doc)).read(), (doc, count)
 
 
 def test_signatures_the_new_keywords_and_the_frozen_ones():

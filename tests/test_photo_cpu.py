@@ -319,45 +319,40 @@ def test_photo_kernels_report_no_spill_and_no_scratch():
     assert lds['photo_levels_kernel'] == 0 and lds['photo_colour_kernel'] == 0 and 0 < lds['photo_clahe_lut_kernel'] <= 8192
 
 
-def test_the_photo_library_exports_what_its_header_declares_and_the_main_abi_is_as_it_was():
-    """csrc/photo.hip is a library of its own, libvpho_photo.so, with include/vpho_photo.h as its whole dynamic symbol table; the main
-    library and include/vpho_hip.h carry nothing of it (their entry-point count is pinned by the tests that came with them)"""
+def test_the_photo_entry_points_are_declared_in_the_one_header_and_exported_by_the_one_library():
+    """csrc/photo.hip links into libvpho_hip.so like every other kernel file: its six entry points are declared in include/vpho_hip.h with
+    VPHO_API and exported by the library.  How many entry points there are, the ABI version, that the exports equal the header and that
+    every `_call` in ops.py passes what the prototype declares are tests/test_abi.py's business"""
     from vpho_amd import build as B
     B.build_extension()
-    hdr = open(os.path.join(ROOT, 'include', 'vpho_photo.h')).read()
-    for proto in (r'VPHO_PHOTO_API const char\* vpho_photo_last_error\(void\);',
-                  r'VPHO_PHOTO_API int vpho_photo_levels_u8\(const unsigned char\* frames, int n, int H, int W, const double\* minv, int P, unsigned char\* out, void\* stream\);',
-                  r'VPHO_PHOTO_API int vpho_photo_clahe_lut_u8\(const unsigned char\* levels, const int\* clip, int n, int P, unsigned char\* l8, unsigned char\* lut, void\* stream\);',
-                  r'VPHO_PHOTO_API int vpho_photo_clahe_apply_u8\(const unsigned char\* levels, const int\* clip,[^;]*unsigned char\* l8_out, void\* stream\);',
-                  r'VPHO_PHOTO_API int vpho_photo_grey_sum_u8\(const unsigned char\* levels, const float\* colour, int n, int P, long long\* sums, void\* stream\);',
-                  r'VPHO_PHOTO_API int vpho_photo_colour_u8\(const unsigned char\* levels, const float\* colour, const float\* contrast, const float\* hue,[^;]*void\* stream\);',
-                  r'VPHO_PHOTO_API int vpho_photo_filter_f32\(const unsigned char\* levels, const float\* k1, const int\* K1, const float\* k2, const int\* K2,[^;]*float\* out, void\* stream\);'):
+    hdr = open(os.path.join(ROOT, 'include', 'vpho_hip.h')).read()
+    for proto in (r'VPHO_API int vpho_photo_levels_u8\(const unsigned char\* frames, int n, int H, int W, const double\* minv, int P, unsigned char\* out, void\* stream\);',
+                  r'VPHO_API int vpho_photo_clahe_lut_u8\(const unsigned char\* levels, const int\* clip, int n, int P, unsigned char\* l8, unsigned char\* lut, void\* stream\);',
+                  r'VPHO_API int vpho_photo_clahe_apply_u8\(const unsigned char\* levels, const int\* clip,[^;]*unsigned char\* l8_out, void\* stream\);',
+                  r'VPHO_API int vpho_photo_grey_sum_u8\(const unsigned char\* levels, const float\* colour, int n, int P, long long\* sums, void\* stream\);',
+                  r'VPHO_API int vpho_photo_colour_u8\(const unsigned char\* levels, const float\* colour, const float\* contrast, const float\* hue,[^;]*void\* stream\);',
+                  r'VPHO_API int vpho_photo_filter_f32\(const unsigned char\* levels, const float\* k1, const int\* K1, const float\* k2, const int\* K2,[^;]*float\* out, void\* stream\);'):
         assert re.search(proto, hdr), proto
     assert 'base.py:349-397' in hdr
-    declared = sorted(set(re.findall(r'\b(vpho_[a-z0-9_]+)\s*\(', re.sub(r'/\*.*?\*/', '', hdr, flags=re.S))))
-    assert len(declared) == 7 == hdr.count('VPHO_PHOTO_API ') - 1
-    nm = lambda lib: sorted(l.split()[-1] for l in subprocess.run(['nm', '-D', '--defined-only', lib], capture_output=True, text=True, check=True).stdout.splitlines()
-                            if l.strip())
-    assert nm(B.PHOTO_LIB) == declared
-    main = nm(B.LIB)
-    assert not [n for n in main if 'photo' in n] and 'photo' not in open(os.path.join(ROOT, 'include', 'vpho_hip.h')).read()
-    # every call of ops.py into the library names a declared function and passes as many arguments as it has before the stream
+    declared = sorted(set(re.findall(r'\b(vpho_photo_[a-z0-9_]+)\s*\(', re.sub(r'/\*.*?\*/', '', hdr, flags=re.S))))
+    assert len(declared) == 6
+    nm = subprocess.run(['nm', '-D', '--defined-only', B.LIB], capture_output=True, text=True, check=True).stdout
+    exported = sorted(l.split()[-1] for l in nm.splitlines() if l.strip())
+    assert [n for n in exported if 'photo' in n] == declared
+    # every photo op of ops.py goes through the one `_call`, once each
     src = open(os.path.join(ROOT, 'vpho_amd', 'ops.py')).read()
-    calls = re.findall(r"_photo_call\('(vpho_photo_[a-z0-9_]+)'", src)
-    assert sorted(calls) == [d for d in declared if d != 'vpho_photo_last_error']
-    import ast
-    flat = re.sub(r'/\*.*?\*/', ' ', hdr, flags=re.S)
-    for node in ast.walk(ast.parse(src)):
-        if isinstance(node, ast.Call) and isinstance(node.func, ast.Name) and node.func.id == '_photo_call':
-            name = node.args[0].value
-            params = re.search(name + r'\s*\(([^)]*)\)', flat).group(1).split(',')
-            assert len(node.args) - 1 == len(params) - 1 and 'stream' in params[-1], (name, len(node.args) - 1, len(params))
+    assert sorted(re.findall(r"\b_call\('(vpho_photo_[a-z0-9_]+)'", src)) == declared
     for doc in ('README.md', 'INTEGRATION.md'):
-        txt = open(os.path.join(ROOT, doc)).read()
-        assert 'libvpho_photo.so' in txt and 'photo.hip' in txt, doc
-    # frames.hip is as it was: the copies in photo.hip are held to it on the GPU, here only that the file still has its two kernels
+        assert 'photo.hip' in open(os.path.join(ROOT, doc)).read(), doc
+    # frames.hip keeps its two kernels; what photo.hip shares with it is one copy, in frames_common.h
     src = open(os.path.join(ROOT, 'vpho_amd', 'csrc', 'frames.hip')).read()
     assert src.count('__global__') == 2 and 'photo' not in src
+    photo = open(os.path.join(ROOT, 'vpho_amd', 'csrc', 'photo.hip')).read()
+    common = open(os.path.join(ROOT, 'vpho_amd', 'csrc', 'frames_common.h')).read()
+    for shared in ('philox4x32_10', 'unit23', 'box_muller', 'cubic_weights', 'level', 'bicubic_crop', 'normalise_erase'):
+        assert len(re.findall(r'__device__ __forceinline__ \w+ ' + shared + r'\(', common)) == 1, shared
+        assert not re.search(r'__device__[^;{]*\b' + shared + r'\(', src + photo), shared
+    assert '__global__' not in common and '#include "frames_common.h"' in src and '#include "frames_common.h"' in photo
 
 
 _DEFAULTS_SCRIPT = '''

@@ -229,9 +229,6 @@ def test_header_declares_the_entry_points_within_abi_13():
     assert len(args) == 15 and args[-1] == 'void* stream' and args[0].startswith('const vpho_obj_mesh_tables*')
     assert [a.split()[-1] for a in args[2:13]] == ['faces', 'F', 'verts', 'n', 'V', 'obj_rt', 'obj_id', 'pitch', 'out', 'flags', 'workspace']
     assert re.search(r'VPHO_API long long vpho_hand_obj_intersection_workspace_bytes\(', code)
-    assert re.search(r'vpho_abi_version\(void\);\s*/\* 13 \*/', txt)
-    src = open(os.path.join(ROOT, 'vpho_amd', 'csrc', 'common.cpp')).read()
-    assert re.search(r'vpho_abi_version\((void)?\)\s*\{\s*return 13;', src)
 
 
 # ------------------------------------------------------------------------------------------------------------ kernel resources

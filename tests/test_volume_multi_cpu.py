@@ -195,9 +195,6 @@ def test_header_declares_both_entry_points_within_abi_13():
     assert re.search(r'VPHO_API long long vpho_hand_obj_intersection_multi_workspace_bytes\(int n, int S, int F\)\s*;', code)
     s = re.search(r'typedef struct vpho_obj_solid_columns \{(.*?)\} vpho_obj_solid_columns;', code, flags=re.S)
     assert s and [' '.join(x.split()) for x in s.group(1).split(';') if x.strip()] == ['const int* col_start', 'const int* col_offset', 'int n_obj, max_cols']
-    assert re.search(r'vpho_abi_version\(void\);\s*/\* 13 \*/', txt)
-    src = open(os.path.join(ROOT, 'vpho_amd', 'csrc', 'common.cpp')).read()
-    assert re.search(r'vpho_abi_version\((void)?\)\s*\{\s*return 13;', src)
     # the split of pen_parity_step lives beside it; the step itself and its three callers are as they were
     common = open(os.path.join(ROOT, 'vpho_amd', 'csrc', 'penetration_common.h')).read()
     assert all(f'__device__ inline {sig}' in common for sig in ('void pen_parity_step(', 'bool pen_parity_xy(', 'void pen_parity_z('))

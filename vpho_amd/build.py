@@ -1,5 +1,4 @@
-"""Build ``vpho_amd/libvpho_hip.so`` (the HIP kernels + the C ABI of include/vpho_hip.h) and ``vpho_amd/libvpho_photo.so`` (csrc/photo.hip, the
-C ABI of include/vpho_photo.h) for gfx950 with hipcc, in-tree.
+"""Build ``vpho_amd/libvpho_hip.so`` (the HIP kernels + the C ABI of include/vpho_hip.h) for gfx950 with hipcc, in-tree.
 
 ``python -m vpho_amd.build`` or ``build_extension()``; objects are cached under ``vpho_amd/csrc/_obj`` by mtime.
 """
@@ -13,10 +12,6 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 OBJ = os.path.join(CSRC, '_obj')
 LIB = os.path.join(HERE, 'libvpho_hip.so')
-# the photometric augmentation is a library of its own: the ABI of include/vpho_hip.h is closed at its 128 entry points.  It links its own
-# copy of common.cpp (error slot, launch checks) and exports nothing but vpho_photo_*
-PHOTO_LIB = os.path.join(HERE, 'libvpho_photo.so')
-PHOTO_SOURCES = ('photo.hip',)
 ARCH = 'gfx950'
 FLAGS = ['-O3', '-std=c++17', '-fPIC', f'--offload-arch={ARCH}', '-ffp-contract=off', '-fvisibility=hidden', '-fvisibility-inlines-hidden', '-Wall', '-Wno-unused-function']
 
@@ -35,7 +30,6 @@ def sources():
 def _newest_header():
     hs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.h')]
     hs.append(os.path.join(os.path.dirname(HERE), 'include', 'vpho_hip.h'))
-    hs.append(os.path.join(os.path.dirname(HERE), 'include', 'vpho_photo.h'))
     return max(os.path.getmtime(h) for h in hs)
 
 
@@ -75,14 +69,7 @@ def build_extension(force=False, verbose=False):
         vmap = os.path.join(OBJ, 'exports.map')
         with open(vmap, 'w') as f:
             f.write('{ global: vpho_*; local: *; };\n')
-        main = [o for o in objs if os.path.basename(o)[:-2] not in PHOTO_SOURCES]
-        run([cc, '-shared', '-fPIC', f'--offload-arch={ARCH}', f'-Wl,--version-script={vmap}', '-o', LIB] + main)
-    if jobs or not os.path.exists(PHOTO_LIB):
-        pmap = os.path.join(OBJ, 'exports_photo.map')
-        with open(pmap, 'w') as f:
-            f.write('{ global: vpho_photo_*; local: *; };\n')
-        photo = [o for o in objs if os.path.basename(o)[:-2] in PHOTO_SOURCES + ('common.cpp',)]
-        run([cc, '-shared', '-fPIC', f'--offload-arch={ARCH}', f'-Wl,--version-script={pmap}', '-o', PHOTO_LIB] + photo)
+        run([cc, '-shared', '-fPIC', f'--offload-arch={ARCH}', f'-Wl,--version-script={vmap}', '-o', LIB] + objs)
     return LIB
 
 

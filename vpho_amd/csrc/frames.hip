@@ -4,45 +4,13 @@
 //   heatmap_targets_kernel  lib/utils/misc_fn.py:285-385 (HeatmapGenerator.get_heatmap, AdaptiveHeatmapGenerator.__call__)
 // Both are one thread per output pixel, no LDS, no atomics; every index into the frame, the Gaussian table and the output is checked.
 #include "common.h"
+#include "frames_common.h"
 #include "../../include/vpho_hip.h"
 #include <cstdint>
 
 namespace {
 
-// ---------------------------------------------------------------------------------------------------------------- Philox4x32-10
-struct U4 { uint32_t x, y, z, w; };
-__device__ __forceinline__ U4 philox4x32_10(U4 c, uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c.x, p1 = (uint64_t)0xCD9E8D57u * c.z;
-        c = U4{(uint32_t)(p1 >> 32) ^ c.y ^ k0, (uint32_t)p1, (uint32_t)(p0 >> 32) ^ c.w ^ k1, (uint32_t)p0};
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return c;
-}
-// a word's upper 23 bits as u = (k + 0.5) / 2^23 in (0, 1): exact in fp32, never 0 or 1
-__device__ __forceinline__ float unit23(uint32_t w) { return ((float)(w >> 9) + 0.5f) * (1.0f / 8388608.0f); }
-// Box-Muller: r = sqrt(-2 ln u1), (r cos 2 pi u2, r sin 2 pi u2); |value| <= sqrt(2 * 24 ln 2) = 5.77
-__device__ __forceinline__ void box_muller(uint32_t a, uint32_t b, float& z0, float& z1) {
-    const float r = sqrtf(-2.0f * logf(unit23(a)));
-    float s, c;
-    sincospif(2.0f * unit23(b), &s, &c);
-    z0 = r * c;
-    z1 = r * s;
-}
-
 // ---------------------------------------------------------------------------------------------------------------- warp + colour
-// Keys' cubic convolution weights with A = -0.75 for the taps at floor - 1 .. floor + 2 (OpenCV's interpolateCubic)
-__device__ __forceinline__ void cubic_weights(float t, float* w) {
-    const float A = -0.75f;
-    w[0] = ((A * (t + 1.f) - 5.f * A) * (t + 1.f) + 8.f * A) * (t + 1.f) - 4.f * A;
-    w[1] = ((A + 2.f) * t - (A + 3.f)) * t * t + 1.f;
-    w[2] = ((A + 2.f) * (1.f - t) - (A + 3.f)) * (1.f - t) * (1.f - t) + 1.f;
-    w[3] = 1.f - w[0] - w[1] - w[2];
-}
-__device__ __forceinline__ float level(float v) { return fminf(fmaxf(rintf(v), 0.f), 255.f); }      // a NaN becomes 0
-
 struct PatchArgs {
     const unsigned char* frames; const double* minv; const float* colour; const unsigned char* flip; const int* erase; const unsigned int* key;
     float* out; int H, W, P;
@@ -55,40 +23,8 @@ __global__ __launch_bounds__(256) void frame_patch_kernel(const PatchArgs a) {
     const int y = (int)(pix / P), x = (int)(pix % P);
     const bool flip = a.flip && a.flip[s];
     const int xs = flip ? P - 1 - x : x;                                         // the patch column that lands here
-    const double* m = a.minv + 6 * (long long)s;
-    const double sx = m[0] * xs + m[1] * y + m[2], sy = m[3] * xs + m[4] * y + m[5];
-    float v[3] = {0.f, 0.f, 0.f};
-    // a coordinate that leaves every tap outside the frame (or is not finite) gives the border value 0
-    if (sx > -3.0 && sx < (double)a.W + 2.0 && sy > -3.0 && sy < (double)a.H + 2.0) {
-        const double fx = floor(sx), fy = floor(sy);
-        const int ix = (int)fx, iy = (int)fy;
-        float wx[4], wy[4];
-        cubic_weights((float)(sx - fx), wx);
-        cubic_weights((float)(sy - fy), wy);
-        const unsigned char* f = a.frames + (long long)s * a.H * a.W * 3;
-        float acc[3] = {0.f, 0.f, 0.f};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int yy = iy - 1 + j;
-            float row[3] = {0.f, 0.f, 0.f};
-            if (yy >= 0 && yy < a.H) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int xx = ix - 1 + i;
-                    if (xx >= 0 && xx < a.W) {
-                        const unsigned char* p = f + ((long long)yy * a.W + xx) * 3;
-                        row[0] += wx[i] * (float)p[0];
-                        row[1] += wx[i] * (float)p[1];
-                        row[2] += wx[i] * (float)p[2];
-                    }
-                }
-            }
-            acc[0] += wy[j] * row[0];
-            acc[1] += wy[j] * row[1];
-            acc[2] += wy[j] * row[2];
-        }
-        v[0] = level(acc[0]); v[1] = level(acc[1]); v[2] = level(acc[2]);
-    }
+    float v[3];
+    bicubic_crop(a.frames + (long long)s * a.H * a.W * 3, a.H, a.W, a.minv + 6 * (long long)s, xs, y, v);
     if (a.colour) {                                                              // every stage ends on an integer grey level
         const float* c = a.colour + 5 * (long long)s;
         const float b = c[3], sat = c[4];
@@ -101,22 +37,8 @@ __global__ __launch_bounds__(256) void frame_patch_kernel(const PatchArgs a) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) v[k] = level(sat * v[k] + g1);
     }
-    const float mean[3] = {0.485f, 0.456f, 0.406f}, sd[3] = {0.229f, 0.224f, 0.225f};
     float o[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) o[k] = (v[k] / 255.0f - mean[k]) / sd[k];
-    if (a.erase) {
-        const int* e = a.erase + 16 * (long long)s;
-        bool in = false;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) in = in || (x >= e[4 * r] && x < e[4 * r + 2] && y >= e[4 * r + 1] && y < e[4 * r + 3]);
-        if (in) {
-            const U4 w = philox4x32_10(U4{(uint32_t)pix, 0u, 0u, 0u}, a.key[2 * s], a.key[2 * s + 1]);
-            float z3;
-            box_muller(w.x, w.y, o[0], o[1]);
-            box_muller(w.z, w.w, o[2], z3);
-        }
-    }
+    normalise_erase(v, a.erase, a.key, s, x, y, pix, o);
     float* q = a.out + (long long)s * 3 * P * P + pix;
     q[0] = o[0];
     q[(long long)P * P] = o[1];

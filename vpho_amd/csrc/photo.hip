@@ -9,43 +9,14 @@
 //   photo_filter_kernel      two K x K filters (K <= 7) with reflect-101 borders from LDS tiles, mirror, normalisation, erasing
 // Integer atomics only (LDS histogram, one 64-bit add per workgroup for the grey sum): nothing depends on the order of workgroups.
 // Every index into a frame, a plane, a LUT, an LDS tile and the output is checked.
-// Built into a library of its own, libvpho_photo.so (include/vpho_photo.h), with its own copy of common.cpp and hence its own error slot.
+// The bicubic crop, level(), the normalisation and the erasing are frames.hip's own code (frames_common.h).
 #include "common.h"
-#include "../../include/vpho_photo.h"
+#include "frames_common.h"
+#include "../../include/vpho_hip.h"
 #include <cstdint>
 
 namespace {
 
-// ---------------------------------------------------------------------------------------------------------------- as in frames.hip
-// Philox4x32-10, unit23, Box-Muller, the Keys weights and level(): copies of frames.hip, which keeps its two kernels and its compiler
-// report to itself; tests/test_gpu_photo.py holds these copies to the originals bit for bit.
-struct U4 { uint32_t x, y, z, w; };
-__device__ __forceinline__ U4 philox4x32_10(U4 c, uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c.x, p1 = (uint64_t)0xCD9E8D57u * c.z;
-        c = U4{(uint32_t)(p1 >> 32) ^ c.y ^ k0, (uint32_t)p1, (uint32_t)(p0 >> 32) ^ c.w ^ k1, (uint32_t)p0};
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return c;
-}
-__device__ __forceinline__ float unit23(uint32_t w) { return ((float)(w >> 9) + 0.5f) * (1.0f / 8388608.0f); }
-__device__ __forceinline__ void box_muller(uint32_t a, uint32_t b, float& z0, float& z1) {
-    const float r = sqrtf(-2.0f * logf(unit23(a)));
-    float s, c;
-    sincospif(2.0f * unit23(b), &s, &c);
-    z0 = r * c;
-    z1 = r * s;
-}
-__device__ __forceinline__ void cubic_weights(float t, float* w) {
-    const float A = -0.75f;
-    w[0] = ((A * (t + 1.f) - 5.f * A) * (t + 1.f) + 8.f * A) * (t + 1.f) - 4.f * A;
-    w[1] = ((A + 2.f) * t - (A + 3.f)) * t * t + 1.f;
-    w[2] = ((A + 2.f) * (1.f - t) - (A + 3.f)) * (1.f - t) * (1.f - t) + 1.f;
-    w[3] = 1.f - w[0] - w[1] - w[2];
-}
-__device__ __forceinline__ float level(float v) { return fminf(fmaxf(rintf(v), 0.f), 255.f); }      // a NaN becomes 0
 __device__ __forceinline__ float level64(double v) { return (float)fmin(fmax(rint(v), 0.0), 255.0); }
 
 // ---------------------------------------------------------------------------------------------------------------- levels
@@ -55,39 +26,8 @@ __global__ __launch_bounds__(256) void photo_levels_kernel(const unsigned char* 
     const long long pix = (long long)blockIdx.x * 256 + threadIdx.x;
     if (pix >= (long long)P * P) return;
     const int y = (int)(pix / P), x = (int)(pix % P);
-    const double* m = minv + 6 * (long long)s;
-    const double sx = m[0] * x + m[1] * y + m[2], sy = m[3] * x + m[4] * y + m[5];
-    float v[3] = {0.f, 0.f, 0.f};
-    if (sx > -3.0 && sx < (double)W + 2.0 && sy > -3.0 && sy < (double)H + 2.0) {
-        const double fx = floor(sx), fy = floor(sy);
-        const int ix = (int)fx, iy = (int)fy;
-        float wx[4], wy[4];
-        cubic_weights((float)(sx - fx), wx);
-        cubic_weights((float)(sy - fy), wy);
-        const unsigned char* f = frames + (long long)s * H * W * 3;
-        float acc[3] = {0.f, 0.f, 0.f};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int yy = iy - 1 + j;
-            float row[3] = {0.f, 0.f, 0.f};
-            if (yy >= 0 && yy < H) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int xx = ix - 1 + i;
-                    if (xx >= 0 && xx < W) {
-                        const unsigned char* p = f + ((long long)yy * W + xx) * 3;
-                        row[0] += wx[i] * (float)p[0];
-                        row[1] += wx[i] * (float)p[1];
-                        row[2] += wx[i] * (float)p[2];
-                    }
-                }
-            }
-            acc[0] += wy[j] * row[0];
-            acc[1] += wy[j] * row[1];
-            acc[2] += wy[j] * row[2];
-        }
-        v[0] = level(acc[0]); v[1] = level(acc[1]); v[2] = level(acc[2]);
-    }
+    float v[3];
+    bicubic_crop(frames + (long long)s * H * W * 3, H, W, minv + 6 * (long long)s, x, y, v);
     unsigned char* q = out + ((long long)s * P * P + pix) * 3;
     q[0] = (unsigned char)v[0];
     q[1] = (unsigned char)v[1];
@@ -390,25 +330,11 @@ __global__ __launch_bounds__(256) void photo_filter_kernel(const FilterArgs a) {
                 v[2] += w * (float)((p >> 16) & 255u);
             }
         v[0] = level(v[0]); v[1] = level(v[1]); v[2] = level(v[2]);
-        // from here on frame_patch_kernel: the patch column x lands at xo, erasing is in output coordinates
+        // from here on as frame_patch_kernel: the patch column x lands at xo, erasing is in output coordinates
         const int xo = flip ? P - 1 - x : x;
         const long long pix = (long long)y * P + xo;
-        const float mean[3] = {0.485f, 0.456f, 0.406f}, sd[3] = {0.229f, 0.224f, 0.225f};
         float o[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) o[k] = (v[k] / 255.0f - mean[k]) / sd[k];
-        if (a.erase) {
-            const int* e = a.erase + 16 * (long long)s;
-            bool in = false;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) in = in || (xo >= e[4 * r] && xo < e[4 * r + 2] && y >= e[4 * r + 1] && y < e[4 * r + 3]);
-            if (in) {
-                const U4 w = philox4x32_10(U4{(uint32_t)pix, 0u, 0u, 0u}, a.key[2 * s], a.key[2 * s + 1]);
-                float z3;
-                box_muller(w.x, w.y, o[0], o[1]);
-                box_muller(w.z, w.w, o[2], z3);
-            }
-        }
+        normalise_erase(v, a.erase, a.key, s, xo, y, pix, o);
         if (bad) o[0] = o[1] = o[2] = __builtin_nanf("");
         float* q = a.out + (long long)s * 3 * P * P + pix;
         q[0] = o[0];
@@ -420,8 +346,6 @@ __global__ __launch_bounds__(256) void photo_filter_kernel(const FilterArgs a) {
 bool photo_sizes_ok(int n, int P) { return n >= 0 && n <= 65535 && P > 0 && P <= 16384; }
 
 }  // namespace
-
-extern "C" const char* vpho_photo_last_error(void) { return vpho::err_slot(); }
 
 extern "C" int vpho_photo_levels_u8(const unsigned char* frames, int n, int H, int W, const double* minv, int P, unsigned char* out, void* stream) {
     VPHO_REQUIRE(photo_sizes_ok(n, P) && H > 0 && W > 0, "vpho_photo_levels_u8: bad size (n %d, H %d, W %d, P %d)", n, H, W, P);

@@ -17,7 +17,7 @@ if not os.path.exists(LIB_PATH):
 lib = C.CDLL(LIB_PATH)
 lib.vpho_last_error.restype = C.c_char_p
 lib.vpho_abi_version.restype = C.c_int
-ABI_VERSION = 13                        # include/vpho_hip.h; a stale library must not be found out by a missing symbol halfway through a run
+ABI_VERSION = 14                        # include/vpho_hip.h; a stale library must not be found out by a missing symbol halfway through a run
 if lib.vpho_abi_version() != ABI_VERSION:
     raise ImportError(f'{LIB_PATH} implements ABI version {lib.vpho_abi_version()}, this binding expects {ABI_VERSION}: rebuild the '
                       f'extension (python -m vpho_amd.build --force)')
@@ -2110,29 +2110,6 @@ def heatmap_targets(pts, box, g, sigma, gmin, size, res=None, left=None, out=Non
 
 
 # ----------------------------------------------------------------------------------------------- photometric augmentation (photo.hip)
-# A library of its own, libvpho_photo.so (include/vpho_photo.h): the ABI of include/vpho_hip.h is closed.  Loaded on first use -- a run that
-# never augments does not open it -- and, like the main library, there is nothing behind it: a missing library is an error.
-PHOTO_LIB_PATH = os.environ.get('VPHO_PHOTO_LIB') or os.path.join(_HERE, 'libvpho_photo.so')
-_photo_lib = None
-
-
-def photo_lib():
-    global _photo_lib
-    if _photo_lib is None:
-        if not os.path.exists(PHOTO_LIB_PATH):
-            raise ImportError(f'{PHOTO_LIB_PATH} is missing: build the HIP extension first (python -m vpho_amd.build or '
-                              f'__graft_entry__.build()); the photometric augmentation has no CPU fallback')
-        _photo_lib = C.CDLL(PHOTO_LIB_PATH)
-        _photo_lib.vpho_photo_last_error.restype = C.c_char_p
-    return _photo_lib
-
-
-def _photo_call(name, *args):
-    plib = photo_lib()
-    if getattr(plib, name)(*args, _stream()) != 0:
-        raise VphoError(plib.vpho_photo_last_error().decode())
-
-
 def _photo_levels(name, levels, clahe=False):
     """the refusals every photo_* op shares, before any launch: (n, P, P, 3) uint8 on the device -> n, P"""
     if not torch.is_tensor(levels) or levels.dim() != 4 or levels.shape[3] != 3 or levels.shape[1] != levels.shape[2] or levels.dtype != torch.uint8:
@@ -2174,7 +2151,7 @@ def photo_levels(frames, minv, patch, out=None):
     if n > 65535 or patch < 1 or patch > 16384:
         raise VphoError(f'photo_levels: n {n} / patch {patch} beyond 65535 images of 16384 pixels a side')
     out = _photo_out('photo_levels', out, (n, patch, patch, 3), frames, torch.uint8)
-    _photo_call('vpho_photo_levels_u8', _u8(frames), I(n), I(H), I(W), _f64(minv), I(patch), _u8(out))
+    _call('vpho_photo_levels_u8', _u8(frames), I(n), I(H), I(W), _f64(minv), I(patch), _u8(out))
     return out
 
 
@@ -2185,7 +2162,7 @@ def photo_clahe_lut(levels, clip):
     n, P = _photo_levels('photo_clahe_lut', levels, clahe=True)
     clip = _photo_host_ints('photo_clahe_lut', 'clip', clip, n, lambda k: 0 <= k <= P * P, 'a clip count in 0 .. P * P').to(levels.device)
     l8, lut = _new((n, P, P), levels, torch.uint8), _new((n, 64, 256), levels, torch.uint8)
-    _photo_call('vpho_photo_clahe_lut_u8', _u8(levels), _i32(clip), I(n), I(P), _u8(l8), _u8(lut))
+    _call('vpho_photo_clahe_lut_u8', _u8(levels), _i32(clip), I(n), I(P), _u8(l8), _u8(lut))
     return l8, lut, clip
 
 
@@ -2198,7 +2175,7 @@ def photo_clahe_apply(levels, clip, l8, lut, out=None, want_l8=False):
             raise VphoError(f'photo_clahe_apply: {name} must be {shape} {dt}')
     out = _photo_out('photo_clahe_apply', out, (n, P, P, 3), levels, torch.uint8)
     l8o = _new((n, P, P), levels, torch.uint8) if want_l8 else None
-    _photo_call('vpho_photo_clahe_apply_u8', _u8(levels), _i32(clip), _u8(l8), _u8(lut), I(n), I(P), _u8(out), _u8(l8o))
+    _call('vpho_photo_clahe_apply_u8', _u8(levels), _i32(clip), _u8(l8), _u8(lut), I(n), I(P), _u8(out), _u8(l8o))
     return (out, l8o) if want_l8 else out
 
 
@@ -2213,7 +2190,7 @@ def photo_grey_sum(levels, colour=None):
     n, P = _photo_levels('photo_grey_sum', levels)
     _photo_rows('photo_grey_sum', 'colour', colour, (n, 5))
     sums = torch.zeros(n, dtype=torch.int64, device=levels.device)
-    _photo_call('vpho_photo_grey_sum_u8', _u8(levels), _f32(colour), I(n), I(P), _ptr(sums, torch.int64))
+    _call('vpho_photo_grey_sum_u8', _u8(levels), _f32(colour), I(n), I(P), _ptr(sums, torch.int64))
     return sums
 
 
@@ -2227,7 +2204,7 @@ def photo_colour(levels, colour=None, contrast=None, hue=None, sums=None, out=No
     if contrast is not None and (sums is None or tuple(sums.shape) != (n,) or sums.dtype != torch.int64):
         raise VphoError('photo_colour: contrast factors need the (n) int64 grey sums of photo_grey_sum')
     out = _photo_out('photo_colour', out, (n, P, P, 3), levels, torch.uint8)
-    _photo_call('vpho_photo_colour_u8', _u8(levels), _f32(colour), _f32(contrast), _f32(hue), None if sums is None else _ptr(sums, torch.int64), I(n), I(P),
+    _call('vpho_photo_colour_u8', _u8(levels), _f32(colour), _f32(contrast), _f32(hue), None if sums is None else _ptr(sums, torch.int64), I(n), I(P),
           _u8(out))
     return out
 
@@ -2250,7 +2227,7 @@ def photo_filter(levels, k1, K1, k2, K2, flip=None, erase=None, key=None, out=No
     if erase is not None and key is None:
         raise VphoError('photo_filter: erase rectangles need a Philox key')
     out = _photo_out('photo_filter', out, (n, 3, P, P), levels, torch.float32)
-    _photo_call('vpho_photo_filter_f32', _u8(levels), _f32(k1), _i32(K1), _f32(k2), _i32(K2), _u8(flip), None if erase is None else _i32(erase),
+    _call('vpho_photo_filter_f32', _u8(levels), _f32(k1), _i32(K1), _f32(k2), _i32(K2), _u8(flip), None if erase is None else _i32(erase),
           None if key is None else _i32(key), I(n), I(P), _f32(out))
     return out
 
