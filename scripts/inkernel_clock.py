@@ -139,7 +139,6 @@ def main():
         x, w, b = rnd(N, H, H, Cc), rnd(Cc, 9 * Cc) * 0.02, rnd(Cc)
         u = winograd_weights(w)
         wgs = (N * H * H // 4 // 64) * (Cc // 64)
-        os.environ['VPHO_WINO8'] = '0'
         run(f'conv_winograd_kernel: 3x3 {Cc} -> {Cc} on {N} x {H} x {H} ({Cc // 8} k stages per workgroup, {wgs} workgroups; TFLOP/s = EXECUTED Winograd products)',
             'wino', lambda: ops.conv3x3_winograd(x, u, b, out_slope=0.01), 2.0 * (N * H * H // 4) * 16 * Cc * Cc, min(wgs, 65536))
     # --- score_head_kernel (hand network, R = 6400 rows x 32 heads)

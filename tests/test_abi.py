@@ -91,12 +91,28 @@ def test_product_library_carries_no_ablation_or_stamp_code():
     env = sorted(set(re.findall(r'VPHO_[A-Z0-9_]+', strs)))
     assert 'VPHO_WINO_ABL' not in env and not [e for e in env if 'ABL' in e or 'STAMP' in e], env
     assert 'vpho_diag_' not in strs
-    macros = ('CONV_ABLATE', 'WINO_ABLATE', 'WINO8_ABLATE', 'FK_ABLATE', 'VPHO_CLOCK_STAMPS')
+    macros = ('CONV_ABLATE', 'WINO_ABLATE', 'FK_ABLATE', 'VPHO_CLOCK_STAMPS')
     assert not [f for f in B.FLAGS if any(m in f for m in macros)], B.FLAGS
     src = open(os.path.join(ROOT, 'vpho_amd', 'csrc', 'conv_igemm.hip')).read()
     # the run-time VPHO_CONV_DBG keeps only its two bit-identical A/B orders
     assert re.search(r'g\.dbg\s*=\s*dbg_env \? \(atoi\(dbg_env\) & \(8 \| 16\)\)', src), 'VPHO_CONV_DBG must be masked to its bit-identical bits'
     assert not re.search(r'g\.dbg & (1|2|4)\b', src)
+
+
+def test_library_reads_the_kept_ab_switches_and_none_of_the_retired_ones():
+    """The A/B switches of kernels that were measured, lost and removed must not come back silently, and the switches whose two sides
+    both still run (each has a bit-identity test of live code against live code) must not be lost by accident: the environment
+    variables the built library names."""
+    import subprocess
+    import __graft_entry__ as g
+    g.build()
+    lib = os.path.join(ROOT, 'vpho_amd', 'libvpho_hip.so')
+    strs = subprocess.run(['strings', '-n', '6', lib], capture_output=True, text=True, check=True).stdout
+    env = set(re.findall(r'VPHO_[A-Z0-9_]+', strs))
+    retired = ('VPHO_PE_RING', 'VPHO_HEAD_PERS', 'VPHO_HEAD_LDS', 'VPHO_WINO8')
+    assert not [e for e in retired if e in env], sorted(env)
+    kept = ('VPHO_HEAD_EPI', 'VPHO_PE_ROWS', 'VPHO_HEAD_CB', 'VPHO_WINO_STAGED')
+    assert not [e for e in kept if e not in env], sorted(env)
 
 
 def test_state_dict_layout_matches_reference_contract(model_cpu):

@@ -65,7 +65,6 @@ BUDGET = {
     'conv_igemm_pers_kernel<128, 128, 4, 2>': (4, 128), 'conv_igemm_pers_bn_kernel<128, 128, 4, 2>': (4, 128),
     'conv_winograd_kernel<0>': (1, 256), 'conv_winograd_kernel<1>': (1, 256), 'conv_winograd_kernel<2>': (1, 256),   # one wave per SIMD by design: 256 accumulators
     'conv_winograd_bn_kernel<0>': (1, 256), 'conv_winograd_bn_kernel<1>': (1, 256), 'conv_winograd_bnb_kernel<0>': (1, 256), 'conv_winograd_bnb_kernel<1>': (1, 256),
-    'conv_winograd8_kernel': (2, 256),
     'conv_wgrad_tn_kernel<64, 64, 2, 2>': (4, 128), 'conv_wgrad_tn_kernel<128, 128, 4, 2>': (4, 128), 'conv_wgrad_tn_kernel<128, 64, 4, 2>': (4, 128),
     'mano_fk_kernel<16>': (3, 168),
 }

@@ -41,6 +41,20 @@ int dynamic_lds(const void* kernel, int bytes) {
     have = bytes;
     return 0;
 }
+
+int workgroup_slots(int* slots) {
+    static int slots_of[64] = {0};
+    int dev = 0;
+    VPHO_HIP(hipGetDevice(&dev));
+    int& have = slots_of[dev & 63];
+    if (!have) {
+        hipDeviceProp_t prop;
+        VPHO_HIP(hipGetDeviceProperties(&prop, dev));
+        have = 2 * prop.multiProcessorCount;
+    }
+    *slots = have;
+    return 0;
+}
 }  // namespace vpho
 
 extern "C" int vpho_prof_enable(int cls, int on) {

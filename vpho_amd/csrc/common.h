@@ -31,6 +31,9 @@ struct ProfScope {
 // Raises a kernel's dynamic-LDS limit (hipFuncAttributeMaxDynamicSharedMemorySize) once per (kernel, device): the attribute belongs to
 // the device's code object, so a process-wide flag would leave a second device's launches without it.
 int dynamic_lds(const void* kernel, int bytes);
+// *slots = 2 x the CU count of the current device: the workgroup slots of the chip-filling kernels (score head, persistent convolution),
+// which are sized for two workgroups per CU.  Per device: one process may drive several GPUs of different sizes.
+int workgroup_slots(int* slots);
 }  // namespace vpho
 
 #define VPHO_REQUIRE(cond, ...) do { if (!(cond)) return vpho::fail(__VA_ARGS__); } while (0)

@@ -1490,15 +1490,8 @@ extern "C" int vpho_conv2d_nhwc_f32(const vpho_conv_desc* dp, void* stream) {
     {
         const char* pe = getenv("VPHO_CONV_PERS");
         const int pers = pe ? atoi(pe) : 1;
-        static int slots_of[64] = {0};
-        int dev = 0;
-        VPHO_HIP(hipGetDevice(&dev));
-        int& slots = slots_of[dev & 63];
-        if (!slots) {
-            hipDeviceProp_t prop;
-            VPHO_HIP(hipGetDeviceProperties(&prop, dev));
-            slots = 2 * prop.multiProcessorCount;
-        }
+        int slots = 0;
+        if (vpho::workgroup_slots(&slots)) return 1;
         const double y_extent = 4.0 * ((double)(d.N - 1) * d.y_sn + (double)(d.OH - 1) * d.y_sy + (double)(d.OW - 1) * d.y_sx + d.Cout);
         const double r_extent = d.res ? 4.0 * ((double)(d.N - 1) * d.r_sn + (double)(d.OH - 1) * d.r_sy + (double)(d.OW - 1) * d.r_sx + d.Cout) : 0.0;
         const bool simple = d.KH == 1 && d.KW == 1 && d.pad_y == 0 && d.pad_x == 0;

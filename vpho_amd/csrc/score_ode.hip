@@ -106,188 +106,19 @@ struct PoseEncArgs {
     float* out; int R;                 // [R][256]
     const RkCtl* ctl; int ctl_mode, write_ynew; const float* kbase; long long n_el; double *ybuf0, *ybuf1;
 };
-constexpr int PE_ROWS = 32, PE_H_LD = 260, PE_NST = 3, PE_STAGE = 256 * 32;
-__device__ __attribute__((aligned(256))) float g_pe_zero_page[64];
+constexpr int PE_ROWS = 32, PE_H_LD = 260;
 
-// 8 waves; wave w owns hidden columns 32w..32w+31 (one 32x32 MFMA tile) of the block's 32 hypotheses.  Both weight
-// matrices stream as ONE sequence of [256][32] chunks (W0's ceil(Dp/32), then W2's 8) through a 3-stage LDS ring filled by
-// global_load_lds (unpadded 128-B rows, 16-B chunk index XOR (row>>1)&7 on the source address), two chunks in flight
-// across each raw s_barrier (counted vmcnt), so the weight latency hides behind the MFMAs and the first two chunks load
-// while the stage state is being formed.  Biases are staged to LDS up front: an ordinary global load consumed while a
-// direct-to-LDS load is in flight would drain the ring (vmcnt is in-order).
-__global__ __launch_bounds__(512) void pose_encoder_kernel(const PoseEncArgs a) {
-    extern __shared__ __attribute__((aligned(1024))) float smem[];
-    const int K1 = (a.Dp + 31) / 32 * 32, X_LD = K1 + 4;
-    float* Ws = smem;                              // [PE_NST][256][32]
-    float* H1 = Ws + PE_NST * PE_STAGE;            // [32][PE_H_LD]
-    float* Bs = H1 + PE_ROWS * PE_H_LD;            // [2][256] biases
-    float* Xs = Bs + 512;                          // [32][X_LD]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, lh = lane >> 5;
-    const int r0 = blockIdx.x * PE_ROWS;
-    const int n1 = K1 / 32, nch = n1 + 8;
-    if (ctl_skip(a.ctl, a.ctl_mode)) return;
-    KSlots ks = a.ks;
-    const double* yv = a.y;
-    double* ynew = a.ynew;
-    double lch = a.lc.h;
-    if (a.ctl && a.ctl_mode == 1 && a.use_lc) {
-        const int par = a.ctl->parity, sw = a.ctl->kswap;
-        yv = par ? a.ybuf1 : a.ybuf0;
-        ynew = a.write_ynew ? (par ? a.ybuf0 : a.ybuf1) : nullptr;
-        lch = a.ctl->h;
-#pragma unroll
-        for (int j = 0; j < 7; ++j) ks.p[j] = a.kbase + (long long)kslot(j, sw) * a.n_el;
-    }
-
-    // ring fill: one wave instruction = 8 rows x 128 B; wave w, pass j fills rows 64j + 8w .. +7
-    const int frow = wave * 8 + (lane >> 3);                               // + 64 j
-    const int fkq = (lane & 7) ^ ((frow >> 1) & 7);                        // logical 16-B chunk (64j keeps (row>>1)&7)
-    auto issue = [&](int c) {
-        float* dst = Ws + (c % PE_NST) * PE_STAGE + wave * 8 * 32;
-        if (c < n1) {
-            const int k = c * 32 + 4 * fkq;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float* src = k < a.Dp ? a.w0 + (long long)(frow + 64 * j) * a.Dp + k : g_pe_zero_page;
-                __builtin_amdgcn_global_load_lds(src, dst + 64 * j * 32, 16, 0, 0);
-            }
-        } else {
-            const float* src = a.w2 + (long long)frow * 256 + (c - n1) * 32 + 4 * fkq;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) __builtin_amdgcn_global_load_lds(src + 64 * j * 256, dst + 64 * j * 32, 16, 0, 0);
-        }
-    };
-    issue(0);
-    issue(1);
-
-    Bs[tid] = tid < 256 ? a.b0[tid] : a.b2[tid - 256];
-    for (int i = tid; i < PE_ROWS * (K1 / 4); i += 512) {
-        const int r = i / (K1 / 4), c = (i - r * (K1 / 4)) * 4;
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (r0 + r < a.R && c < a.Dp) {
-            if (!a.use_lc) v = *reinterpret_cast<const f32x4*>(a.X + (long long)(r0 + r) * a.Dp + c);
-            else {
-                // all seven stage slots are loaded up front (one memory round trip instead of lc.n dependent ones);
-                // slots >= lc.n are read from slot 0 and never enter the sum, which keeps its order j = 0..n-1
-                const long long e0 = (long long)(r0 + r) * a.D + c;
-                float kv[7][4];
-                double yl[4];
-                if ((a.D & 3) == 0) {
-#pragma unroll
-                    for (int j = 0; j < 7; ++j) {
-                        const f32x4 k4 = *reinterpret_cast<const f32x4*>(ks.p[j < a.lc.n ? j : 0] + e0);
-                        kv[j][0] = k4[0]; kv[j][1] = k4[1]; kv[j][2] = k4[2]; kv[j][3] = k4[3];
-                    }
-                    const f64x2 y01 = *reinterpret_cast<const f64x2*>(yv + e0), y23 = *reinterpret_cast<const f64x2*>(yv + e0 + 2);
-                    yl[0] = y01[0]; yl[1] = y01[1]; yl[2] = y23[0]; yl[3] = y23[1];
-                } else {
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const long long e = c + u < a.D ? e0 + u : e0;
-#pragma unroll
-                        for (int j = 0; j < 7; ++j) kv[j][u] = ks.p[j < a.lc.n ? j : 0][e];
-                        yl[u] = yv[e];
-                    }
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    double sacc = 0.0;
-#pragma unroll
-                    for (int j = 0; j < 7; ++j) sacc = j < a.lc.n ? sacc + (double)kv[j][u] * a.lc.c[j] : sacc;
-                    const double xv = yl[u] + sacc * lch;
-                    if (c + u < a.D) {
-                        v[u] = (float)xv;
-                        if (ynew) ynew[e0 + u] = xv;
-                    }
-                }
-            }
-        }
-        *reinterpret_cast<f32x4*>(Xs + r * X_LD + c) = v;
-    }
-
-    f32x16 acc;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-    const int sw = (li >> 1) & 7;
-    struct Frags { f32x4 a[4], b[4]; };
-    auto frags = [&](int c, Frags& f) {
-        const float* As = c < n1 ? Xs + li * X_LD + c * 32 + 4 * lh : H1 + li * PE_H_LD + (c - n1) * 32 + 4 * lh;
-        const float* Wc = Ws + (c % PE_NST) * PE_STAGE + (wave * 32 + li) * 32;
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-            f.a[kk] = *reinterpret_cast<const f32x4*>(As + kk * 8);
-            f.b[kk] = *reinterpret_cast<const f32x4*>(Wc + (((2 * kk + lh) ^ sw) << 2));
-        }
-    };
-    auto mfmas = [&](const Frags& f) {
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(f.a[kk][q], f.b[kk][q], acc, 0, 0, 0);
-    };
-    // Chunk c has landed for this wave once at most the 4 loads of chunk c+1 are outstanding; the barrier makes that true
-    // for every wave's share and retires everybody's fragment reads of stage (c-1)%3, which chunk c+2 then overwrites.
-    // The MFMAs run one phase behind the fragment reads: chunk c's ds_reads overlap chunk c-1's matrix work.
-    auto phase = [&](int c, Frags& fload, const Frags& fuse) {
-        if (c + 1 < nch) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        if (c + 2 < nch) issue(c + 2);
-        if (c != n1) {
-            frags(c, fload);
-            mfmas(fuse);
-        } else {
-            // layer boundary: h1 = relu(acc + b0) -> LDS [row][hidden] (C layout: hidden unit on the lane, hypothesis row
-            // on the register) must be complete in every wave before anyone reads it as the next A operand
-            mfmas(fuse);
-            const int col = wave * 32 + li;
-            const float bv = Bs[col];
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int row = (e & 3) + 8 * (e >> 2) + 4 * lh;
-                const float v = acc[e] + bv;
-                H1[row * PE_H_LD + col] = v > 0.f ? v : 0.f;
-                acc[e] = 0.f;
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-            frags(c, fload);
-        }
-    };
-    Frags f0, f1;
-    asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    issue(2);
-    frags(0, f0);
-    for (int c = 1; c < nch; c += 2) {
-        phase(c, f1, f0);
-        if (c + 1 < nch) phase(c + 1, f0, f1);
-    }
-    mfmas((nch & 1) ? f0 : f1);
-    const int col = wave * 32 + li;
-    const float bv = Bs[256 + col];
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-        const int row = r0 + (e & 3) + 8 * (e >> 2) + 4 * lh;
-        if (row < a.R) {
-            const float v = acc[e] + bv;
-            a.out[(long long)row * 256 + col] = v > 0.f ? v : 0.f;
-        }
-    }
-}
-
-// Round 4: the same two layers with the weight fragments in REGISTERS.  A wave only ever reads its own 32 rows of a weight chunk,
-// so the ring above used LDS as a prefetch buffer, not for sharing: 96 of the kernel's 143 KB, which made a workgroup own its CU --
-// under the pipelined evaluator a pose-encoder workgroup had to wait until BOTH convolution workgroups of a CU had drained (135 us
-// average against 22 us exclusive), 102 times per step on the sampler's serial chain.  Here a lane loads its B fragments
-// (W[32 wave + lane&31][32 c + 8 kk + 4 (lane>>5) .. +3], 16 bytes) straight from L2 into a three-chunk register ring, three chunks
-// ahead of their use; the k order of the products is the ring kernel's, so the outputs are bit-identical.  What is left in LDS: the
-// A operand (stage state X, then -- aliased, the state is dead by then -- the 32 x 256 intermediate) and the biases: 35 KB, three
-// workgroup barriers instead of twelve, <= 128 registers: the footprint of ONE direct-convolution workgroup, so it takes the next
-// free slot of any CU instead of a whole CU.
+// 8 waves; wave w owns hidden columns 32w..32w+31 (one 32x32 MFMA tile) of the workgroup's hypotheses.  Both weight matrices stream as
+// ONE sequence of [256][32] chunks (W0's ceil(Dp/32), then W2's 8) with the weight fragments in REGISTERS: a wave only ever reads its
+// own 32 rows of a weight chunk, so nothing about the weights is shared and LDS would only be a prefetch buffer for them.  A lane loads
+// its B fragments (W[32 wave + lane&31][32 c + 8 kk + 4 (lane>>5) .. +3], 16 bytes) straight from L2 into a three-chunk register ring,
+// three chunks ahead of their use, in the chunk sequence's k order.  In LDS: the A operand (stage state X, then -- aliased, the state
+// is dead by then -- the 32 x 256 intermediate) and the biases: 35 KB, three workgroup barriers, <= 128 registers: the footprint of
+// ONE direct-convolution workgroup, so under the pipelined evaluator a pose-encoder workgroup takes the next free slot of any CU and
+// does not wait for a whole CU to drain (102 launches per step sit on the sampler's serial chain).
+// (Up to commit e9cf68e this file also held two kernels that had lost their measurements and were reachable only through an A/B
+// switch: a pose encoder that staged the weight chunks through a 143 KB LDS ring, one workgroup per CU, and a persistent score head
+// whose workgroups walked several tiles.  Both computed the same bits as the kernels here; docs/LOG.md has the numbers.)
 // RT = row tiles of 32 hypotheses per workgroup.  RT = 1: the kernel as described above.  RT = 2 (round 6, launches of more than 8 192 rows --
 // BASELINE cfg4's 32 768): a workgroup streams the same 352 KB of weights for 64 rows instead of 32 -- every B fragment feeds two matrix
 // instructions, half the L2 -> register weight traffic per row -- with the A fragments read one 8-k slice ahead instead of a whole chunk
@@ -741,7 +572,8 @@ __device__ __forceinline__ void head_tile(const HeadArgs& a, float* smem, const 
     __syncthreads();
     // (Round 5, measured no better on one box, 3 interleaved runs each: the combine WITHOUT this barrier -- the waves that share a row group
     // draw an LDS ticket and the last one combines its 32 rows, 233-238 us against 234-237; s_setprio 1 / 3 around the main loop, 230 against
-    // 228-230 (scripts/build_prio.sh).  With the persistent variant below that is four ways of shortening a tile's life outside its main
+    // 228-230 (scripts/build_prio.sh).  With a workgroup that walks several tiles and requests the next tile's first stages under this epilogue
+    // (profiles/r05_head_persistent_ab.txt: 230-238 us against 232-234) that is four ways of shortening a tile's life outside its main
     // loop without moving the launch time: the 2 x 8 waves of a CU are bound by what they share, not by a workgroup's own serial parts.)
     // One output per thread: thread t -> (row t / 3, component t % 3), 3 x ROWS threads.  Round 4 gave a row's three components to ONE of
     // 128 threads (two of the eight waves: 24 strided LDS reads, three 4-byte stores 384 B apart and three divisions each, behind two
@@ -795,244 +627,6 @@ __global__ __launch_bounds__(512, 4) void score_head_kernel(const HeadArgs a) { 
 // the epilogue as it was before the run layout (VPHO_HEAD_EPI=0): the reference of tests/test_gpu_head_epilogue.py and of the A/B in docs/LOG.md
 template <bool CB>
 __global__ __launch_bounds__(512, 4) void score_head_epi0_kernel(const HeadArgs a) { score_head_body<CB, 0>(a); }
-
-// --------------------------------------------------------------------------------------------- persistent score head (round 5 experiment, opt-in: VPHO_HEAD_PERS=1)
-// The in-kernel stamps of profiles/r05_inkernel_clock.txt: a 128-row tile lives 62 us -- entry 0.7, first fill wait 1.0, main loop 45,
-// epilogue 11 (partial sums 5.5, then a barrier and a combine that keeps 2 of the 8 waves busy for 5.7), slot turnover 0.8 -- and a CU has
-// two workgroups in their main loops for only 46 % of the launch.  Here a workgroup WALKS its tiles (b, b + grid, ...: 128-row tiles of
-// all heads first, then the 32-row tail tiles) and
-//   * requests the next tile's first two k stages -- and loads its epilogue tables into registers -- right behind the current tile's
-//     last barrier, so they land under the epilogue (the partial sums have an LDS region of their own: both stage buffers are free);
-//   * finishes a tile with ONE output per thread (384 threads instead of 128 x 3), written by a buffer store that every thread issues
-//     (an out-of-range offset for the idle ones): the counted wait for the next tile's first stage is exact;
-//   * counts NaNs in a register and adds them once per workgroup.
-// Arithmetic, k order, partial sums and their order are head_tile's: bit-identical scores (tests/test_gpu_sampler.py).
-#define VPHO_WAIT_VMH(n) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(n) : "memory")
-template <bool CB>
-__global__ __launch_bounds__(512, 4) void score_head_pers_kernel(const HeadArgs a) {
-    extern __shared__ __attribute__((aligned(1024))) float smem[];
-    if (ctl_skip(a.ctl, a.ctl_mode)) return;
-    constexpr int STAGE = (256 + 128) * HB_K;
-    constexpr int CPR = HB_K / 4, RPW = 64 / CPR, RPP = 8 * RPW, SW_SHIFT = 2;
-    static_assert(HB_K == 16 && RPP == 128, "fill layout");
-    constexpr int NFW = 256 / RPP, NF = NFW + 1;                    // LDS-DMA instructions per stage and wave: weights + activations
-    constexpr int NK = 256 / HB_K, NKK = HB_K / 8;
-    constexpr int CB_LD = 257, B2_AT = 900;
-    float* Eb = smem + 2 * STAGE;                                    // [256][4] {ct, w2_0, w2_1, w2_2} of the tile's head
-    float* Cb = Eb + 256 * 4;                                        // [3][257] per-image terms of the tile's images | b2 of the head at [B2_AT..+2]
-    float* Ob = Cb + 1024;                                           // [8 parts][128 rows][4] partial outputs
-    VPHO_STAMP_INIT();
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), li = lane & 31, lh = lane >> 5;
-    const int n_full = a.nheads * a.full_tiles, total = n_full + a.nheads * a.tail_tiles, G = gridDim.x;
-    int b = blockIdx.x;
-    if (b >= total) return;
-    float inv_std = a.inv_std_den, coef = a.coef;
-    float* outp = a.out;
-    if (a.ctl && a.ctl_mode == 1) {
-        inv_std = a.ctl->inv_std[a.stage]; coef = a.ctl->coef[a.stage];
-        outp = a.kbase + (long long)kslot(a.out_slot, a.ctl->kswap) * a.n_el;
-    }
-    const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.w1p), 0, 0xFFFFFFF0u, 0x00020000);
-    const __amdgpu_buffer_rsrc_t pr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.p2), 0, 0xFFFFFFF0u, 0x00020000);
-    const __amdgpu_buffer_rsrc_t orr = __builtin_amdgcn_make_buffer_rsrc(outp, 0, 0xFFFFFFF0u, 0x00020000);
-    typedef __attribute__((address_space(3))) void* lds_ptr;
-    const int lrow = wave * RPW + lane / CPR;
-    const int kq = (lane % CPR) ^ ((lrow >> SW_SHIFT) & (CPR - 1));
-    int woff[NFW];
-#pragma unroll
-    for (int j = 0; j < NFW; ++j) woff[j] = ((lrow + RPP * j) * 256 + 4 * kq) * 4;
-
-    // tile b -> head n, first row r0, rows (128 | 32)
-    auto tile_of = [&](int t, int& n, int& r0, int& rows) {
-        if (t < n_full) { n = t / a.full_tiles; r0 = (t - n * a.full_tiles) * 128; rows = 128; }
-        else { const int q = t - n_full; n = q / a.tail_tiles; r0 = a.full_tiles * 128 + (q - n * a.tail_tiles) * 32; rows = 32; }
-    };
-    int poff;                                                        // activation row of this lane in the tile being filled
-    auto set_poff = [&](int r0, int rows) {
-        const int r = r0 + lrow;
-        poff = (r < a.R && lrow < rows) ? (int)(((unsigned)r * 256u + 4u * (unsigned)kq) * 4u) : -1;
-    };
-    auto fill = [&](int buf, int kt, int n) {
-        float* Ws = smem + buf * STAGE + wave * RPW * HB_K;
-        float* Ps = smem + buf * STAGE + 256 * HB_K + wave * RPW * HB_K;
-        const int koff = kt * HB_K * 4, wbase = n * (256 * 256 * 4) + koff;
-#pragma unroll
-        for (int j = 0; j < NFW; ++j) {
-            const int wo = woff[j];
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(wr, (lds_ptr)(Ws + RPP * j * HB_K), 16, wo, wbase, 0, 0);
-        }
-        const int po = poff;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(pr, (lds_ptr)Ps, 16, po, koff, 0, 0);
-    };
-    // epilogue tables of a tile, into one f32x4 per thread: threads 0..255 the head's row {ct, w2}, threads 256..511 column j = tid - 256 of
-    // the per-image terms of the (at most 3) images the tile spans, and b2 of the head in the first three of them
-    // (tq: the thread index as an OPAQUE per-call value -- everything derived from a visible threadIdx.x is loop-invariant over the tiles,
-    // gets hoisted out of the tile loop and spilled; a scratch reload is a vector-memory operation whose wait also waits for the fills)
-    // Branch-free: four dword loads per thread from addresses chosen by selects -- a branch per table would end in a join where the
-    // compiler waits for the loads, in front of the fills that have to be requested next
-    auto load_tables = [&](int n, int r0, int rows) -> f32x4 {
-        int tq = tid;
-        asm volatile("" : "+v"(tq));
-        const bool lo = tq < 256;
-        const int j = lo ? tq : tq - 256;
-        const int img0 = r0 / a.S, nimg = (min(r0 + rows, a.R) - 1) / a.S - img0;            // images beyond the first
-        const float* w2r = a.w2 + (long long)(n * 256 + j) * 4;
-        const float* cm = a.cimg + (long long)img0 * a.NH + n * 256 + j;
-        const float* p0 = lo ? a.ct + n * 256 + j : cm;
-        const float* p1 = lo ? w2r + 0 : cm + (nimg >= 1 ? a.NH : 0);
-        const float* p2 = lo ? w2r + 1 : cm + (nimg >= 2 ? 2 * a.NH : 0);
-        const float* p3 = lo ? w2r + 2 : a.b2 + n * 3 + min(j, 2);
-        f32x4 v;
-        v[0] = *p0; v[1] = *p1; v[2] = *p2; v[3] = *p3;
-        return v;
-    };
-    auto store_tables = [&](const f32x4& v) {
-        int tq = tid;
-        asm volatile("" : "+v"(tq));
-        if (tq < 256) *reinterpret_cast<f32x4*>(Eb + tq * 4) = v;
-        else {
-            const int j = tq - 256;
-            if (CB) { Cb[j] = v[0]; Cb[CB_LD + j] = v[1]; Cb[2 * CB_LD + j] = v[2]; }
-            if (j < 3) Cb[B2_AT + j] = v[3];
-        }
-    };
-
-    int n, r0, rows, nans = 0;
-    tile_of(b, n, r0, rows);
-    {
-        const f32x4 tv = load_tables(n, r0, rows);
-        set_poff(r0, rows);
-        fill(0, 0, n);
-        fill(1, 1, n);
-        store_tables(tv);
-    }
-    VPHO_STAMP_AT(1);
-    const int sw = (li >> SW_SHIFT) & (CPR - 1);
-    bool first = true;
-
-    // one tile: TI = 4 (128 rows: wave = row group rg x hidden half hh) or TI = 1 (32 rows: wave = hidden slice)
-    auto tile = [&](auto ti_tag) -> bool {
-        constexpr int TI = decltype(ti_tag)::value;
-        const int rg = TI == 4 ? (wave & 3) : 0, hh = TI == 4 ? (wave >> 2) : wave;
-        f32x16 acc[TI];
-#pragma unroll
-        for (int i = 0; i < TI; ++i)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][e] = 0.f;
-        // ---- stage 0 of this tile (and, behind the barrier, its tables) has landed?  Younger than it: stage 1 (NF) and, from the
-        // second tile on, the previous tile's output store (1)
-        if (first) VPHO_WAIT_VMH(NF); else VPHO_WAIT_VMH(NF + 1);
-        VPHO_BARRIER_LDS_ONLY();                                    // (not __syncthreads(): its fence would wait for the previous tile's store)
-        if (first) VPHO_STAMP_AT(2);
-        VPHO_PRIO_MAIN();
-        for (int kt = 0; kt < NK; ++kt) {
-            const int buf = kt & 1;
-            const float* As = smem + buf * STAGE + (hh * 32 * TI + li) * HB_K;
-            const float* Bs = smem + buf * STAGE + 256 * HB_K + (rg * 32 + li) * HB_K;
-            f32x4 bq, av[TI];
-            auto frags = [&](int kk) {
-                const int ch = ((2 * kk + lh) ^ sw) * 4;
-                bq = *reinterpret_cast<const f32x4*>(Bs + ch);
-#pragma unroll
-                for (int i = 0; i < TI; ++i) av[i] = *reinterpret_cast<const f32x4*>(As + i * 32 * HB_K + ch);
-            };
-            auto mfmas = [&]() {
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-#pragma unroll
-                    for (int i = 0; i < TI; ++i)
-                        acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i][q], bq[q], acc[i], 0, 0, 0);
-            };
-#pragma unroll
-            for (int kk = 0; kk < NKK - 1; ++kk) { frags(kk); mfmas(); }
-            frags(NKK - 1);
-            if (kt + 1 < NK) {
-                VPHO_SYNC_LDS_DMA();                                // every wave has its fragments of stage `buf`; stage kt + 1 has landed
-                if (kt + 2 < NK) fill(buf, kt + 2, n);
-            }
-            mfmas();
-        }
-        __syncthreads();                                            // both stage buffers are free
-        VPHO_PRIO_REST();
-        if (first) VPHO_STAMP_AT(3);
-        // ---- next tile: tables into registers, then its first two stages, BEFORE this tile's epilogue
-        const int en = n, er0 = r0, erows = rows;
-        b += G;
-        const bool more = b < total;
-        f32x4 tvn = {0.f, 0.f, 0.f, 0.f};
-        if (more) {
-            tile_of(b, n, r0, rows);
-            tvn = load_tables(n, r0, rows);
-            set_poff(r0, rows);
-            fill(0, 0, n);
-            fill(1, 1, n);
-        }
-        // ---- epilogue: hidden unit j = 32*TI*hh + 32*i + (e&3) + 8*(e>>2) + 4*lh on the register, hypothesis on the lane; a row's 256 hidden
-        // units are summed as EIGHT partial sums of 32 in ascending order, whatever the tile kind (see head_tile)
-        const int lrow_out = rg * 32 + li, row = er0 + lrow_out;
-        const bool live = row < a.R;
-        // (the lane's first hidden unit as an OPAQUE per-tile value: left visible, the compiler hoists the 64 loop-invariant LDS addresses
-        // of this epilogue out of the tile loop and spills them: 45 registers of scratch)
-        int j0 = 32 * TI * hh + 4 * lh;
-        asm volatile("" : "+v"(j0));
-        const float* cim = a.cimg + (long long)(live ? row / a.S : 0) * a.NH + en * 256 + j0;
-        const float* cbl = Cb + (live ? row / a.S - er0 / a.S : 0) * CB_LD + j0;
-        const float* ebl = Eb + j0 * 4;
-#pragma unroll
-        for (int i = 0; i < TI; ++i) {
-            float o0 = 0.f, o1 = 0.f, o2 = 0.f;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int j = 32 * i + (e & 3) + 8 * (e >> 2);      // + j0
-                const f32x4 t = *reinterpret_cast<const f32x4*>(ebl + j * 4);
-                float h = acc[i][e] + (CB ? cbl[j] : cim[j]) + t[0];
-                h = h > 0.f ? h : 0.f;
-                o0 += h * t[1]; o1 += h * t[2]; o2 += h * t[3];
-            }
-            o0 += __shfl_xor(o0, 32); o1 += __shfl_xor(o1, 32); o2 += __shfl_xor(o2, 32);
-            if (lh == 0) {
-                float* ob = Ob + ((hh * TI + i) * 128 + lrow_out) * 4;
-                ob[0] = o0; ob[1] = o1; ob[2] = o2;
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        if (first) VPHO_STAMP_AT(5);
-        VPHO_BARRIER_LDS_ONLY();                                    // partial sums complete; Eb / Cb are no longer read (no fence: the next tile's fills are in flight)
-        int tq = tid;
-        asm volatile("" : "+v"(tq));
-        const float b2v = tq < 3 * erows ? Cb[B2_AT + tq % 3] : 0.f;
-        VPHO_BARRIER_LDS_ONLY();                                    // ... b2 of THIS tile read before the tables of the next one overwrite it
-        if (more) store_tables(tvn);
-        // ---- one output per thread: thread t -> (row t / 3, component t % 3); every thread issues the store (out of range when idle)
-        {
-            const int rl = tq / 3, dd = tq - 3 * rl, orow = er0 + rl;
-            int off = -1;
-            float sv = 0.f;
-            if (rl < erows && orow < a.R) {
-                float acc2 = Ob[rl * 4 + dd];
-#pragma unroll
-                for (int part = 1; part < 8; ++part) acc2 += Ob[(part * 128 + rl) * 4 + dd];
-                sv = (acc2 + b2v) / inv_std;
-                if (a.rhs_mode) {
-                    // score_eval_wrapper's nan_to_num (score_based_model.py:65-72), entry by entry; see head_tile
-                    if (sv != sv) { sv = 0.f; ++nans; } else if (fabsf(sv) == INFINITY) sv = 0.f;
-                    sv = 0.f - coef * sv;
-                }
-                off = (int)(((long long)orow * a.D + en * 3 + dd) * 4);
-            }
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, sv), orr, off, 0, 0);
-        }
-        if (first) VPHO_STAMP_AT(4);
-        first = false;
-        return more;
-    };
-    while (true) {
-        const bool more = rows == 128 ? tile(std::integral_constant<int, 4>{}) : tile(std::integral_constant<int, 1>{});
-        if (!more) break;
-    }
-    if (nans) atomicAdd(a.nan_count, nans);
-    VPHO_STAMP_WRITE(head, blockIdx.x);
-}
 
 // --------------------------------------------------------------------------------------------- score head, split-bf16 products (opt-in)
 // VPHO_SCORE_MFMA=bf16x6 | bf16x9 (not the default; the fp32-MFMA kernel above is the product path and the one every parity claim is
@@ -1609,44 +1203,35 @@ int eval_net(Ctx& c, const float* X, float t, int rhs_mode, float coef, float* o
         pa.ctl = cc.mode ? c.ws.ctl : nullptr; pa.ctl_mode = cc.mode; pa.write_ynew = cc.write_ynew; pa.kbase = c.ws.K; pa.n_el = c.n_el;
         pa.ybuf0 = c.ws.y; pa.ybuf1 = c.ws.ynew;
         const int K1 = (pa.Dp + 31) / 32 * 32;
-        const char* pe_env = getenv("VPHO_PE_RING");                            // round 3's LDS-ring kernel (A/B measurements, read per call)
-        const bool pe_ring = pe_env && atoi(pe_env);
         const dim3 pe_grid((unsigned)((c.R + PE_ROWS - 1) / PE_ROWS));
         vpho::ProfScope pe_prof(vpho::PROF_POSE_ENC, c.s, 2.0 * (double)c.R * 256.0 * (K1 + 256.0), 0.0);
-        if (pe_ring) {
-            const size_t pe_lds = (size_t)(PE_NST * PE_STAGE + PE_ROWS * PE_H_LD + 512 + PE_ROWS * (K1 + 4)) * sizeof(float);
-            VPHO_DYN_LDS(pose_encoder_kernel, 150 * 1024);
-            VPHO_REQUIRE(pe_lds <= 150 * 1024, "pose encoder: input dimension %d too large for the LDS tile", pa.Dp);
-            hipLaunchKernelGGL(pose_encoder_kernel, pe_grid, dim3(512), pe_lds, c.s, pa);
-        } else {
-            const size_t pe_lds = (size_t)(PE_ROWS * PE_H_LD + 512) * sizeof(float);            // 35 328 B
-            VPHO_REQUIRE(K1 <= 128 && (pa.Dp & 3) == 0, "pose encoder: input dimension %d (padded %d) not supported (<= 128, multiple of 4)", c.w->D, pa.Dp);
-            // 64-row workgroups above 8 192 rows, i.e. as soon as 32-row workgroups would be more than one per CU (measured, isolated launches, hand /
-            // object network: 12 800 rows 35.4 / 33.1 -> 30.4 / 27.9 us, 16 384 rows 35.8 / 32.6 -> 30.7 / 26.8, 32 768 rows -- BASELINE cfg4 -- 67.7 / 58.7 ->
-            // 57.8 / 47.8; at the README config's 6 400 rows the 32-row kernel wins, 18.7 against 28.9: 200 workgroups against 100 on 256 CUs).
-            // VPHO_PE_ROWS=32 / 64 forces either (A/B aid, read per call; the two are bit-identical)
-            const char* rows_env = getenv("VPHO_PE_ROWS");
-            const bool rows64 = rows_env ? atoi(rows_env) == 64 : c.R > 8192;
-            if (rows64) {
-                const size_t lds64 = (size_t)(2 * PE_ROWS * PE_H_LD + 512) * sizeof(float);          // 68 608 B
-                const dim3 grid64((unsigned)((c.R + 2 * PE_ROWS - 1) / (2 * PE_ROWS)));
-                VPHO_DYN_LDS(pose_encoder_reg64_kernel<1>, lds64); VPHO_DYN_LDS(pose_encoder_reg64_kernel<2>, lds64);
-                VPHO_DYN_LDS(pose_encoder_reg64_kernel<3>, lds64); VPHO_DYN_LDS(pose_encoder_reg64_kernel<4>, lds64);
-                switch (K1 / 32) {
-                    case 1: hipLaunchKernelGGL(pose_encoder_reg64_kernel<1>, grid64, dim3(512), lds64, c.s, pa); break;
-                    case 2: hipLaunchKernelGGL(pose_encoder_reg64_kernel<2>, grid64, dim3(512), lds64, c.s, pa); break;
-                    case 3: hipLaunchKernelGGL(pose_encoder_reg64_kernel<3>, grid64, dim3(512), lds64, c.s, pa); break;
-                    default: hipLaunchKernelGGL(pose_encoder_reg64_kernel<4>, grid64, dim3(512), lds64, c.s, pa); break;
-                }
-            } else
+        const size_t pe_lds = (size_t)(PE_ROWS * PE_H_LD + 512) * sizeof(float);            // 35 328 B
+        VPHO_REQUIRE(K1 <= 128 && (pa.Dp & 3) == 0, "pose encoder: input dimension %d (padded %d) not supported (<= 128, multiple of 4)", c.w->D, pa.Dp);
+        // 64-row workgroups above 8 192 rows, i.e. as soon as 32-row workgroups would be more than one per CU (measured, isolated launches, hand /
+        // object network: 12 800 rows 35.4 / 33.1 -> 30.4 / 27.9 us, 16 384 rows 35.8 / 32.6 -> 30.7 / 26.8, 32 768 rows -- BASELINE cfg4 -- 67.7 / 58.7 ->
+        // 57.8 / 47.8; at the README config's 6 400 rows the 32-row kernel wins, 18.7 against 28.9: 200 workgroups against 100 on 256 CUs).
+        // VPHO_PE_ROWS=32 / 64 forces either (A/B aid, read per call; the two are bit-identical)
+        const char* rows_env = getenv("VPHO_PE_ROWS");
+        const bool rows64 = rows_env ? atoi(rows_env) == 64 : c.R > 8192;
+        if (rows64) {
+            const size_t lds64 = (size_t)(2 * PE_ROWS * PE_H_LD + 512) * sizeof(float);          // 68 608 B
+            const dim3 grid64((unsigned)((c.R + 2 * PE_ROWS - 1) / (2 * PE_ROWS)));
+            VPHO_DYN_LDS(pose_encoder_reg64_kernel<1>, lds64); VPHO_DYN_LDS(pose_encoder_reg64_kernel<2>, lds64);
+            VPHO_DYN_LDS(pose_encoder_reg64_kernel<3>, lds64); VPHO_DYN_LDS(pose_encoder_reg64_kernel<4>, lds64);
             switch (K1 / 32) {
-                case 1: hipLaunchKernelGGL(pose_encoder_reg_kernel<1>, pe_grid, dim3(512), pe_lds, c.s, pa); break;
-                case 2: hipLaunchKernelGGL(pose_encoder_reg_kernel<2>, pe_grid, dim3(512), pe_lds, c.s, pa); break;
-                case 3: hipLaunchKernelGGL(pose_encoder_reg_kernel<3>, pe_grid, dim3(512), pe_lds, c.s, pa); break;
-                default: hipLaunchKernelGGL(pose_encoder_reg_kernel<4>, pe_grid, dim3(512), pe_lds, c.s, pa); break;
+                case 1: hipLaunchKernelGGL(pose_encoder_reg64_kernel<1>, grid64, dim3(512), lds64, c.s, pa); break;
+                case 2: hipLaunchKernelGGL(pose_encoder_reg64_kernel<2>, grid64, dim3(512), lds64, c.s, pa); break;
+                case 3: hipLaunchKernelGGL(pose_encoder_reg64_kernel<3>, grid64, dim3(512), lds64, c.s, pa); break;
+                default: hipLaunchKernelGGL(pose_encoder_reg64_kernel<4>, grid64, dim3(512), lds64, c.s, pa); break;
             }
+        } else
+        switch (K1 / 32) {
+            case 1: hipLaunchKernelGGL(pose_encoder_reg_kernel<1>, pe_grid, dim3(512), pe_lds, c.s, pa); break;
+            case 2: hipLaunchKernelGGL(pose_encoder_reg_kernel<2>, pe_grid, dim3(512), pe_lds, c.s, pa); break;
+            case 3: hipLaunchKernelGGL(pose_encoder_reg_kernel<3>, pe_grid, dim3(512), pe_lds, c.s, pa); break;
+            default: hipLaunchKernelGGL(pose_encoder_reg_kernel<4>, pe_grid, dim3(512), pe_lds, c.s, pa); break;
         }
-        if (int e = vpho::check_launch("pose_encoder_kernel")) return e;
+        if (int e = vpho::check_launch(rows64 ? "pose_encoder_reg64_kernel" : "pose_encoder_reg_kernel")) return e;
     }
     VPHO_REQUIRE((double)c.R * 256.0 * 4.0 < 4.0e9, "score head: %lld hypothesis rows exceed the 32-bit buffer offsets", (long long)c.R);
     HeadArgs a;
@@ -1656,7 +1241,6 @@ int eval_net(Ctx& c, const float* X, float t, int rhs_mode, float coef, float* o
     a.ctl = cc.mode ? c.ws.ctl : nullptr; a.ctl_mode = cc.mode; a.stage = cc.stage; a.out_slot = cc.out_slot; a.kbase = c.ws.K; a.n_el = c.n_el;
     // [2] stages | [256][4] epilogue table | per-image terms (3 x 257 of 1024 floats)
     size_t lds = (size_t)(2 * (256 + 128) * HB_K + 256 * 4 + 2 * 128 * 4) * sizeof(float);
-    if (getenv("VPHO_HEAD_LDS")) lds = (size_t)atoi(getenv("VPHO_HEAD_LDS"));   // tuning aid: force 1 block/CU
     VPHO_DYN_LDS(score_head_kernel<true>, lds);
     VPHO_DYN_LDS(score_head_kernel<false>, lds);
     VPHO_DYN_LDS(score_head_epi0_kernel<true>, lds);
@@ -1664,15 +1248,8 @@ int eval_net(Ctx& c, const float* X, float t, int rhs_mode, float coef, float* o
     // Tile plan: 128-row tiles; when the last round of the launch would be less than half full, the rows beyond the last full round
     // become 32-row tail tiles (see head_tile).  VPHO_HEAD_TAIL=0: ordinary tiles only.
     static const int tail_on = getenv("VPHO_HEAD_TAIL") ? atoi(getenv("VPHO_HEAD_TAIL")) : 1;
-    static int slots_of[64] = {0};                          // per device: one process may drive several GPUs of different sizes
-    int dev = 0;
-    VPHO_HIP(hipGetDevice(&dev));
-    int& slots = slots_of[dev & 63];
-    if (!slots) {
-        hipDeviceProp_t prop;
-        VPHO_HIP(hipGetDeviceProperties(&prop, dev));
-        slots = 2 * prop.multiProcessorCount;               // two 57 KB workgroups per CU
-    }
+    int slots = 0;                                          // two 57 KB workgroups per CU
+    if (vpho::workgroup_slots(&slots)) return 1;
     const int tiles = (int)((c.R + 127) / 128), nheads = c.w->nheads;
     a.nheads = nheads; a.full_tiles = tiles; a.tail_tiles = 0;
     const long long total = (long long)tiles * nheads;
@@ -1697,20 +1274,7 @@ int eval_net(Ctx& c, const float* X, float t, int rhs_mode, float coef, float* o
         const char* cb_s = getenv("VPHO_HEAD_CB");
         const int cb_env = cb_s ? atoi(cb_s) : 1;
         const dim3 grid((unsigned)(nheads * (a.full_tiles + a.tail_tiles)));
-        // persistent kernel, OPT-IN (VPHO_HEAD_PERS=1; same bits): min(tiles, workgroup slots) workgroups walk the tiles.  Measured round 5
-        // (profiles/r05_head_persistent_ab.txt): stand-alone 230-238 us against 232-234 for one workgroup per tile, the pipelined step
-        // 29.9-30.1 ms against 29.5-29.6 -- with two workgroups per CU the other workgroup's matrix work already covers a tile's prologue,
-        // and workgroups that hold their CU slot for the whole launch keep the other streams' kernels out.  Not the default.
-        const char* pp = getenv("VPHO_HEAD_PERS");
-        const int pers = pp ? atoi(pp) : 0;
         const bool cb = c.S >= 64 && cb_env;
-        if (pers && cb && (double)c.R * c.w->D * 4.0 < 3.9e9 && (double)c.w->nheads * 256 * 256 * 4.0 < 3.9e9) {
-            const size_t plds = (size_t)(2 * (256 + 128) * HB_K + 256 * 4 + 1024 + 8 * 128 * 4) * sizeof(float);     // 72 KB: two workgroups per CU
-            VPHO_DYN_LDS(score_head_pers_kernel<true>, plds);
-            const dim3 pgrid((unsigned)std::min<long long>((long long)grid.x, (long long)slots));
-            hipLaunchKernelGGL(score_head_pers_kernel<true>, pgrid, dim3(512), plds, c.s, a);       // sample_num >= 64 (the LDS copy of the per-image terms); smaller: the one-tile kernel
-            return vpho::check_launch("score_head_pers_kernel");
-        }
         // VPHO_HEAD_EPI=0: the reference epilogue (read per call; same bits)
         const char* epi_s = getenv("VPHO_HEAD_EPI");
         if (epi_s && atoi(epi_s) == 0) {

@@ -398,10 +398,6 @@ def winograd_ok(H, W, cin, cout, x_ld):
 _TRAIN_WINOGRAD = os.environ.get('VPHO_TRAIN_WINOGRAD', '1') != '0'
 
 
-def _wino8():
-    return os.environ.get('VPHO_WINO8', '0') not in ('0', '')      # the 8-wave experiment kernel has no BatchNorm epilogue (read per call, like the library)
-
-
 def _winograd_bn(x, u, bias, out_slope, cin, cout, bn, gate_slope=1.0):
     """full-map Winograd convolution with the BatchNorm reductions in its epilogue (vpho_conv3x3_winograd_stats_nhwc_f32)"""
     N, H, W, x_ld = x.shape
@@ -428,7 +424,7 @@ def conv3x3_train(x, w, bias=None, out_slope=1.0, rows=None, bn=None):
     if not _TRAIN_WINOGRAD or not winograd_ok(H, W, cin, cout, x_ld) or w.shape[1] != 9 * cin:
         return conv2d_nhwc(x, w, bias, kh=3, kw=3, pad=1, out_slope=out_slope, bn=bn)
     u = winograd_weights_device(w)
-    if bn is not None and FUSE_BN and rows is None and not _wino8():
+    if bn is not None and FUSE_BN and rows is None:
         return _winograd_bn(x, u, bias, out_slope, cin, cout, bn)
     if rows is not None:
         assert rows.shape == (N, H, W)
@@ -458,7 +454,7 @@ def conv3x3_dgrad_winograd(dy, w, gate=None, rows=None, bn=None):
     if gate is None:
         return conv3x3_winograd(dy, u, None, 1.0)
     g, slope = gate
-    if bn is not None and bn.x is not None and FUSE_BN and not _wino8():
+    if bn is not None and bn.x is not None and FUSE_BN:
         return _winograd_bn(dy, u, None, 1.0, cout, cin, bn, gate_slope=slope)
     assert g.shape == (N, H, W, cin) and g.is_contiguous()
     out = torch.empty((N, H, W, cin), device=dy.device, dtype=torch.float32)
