@@ -94,9 +94,11 @@ def test_product_library_carries_no_ablation_or_stamp_code():
     macros = ('CONV_ABLATE', 'WINO_ABLATE', 'FK_ABLATE', 'VPHO_CLOCK_STAMPS')
     assert not [f for f in B.FLAGS if any(m in f for m in macros)], B.FLAGS
     src = open(os.path.join(ROOT, 'vpho_amd', 'csrc', 'conv_igemm.hip')).read()
-    # the run-time VPHO_CONV_DBG keeps only its two bit-identical A/B orders
-    assert re.search(r'g\.dbg\s*=\s*dbg_env \? \(atoi\(dbg_env\) & \(8 \| 16\)\)', src), 'VPHO_CONV_DBG must be masked to its bit-identical bits'
-    assert not re.search(r'g\.dbg & (1|2|4)\b', src)
+    plan = open(os.path.join(ROOT, 'vpho_amd', 'csrc', 'conv_plan.h')).read()
+    # the run-time VPHO_CONV_DBG keeps only its two bit-identical A/B orders: Geo::dbg has ONE writer, the plan, and it masks
+    assert re.search(r'g\.dbg\s*=\s*sw\.dbg & \(8 \| 16\);', plan), 'VPHO_CONV_DBG must be masked to its bit-identical bits'
+    assert len(re.findall(r'\bdbg\s*=[^=]', plan + src)) == 1 and 'env_int("VPHO_CONV_DBG", 0)' in plan
+    assert not re.search(r'g\.dbg & (1|2|4)\b', src + plan)
 
 
 def test_library_reads_the_kept_ab_switches_and_none_of_the_retired_ones():

@@ -133,6 +133,7 @@ def _rows_match_tiles(part, y2, bm):
 
 
 # (N, H, W, cin, cout, k, bm): the direct kernel's 128x128 / 128x64 / 64x64 tile classes (VPHO_CONV_PERS=0), ragged M and channel tails
+# (pinned without a device by tests/_conv_plan_cases.py: a_bn_stats_direct_*, and a_bn_stats_persistent_* for the test after this one)
 DIRECT = [(61, 33, 33, 64, 256, 1, 128), (64, 16, 16, 128, 128, 3, 128), (63, 16, 17, 128, 128, 3, 128), (16, 16, 16, 256, 64, 1, 64),
           (2, 9, 7, 32, 40, 1, 64), (3, 8, 8, 36, 132, 1, 64), (2, 10, 6, 16, 64, 3, 64), (3, 12, 12, 64, 128, 3, 64)]
 

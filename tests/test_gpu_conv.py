@@ -62,7 +62,8 @@ def test_conv_epilogue_residual_lrelu_and_prologue_affine():
 def test_residual_requested_before_the_last_k_stage(N, H, Cin, Cout):
     """round 4: the residual tile of a 1x1 expansion (conv3 of every bottleneck, backbone_FPN_HFL.py:311-350) is loaded in front of the last
     k stage instead of after it.  K = 32 (one stage: requested before the only stage), 64, 96 ... 512 in all three tile classes, ragged
-    pixel counts and Cout tails; against torch, and bit-identical to the round-3 order of the same kernel (VPHO_CONV_DBG=8)."""
+    pixel counts and Cout tails; against torch, and bit-identical to the round-3 order of the same kernel (VPHO_CONV_DBG=8).  Which
+    class each shape reaches: tests/_conv_plan_cases.py, a_residual_*."""
     import os
     from vpho_amd import ops
     from vpho_amd.model.pack import pack_conv
@@ -83,7 +84,8 @@ def test_residual_requested_before_the_last_k_stage(N, H, Cin, Cout):
 @pytest.mark.parametrize('N,H,Cin,Cout', [(16, 32, 256, 256), (9, 31, 128, 64), (3, 17, 512, 128), (2, 8, 544, 64)])
 def test_prologue_affine_on_the_direct_to_lds_kernel(N, H, Cin, Cout):
     """Pre-activation BN + LeakyReLU applied to the fragments as they are read from LDS (1x1, Cin % 32 == 0, Cin <= 512) in all
-    three tile classes incl. ragged pixel counts; Cin = 544 exceeds the table and takes the register-staged kernel."""
+    three tile classes incl. ragged pixel counts; Cin = 544 exceeds the table and takes the register-staged kernel.  Pinned by
+    tests/_conv_plan_cases.py, a_prologue_*."""
     from vpho_amd import ops
     from vpho_amd.model.pack import pack_conv
     x, w, b = _rand((N, Cin, H, H), 40), _rand((Cout, Cin, 1, 1), 41, (2.0 / Cin) ** 0.5), _rand((Cout,), 42)
@@ -418,3 +420,48 @@ def test_grouped_winograd_is_bit_identical_to_one_launch_per_group(N, H, W, Cin,
         one = ops.conv3x3(xi, w[i].contiguous(), b[i].contiguous(), out_slope=0.01)
         assert torch.equal(got[i * N:(i + 1) * N], one), (i, float((got[i * N:(i + 1) * N] - one).abs().max()))
 
+
+
+def test_launches_reach_the_kernel_class_the_plan_table_names():
+    """tests/_conv_plan_cases.py pins, on the CPU, which kernel class a shape reaches (tests/test_conv_plan_cpu.py); this runs the GPU_CASES
+    of that table -- one shape per class, some 1 GFLOP each (the weight gradient's 128-row tiles start at 2 and 8 by their own rule) -- and
+    watches the profiling counters: the class the table names counts one launch, every other class none."""
+    from vpho_amd import ops
+    from vpho_amd.model.pack import winograd_weights
+    from tests._conv_plan_cases import CASES, GPU_CASES
+    classes = ['conv_igemm_128x128', 'conv_igemm_128x64', 'conv_igemm_64x64', 'conv_winograd', 'conv_wgrad_64x64', 'conv_wgrad_128x128']
+    g = torch.Generator().manual_seed(7)
+    seen = set()
+    try:
+        for c in classes:
+            ops.prof_enable(c)
+            ops.prof_collect(c)
+        for case in GPU_CASES:
+            line, plan = CASES[case]
+            f = {k: int(v) for k, v in (t.split('=') for t in line.split()[1:])}
+            kind = line.split()[0]
+            if kind == 'conv':
+                assert set(f) <= {'N', 'H', 'Cin', 'Cout', 'bias'}, 'a plain 1x1 convolution with a bias'
+                want = dict(t.split('=', 1) for t in plan.split())['prof']
+                x = torch.randn(f['N'], f['H'], f['H'], f['Cin'], generator=g).cuda()
+                w = (torch.randn(f['Cout'], f['Cin'], generator=g) * f['Cin'] ** -0.5).cuda()
+                y = ops.conv2d_nhwc(x, w, torch.randn(f['Cout'], generator=g).cuda())
+            elif kind == 'wino':
+                want = 'conv_winograd'
+                x = torch.randn(f['N'], f['H'], f['H'], f['Cin'], generator=g).cuda()
+                w = (torch.randn(f['Cout'], 9 * f['Cin'], generator=g) * (9 * f['Cin']) ** -0.5).cuda()
+                y = ops.conv3x3_winograd(x, winograd_weights(w), torch.randn(f['Cout'], generator=g).cuda())
+            else:
+                want = dict(t.split('=', 1) for t in plan.split())['prof']
+                k = f['K']
+                x = torch.randn(f['N'], f['OH'], f['OH'], f['Cin'], generator=g).cuda()
+                dy = torch.randn(f['N'], f['OH'], f['OH'], f['Cout'], generator=g).cuda()
+                y = ops.conv2d_wgrad_nhwc(x, dy, k, k, 1, k // 2, k // 2)
+            assert torch.isfinite(y).all()
+            counts = {c: ops.prof_collect(c)['launches'] for c in classes}
+            assert counts == {c: int(c == want) for c in classes}, (case, want, counts)
+            seen.add(want)
+    finally:
+        for c in classes:
+            ops.prof_enable(c, False)
+    assert seen == set(classes)

@@ -11,9 +11,7 @@
 //
 // Roofline: fp32 MFMA, 2*M*N*K flop per launch against 157.3 TFLOP/s.
 #include "common.h"
-#include "../../include/vpho_hip.h"
-#include <cstdlib>
-#include <algorithm>
+#include "conv_plan.h"                         // Geo, BK, SBK, GLDS_PRE_MAX; which kernel a launch reaches: plan_conv
 
 VPHO_STAMP_DECL(conv)
 
@@ -22,23 +20,7 @@ namespace {
 #ifndef CONV_ABLATE
 #define CONV_ABLATE 0                          // timing experiments only (scripts/kernel_ablate.sh conv_igemm CONV_ABLATE 1 2 4; direct-to-LDS kernel: 32 a quarter of the fragment reads, 64 no stage fills after the second, 128 no stage barrier, 256 no epilogue): 1 no global loads, 2 no in-loop
 #endif                                         // barriers, 4 no LDS stores in conv_igemm_kernel -- wrong results, never in the product build
-constexpr int BK = 32;
 constexpr int LDS_LD = BK + 4;
-constexpr int GLDS_PRE_MAX = 512;     // most input channels of a pre-activation 1x1 convolution on the direct-to-LDS kernel
-
-struct Geo {
-    vpho_conv_desc d;
-    int M, K, tiles_m, tiles_n, ntiles;
-    int w_ld;                       // floats between consecutive weight rows (K unless the launch reduces a K-slice)
-    long long x_zs, w_zs, y_zs;     // per blockIdx.y advance of x / w / y (split reductions, groups; 0 for ordinary launches)
-    long long b_zs, r_zs, x2_zs, pre_zs, ru_zs;   // ... and of bias / res / x2 / in_scale + in_shift / res_up (groups only)
-    int y_linear, r_linear, vec_epilogue;
-    int uni;   // Cin % 32 == 0: wave-uniform taps (direct-to-LDS kernel)
-    int dbg;   // A/B switches whose results are bit-identical (VPHO_CONV_DBG, read per call): 8 = residual tile requested in the epilogue
-               // (round 3) instead of in front of the last k stage, 16 = second stage requested after the first has landed (round 3).
-               // The timing ablations that produce WRONG results (skip global loads / barriers / LDS stores) are compile-time only:
-               // -DCONV_ABLATE=<mask> in a diagnostic build (scripts/kernel_ablate.sh), never in the product library
-};
 
 // blockIdx.y = slice of a split reduction or group of a grouped launch: the same problem on advanced operands
 __device__ __forceinline__ void advance_group(vpho_conv_desc& d, const Geo& g, const unsigned by) {
@@ -1105,7 +1087,6 @@ __global__ __launch_bounds__(64 * WM * WN, 4) void conv_igemm_pers_bn_kernel(con
 // kt+1 are read and split in the shadow of the MFMAs of stage kt.  Shapes: Cin % 16 == 0 (every stage inside one filter tap), no
 // prologue affine; everything else takes the fp32 kernels.
 typedef __bf16 cbf16x8 __attribute__((ext_vector_type(8)));
-constexpr int SBK = 16;
 
 __device__ __forceinline__ void conv_split3(const f32x4& x0, const f32x4& x1, cbf16x8& h, cbf16x8& m, cbf16x8& l) {
 #pragma unroll
@@ -1331,206 +1312,35 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_igemm_split_kernel(const Ge
     }
 }
 
+// (family, tile) -> kernel: plan_conv's two keys.  A pair the plan never produces has no kernel.
+using ConvKernel = void (*)(const Geo);
+const ConvKernel conv_kernels[CONV_NFAMILY][CONV_NTILE] = {
+    //                  TILE_128                                       TILE_128x64                                   TILE_64                                     TILE_128_W4
+    /* CONV_REG      */ {conv_igemm_kernel<128, 128, 4, 2, 1>,         conv_igemm_kernel<128, 64, 4, 2, 1>,          conv_igemm_kernel<64, 64, 2, 2, 1>,         conv_igemm_kernel<128, 128, 2, 2, 1>},
+    /* CONV_GLDS     */ {conv_igemm_glds_kernel<128, 128, 4, 2>,       conv_igemm_glds_kernel<128, 64, 4, 2>,        conv_igemm_glds_kernel<64, 64, 2, 2>,       nullptr},
+    /* CONV_GLDS_PRE */ {conv_igemm_glds_kernel<128, 128, 4, 2, true>, conv_igemm_glds_kernel<128, 64, 4, 2, true>,  conv_igemm_glds_kernel<64, 64, 2, 2, true>, nullptr},
+    /* CONV_SPLIT6   */ {conv_igemm_split_kernel<128, 128, 4, 2, 6>,   conv_igemm_split_kernel<128, 64, 4, 2, 6>,    conv_igemm_split_kernel<64, 64, 2, 2, 6>,   nullptr},
+    /* CONV_SPLIT9   */ {conv_igemm_split_kernel<128, 128, 4, 2, 9>,   conv_igemm_split_kernel<128, 64, 4, 2, 9>,    conv_igemm_split_kernel<64, 64, 2, 2, 9>,   nullptr},
+    /* CONV_PERS     */ {conv_igemm_pers_kernel<128, 128, 4, 2>,       nullptr,                                      nullptr,                                    nullptr},
+    /* CONV_PERS_BN  */ {conv_igemm_pers_bn_kernel<128, 128, 4, 2>,    nullptr,                                      nullptr,                                    nullptr},
+};
+static_assert(PLAN_PROF_CONV128 == vpho::PROF_CONV128 && PLAN_PROF_CONV64 == vpho::PROF_CONV64 && PLAN_PROF_CONV128x64 == vpho::PROF_CONV128x64,
+              "conv_plan.h numbers the profiling classes as common.h does");
+
 }  // namespace
 
 extern "C" int vpho_conv2d_nhwc_f32(const vpho_conv_desc* dp, void* stream) {
-    VPHO_REQUIRE(dp != nullptr, "vpho_conv2d_nhwc_f32: null descriptor");
-    const vpho_conv_desc& d = *dp;
-    VPHO_REQUIRE(d.x && d.w && d.y, "vpho_conv2d_nhwc_f32: null tensor");
-    VPHO_REQUIRE(d.N > 0 && d.H > 0 && d.W > 0 && d.Cin > 0 && d.Cout > 0 && d.KH > 0 && d.KW > 0 && d.stride > 0,
-                 "vpho_conv2d_nhwc_f32: non-positive dimension");
-    VPHO_REQUIRE(d.Cin % 4 == 0 && d.x_ld % 4 == 0 && d.x_ld >= d.Cin, "vpho_conv2d_nhwc_f32: Cin=%d x_ld=%d must be multiples of 4, x_ld>=Cin", d.Cin, d.x_ld);
-    VPHO_REQUIRE(((uintptr_t)d.x & 15) == 0 && ((uintptr_t)d.w & 15) == 0, "vpho_conv2d_nhwc_f32: x/w must be 16-byte aligned");
-    VPHO_REQUIRE((d.in_scale == nullptr) == (d.in_shift == nullptr), "vpho_conv2d_nhwc_f32: in_scale/in_shift must come together");
-    VPHO_REQUIRE(d.in_scale == nullptr || (((uintptr_t)d.in_scale & 15) == 0 && ((uintptr_t)d.in_shift & 15) == 0), "vpho_conv2d_nhwc_f32: in_scale/in_shift alignment");
-    VPHO_REQUIRE(d.OH > 0 && d.OW > 0, "vpho_conv2d_nhwc_f32: empty output");
-    // the last tap of the last output pixel may not start beyond the padded input by more than the pad
-    VPHO_REQUIRE((d.OH - 1) * d.stride - d.pad_y < d.H && (d.OW - 1) * d.stride - d.pad_x < d.W, "vpho_conv2d_nhwc_f32: output larger than input allows");
-    long long M = (long long)d.N * d.OH * d.OW;
-    VPHO_REQUIRE(M < (1ll << 31), "vpho_conv2d_nhwc_f32: too many output pixels");
+    int slots = -1;
+    if (vpho::workgroup_slots(&slots)) slots = -1;               // its error is returned only where the plan comes to need the slots
     Geo g;
-    g.d = d;
-    g.M = (int)M;
-    g.K = d.KH * d.KW * d.Cin + (d.x2 ? d.Cin2 : 0);
-    const int splits = d.splits > 1 ? d.splits : 1;
-    g.w_ld = d.w_ld > 0 ? d.w_ld : g.K;
-    g.x_zs = splits > 1 ? d.x_split : 0; g.w_zs = splits > 1 ? d.w_split : 0; g.y_zs = splits > 1 ? d.y_split : 0;
-    g.b_zs = g.r_zs = g.x2_zs = g.pre_zs = g.ru_zs = 0;
-    // grouped launch (ABI 11): blockIdx.y = group; the twin hand / object branches of the feature path (same shapes, different weights,
-    // backbone_FPN_HFL.py:79-109) as ONE launch -- twice the tiles, half the launches, every output's k order unchanged
-    const int groups = d.groups > 1 ? d.groups : 1;
-    if (groups > 1) {
-        VPHO_REQUIRE(splits == 1 && !d.row_map && !d.gate && !d.w_planes, "vpho_conv2d_nhwc_f32: grouped launches take no splits / pixel list / gate / bf16 planes");
-        VPHO_REQUIRE(d.x_group >= 0 && d.w_group > 0 && d.y_group > 0 && d.x_group % 4 == 0 && d.w_group % 4 == 0 && d.y_group % 4 == 0 && d.bias_group % 4 == 0 &&
-                     d.res_group % 4 == 0 && d.x2_group % 4 == 0 && d.pre_group % 4 == 0 && d.ru_group % 4 == 0,
-                     "vpho_conv2d_nhwc_f32: group strides must be non-negative multiples of 4 floats (x_group may be 0: a shared input)");
-        g.x_zs = d.x_group; g.w_zs = d.w_group; g.y_zs = d.y_group; g.b_zs = d.bias_group; g.r_zs = d.res_group; g.x2_zs = d.x2_group;
-        g.pre_zs = d.pre_group; g.ru_zs = d.ru_group;
-    }
-    const int ny = splits * groups;                               // grid.y (at most one of the two is > 1)
-    VPHO_REQUIRE(g.w_ld >= g.K && g.w_ld % 4 == 0 && g.x_zs % 4 == 0 && g.w_zs % 4 == 0, "vpho_conv2d_nhwc_f32: w_ld / split strides must be multiples of 4, w_ld >= K");
-    VPHO_REQUIRE(splits == 1 || (!d.res && !d.bias && !d.in_scale && !d.gate), "vpho_conv2d_nhwc_f32: split launches produce plain partial sums (no bias / residual / prologue / gate)");
-    g.y_linear = (d.y_sy == d.y_sx * d.OW && d.y_sn == d.y_sy * d.OH) ? 1 : 0;
-    g.r_linear = (d.res == nullptr) || (d.r_sy == d.r_sx * d.OW && d.r_sn == d.r_sy * d.OH) ? 1 : 0;
-    VPHO_REQUIRE((d.row_map == nullptr) == (d.row_count == nullptr), "vpho_conv2d_nhwc_f32: row_map / row_count must come together");
-    if (d.row_map) {
-        VPHO_REQUIRE(splits == 1 && !d.gate, "vpho_conv2d_nhwc_f32: pixel-list launches take no splits / gate");
-        if (!d.rows_scatter) g.y_linear = g.r_linear = 1;   // compact output: row r of y (and res) is the r-th listed pixel
-    }
-    // 16-byte epilogue when every output pixel's channel run (and the residual's) is 16-byte addressable
-    auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-    g.vec_epilogue = (d.Cout % 4 == 0 && al16(d.y) && d.y_sx % 4 == 0 && d.y_sy % 4 == 0 && d.y_sn % 4 == 0 &&
-                      (!d.bias || al16(d.bias)) &&
-                      (!d.gate || al16(d.gate)) &&
-                      (!d.res || (al16(d.res) && d.r_sx % 4 == 0 && d.r_sy % 4 == 0 && d.r_sn % 4 == 0))) ? 1 : 0;
-    // (round 5: the direct-to-LDS kernel's own ablations on the one-round layers, scripts/conv_oneround.py, 3.36 ms per step over nine shapes: stage
-    // fills 6 %, stage barrier 1.5 %, epilogue 8.6 %, matrix instructions + launch shape the rest; 4-byte stores straight from the accumulators
-    // instead of this 16-byte epilogue: +2.5 %)
-    const char* dbg_env = getenv("VPHO_CONV_DBG");
-    g.dbg = dbg_env ? (atoi(dbg_env) & (8 | 16)) : 0;          // only the bit-identical A/B orders exist at run time
-    if (d.x2) {
-        // second input concatenated along the channels (projection shortcut merged into conv3): direct-to-LDS kernels, wave-uniform taps
-        VPHO_REQUIRE(d.KH == 1 && d.KW == 1 && d.pad_y == 0 && d.pad_x == 0 && d.Cin % BK == 0 && d.Cin2 > 0 && d.Cin2 % BK == 0 && d.x2_ld % 4 == 0 &&
-                     d.x2_ld >= d.Cin2 && d.stride2 > 0 && al16(d.x2) && !d.row_map && !d.in_scale && splits == 1 && !d.w_planes,
-                     "vpho_conv2d_nhwc_f32: x2 needs a 1x1 unpadded convolution, Cin and Cin2 multiples of 32, no pixel list / prologue / splits / planes");
-        VPHO_REQUIRE((d.OH - 1) * d.stride2 < d.H2 && (d.OW - 1) * d.stride2 < d.W2 && 4.0 * d.N * d.H2 * d.W2 * (double)d.x2_ld < 3.9e9,
-                     "vpho_conv2d_nhwc_f32: x2 of %d x %d pixels read at stride %d does not cover the %d x %d output (or exceeds 3.9 GB)", d.H2, d.W2, d.stride2, d.OH, d.OW);
-    }
-    if (d.res_up) {
-        // up-sampled residual (the FPN's top-down add): served by the direct-to-LDS kernels' 16-byte epilogue only
-        VPHO_REQUIRE(!d.res && !d.gate && splits == 1 && d.ru_H > 0 && d.ru_W > 0 && d.ru_ld >= d.Cout && d.ru_ld % 4 == 0 && al16(d.res_up),
-                     "vpho_conv2d_nhwc_f32: res_up needs no res / gate / splits, a (N, ru_H, ru_W, ru_ld >= Cout) map with ru_ld %% 4 == 0, 16-byte aligned");
-        VPHO_REQUIRE(g.vec_epilogue && d.in_scale == nullptr && !d.w_planes && (!d.row_map || d.rows_scatter),
-                     "vpho_conv2d_nhwc_f32: res_up needs 16-byte addressable output rows, no prologue affine, no split-bf16 planes, scattered pixel lists");
-        VPHO_REQUIRE(4.0 * d.N * d.ru_H * d.ru_W * (double)d.ru_ld < 3.9e9, "vpho_conv2d_nhwc_f32: res_up map too large");
-    }
+    ConvPlan p;
+    const int refused = plan_conv(dp, slots, read_conv_switches(), &g, &p);
+    if (p.stats_rows >= 0) *dp->stats_rows = p.stats_rows;
+    if (refused) return p.need_slots ? 1 : vpho::fail("%s", p.error);
     hipStream_t s = (hipStream_t)stream;
-    // BatchNorm reductions in the epilogue (ABI 13): the direct-to-LDS kernels' 16-byte epilogue, one partial row per M-tile
-    if (d.stats_rows) *d.stats_rows = 0;
-    const bool stats_shape = g.vec_epilogue && splits == 1 && groups == 1 && !d.row_map && !d.w_planes && (d.in_scale == nullptr);
-    if (d.bn_x) {
-        VPHO_REQUIRE(d.stats && d.stats_rows && d.bn_mean && d.bn_invstd && (d.gate || (d.bn_gamma && d.bn_beta)),
-                     "vpho_conv2d_nhwc_f32: bn_x needs stats, stats_rows, mean / invstd and -- without a stored gate -- gamma / beta");
-        VPHO_REQUIRE((stats_shape || d.gate) && al16(d.bn_x) && al16(d.bn_mean) && al16(d.bn_invstd) && (!d.bn_gamma || (al16(d.bn_gamma) && al16(d.bn_beta))),
-                     "vpho_conv2d_nhwc_f32: bn_x without a stored gate is served by the direct-to-LDS 16-byte epilogue only (Cout %% 4 == 0, aligned, no splits / groups / pixel list / prologue / planes)");
-    }
-    VPHO_REQUIRE(!d.stats || (d.stats_rows && d.stats_cap > 0 && al16(d.stats)), "vpho_conv2d_nhwc_f32: stats needs stats_rows (host) and stats_cap");
-    const long long big_tiles = ((M + 127) / 128) * ((d.Cout + 127) / 128) * ny;
-    const double m_acc = (d.row_map && d.rows_hint > 0) ? (double)d.rows_hint : (double)M;   // rows the launch really computes
-    const double flops = 2.0 * m_acc * d.Cout * g.K * ny;
-    // algorithmic HBM bytes: input, packed weights and output once each (+ residual, + bias)
-    const double bytes = groups * 4.0 * ((double)d.N * d.H * d.W * d.Cin + (d.x2 ? (double)d.N * d.OH * d.OW * d.Cin2 : 0.0) + (double)d.Cout * g.K + m_acc * d.Cout * (d.res ? 2 : 1) + d.Cout + (d.res_up ? (double)d.N * d.ru_H * d.ru_W * d.Cout : 0.0));
-    static const int force_tile = getenv("VPHO_CONV_TILE") ? atoi(getenv("VPHO_CONV_TILE")) : 0;   // tuning aid
-    // tile choice (measured on MI355X, scripts/conv_tune.py): 8-wave 128x128 when it still gives >= 2 tiles per CU,
-    // 8-wave 128x64 when that gives >= 1 tile per CU, else the 4-wave 64x64 tile (small feature maps, narrow heads)
-    const long long tiles_12864 = ((M + 127) / 128) * ((d.Cout + 63) / 64) * ny;
-    int variant = 64;
-    if (big_tiles >= 256 && d.Cout % 128 == 0) variant = 1288;
-    else if (tiles_12864 >= 256 && d.Cout >= 48) variant = 12864;
-    if (force_tile) variant = force_tile;
-    bool stats_kernel = false, stats_failed = false;               // stats_kernel: the switch below launches conv_igemm_glds_kernel
-    auto launch = [&](auto kernel, int bm, int bn, int threads, int cls) {
-        vpho::ProfScope prof(cls, s, flops, bytes);
-        g.tiles_m = (int)((M + bm - 1) / bm); g.tiles_n = (d.Cout + bn - 1) / bn;
-        g.ntiles = g.tiles_m * g.tiles_n;
-        if (d.stats) {
-            const bool on = stats_kernel && stats_shape && g.tiles_m <= d.stats_cap;
-            if (on) {
-                *d.stats_rows = g.tiles_m;
-                if (d.bn_x && d.bn_gamma) g.d.gate = nullptr;       // the gate recomputed from bn_x; the stored one was the fall-back
-            } else {
-                // no BatchNorm epilogue: the stored gate as is, no partial rows (the caller runs the stand-alone reduction); without a
-                // stored gate to fall back to the call fails -- never drop the gate silently
-                g.d.stats = nullptr;
-                if (d.bn_x) { if (!d.gate) { stats_failed = true; return; } g.d.bn_x = nullptr; }
-            }
-        }
-        hipLaunchKernelGGL(kernel, dim3((g.ntiles + 7) / 8 * 8, ny), dim3(threads), 0, s, g);
-    };
-    static const int no_glds = getenv("VPHO_CONV_NO_GLDS") ? atoi(getenv("VPHO_CONV_NO_GLDS")) : 0;   // tuning aid
-    // the direct-to-LDS kernels address x and w by 32-bit byte offsets: both extents (all splits included) must stay below 4 GB
-    // (the largest activation of the reference's configurations is 0.27 GB)
-    const double x_extent = 4.0 * (((double)d.N * d.H * d.W - 1) * d.x_ld + d.Cin + (double)(ny - 1) * (double)g.x_zs);
-    const double w_extent = 4.0 * (((double)d.Cout - 1) * g.w_ld + g.K + (double)(ny - 1) * (double)g.w_zs);
-    VPHO_REQUIRE(x_extent < 3.9e9 && w_extent < 3.9e9 && g.x_zs >= 0 && g.w_zs >= 0,
-                 "vpho_conv2d_nhwc_f32: input (%.2f GB) and weights (%.2f GB) must each stay below 3.9 GB", x_extent * 1e-9, w_extent * 1e-9);
-    static const int no_uni = getenv("VPHO_CONV_NO_UNI") ? atoi(getenv("VPHO_CONV_NO_UNI")) : 0;          // tuning aid
-    g.uni = (d.Cin % BK == 0 && d.pad_y >= 0 && d.pad_x >= 0 && !no_uni) ? 1 : 0;
-    // a pre-activation prologue rides on the direct-to-LDS kernel when the fragment's k is a plain channel index (1x1, unpadded,
-    // Cin a multiple of 32 and within the LDS table); everything else with a prologue takes the register-staged kernel
-    const bool pre_on_read = d.in_scale != nullptr && g.uni && d.KH == 1 && d.KW == 1 && d.pad_y == 0 && d.pad_x == 0 && d.Cin <= GLDS_PRE_MAX;
-    const bool glds = (d.in_scale == nullptr || pre_on_read) && (!no_glds || d.res_up != nullptr || d.x2 != nullptr || d.bn_x != nullptr);
-    stats_kernel = glds && variant != 128;
-    VPHO_REQUIRE(!d.x2 || (g.uni && variant != 128), "vpho_conv2d_nhwc_f32: x2 is served by the direct-to-LDS kernels with wave-uniform taps only");
-    VPHO_REQUIRE(!d.res_up || variant != 128, "vpho_conv2d_nhwc_f32: res_up is not served by the forced register-staged tile");
-    // opt-in split-bf16 products (never the default): shapes the split kernel takes, everything else stays on the fp32 kernels
-    const bool split_ok = d.w_planes != nullptr && (d.plane_terms == 6 || d.plane_terms == 9) && d.in_scale == nullptr && splits == 1 && !d.gate &&
-                          d.Cin % SBK == 0 && g.vec_epilogue && d.pad_y >= 0 && d.pad_x >= 0 && g.w_ld == g.K &&
-                          ((uintptr_t)d.w_planes & 15) == 0 && 6.0 * d.Cout * g.K < 3.9e9;
-    if (split_ok) {
-        const bool x9 = d.plane_terms == 9;
-        switch (variant) {
-            case 128: case 1288:
-                if (x9) launch(conv_igemm_split_kernel<128, 128, 4, 2, 9>, 128, 128, 512, vpho::PROF_CONV128);
-                else    launch(conv_igemm_split_kernel<128, 128, 4, 2, 6>, 128, 128, 512, vpho::PROF_CONV128);
-                break;
-            case 12864:
-                if (x9) launch(conv_igemm_split_kernel<128, 64, 4, 2, 9>, 128, 64, 512, vpho::PROF_CONV128x64);
-                else    launch(conv_igemm_split_kernel<128, 64, 4, 2, 6>, 128, 64, 512, vpho::PROF_CONV128x64);
-                break;
-            default:
-                if (x9) launch(conv_igemm_split_kernel<64, 64, 2, 2, 9>, 64, 64, 256, vpho::PROF_CONV64);
-                else    launch(conv_igemm_split_kernel<64, 64, 2, 2, 6>, 64, 64, 256, vpho::PROF_CONV64);
-                break;
-        }
-        return vpho::check_launch("conv_igemm_split_kernel");
-    }
-    // persistent multi-tile kernel (round 5): 1x1 launches of the 128x128 class with more tiles than workgroup slots (two 80-KB workgroups
-    // per CU).  VPHO_CONV_PERS: 0 = never (round 4's kernel, A/B aid -- same bits), 1 = default, 2 = also launches of at most one round
     {
-        const char* pe = getenv("VPHO_CONV_PERS");
-        const int pers = pe ? atoi(pe) : 1;
-        int slots = 0;
-        if (vpho::workgroup_slots(&slots)) return 1;
-        const double y_extent = 4.0 * ((double)(d.N - 1) * d.y_sn + (double)(d.OH - 1) * d.y_sy + (double)(d.OW - 1) * d.y_sx + d.Cout);
-        const double r_extent = d.res ? 4.0 * ((double)(d.N - 1) * d.r_sn + (double)(d.OH - 1) * d.r_sy + (double)(d.OW - 1) * d.r_sx + d.Cout) : 0.0;
-        const bool simple = d.KH == 1 && d.KW == 1 && d.pad_y == 0 && d.pad_x == 0;
-        const bool ok = pers && variant == 1288 && glds && !pre_on_read && d.in_scale == nullptr && g.uni && simple && g.vec_epilogue && !d.row_map && !d.res_up &&
-                        !d.gate && !d.bn_x && splits == 1 && y_extent < 3.9e9 && r_extent < 3.9e9 && d.y_sn >= 0 && d.y_sy >= 0 && d.y_sx >= 0 &&
-                        (!d.x2 || 4.0 * d.N * d.H2 * d.W2 * (double)d.x2_ld < 3.9e9);
-        if (ok && (big_tiles > slots || pers >= 2)) {
-            vpho::ProfScope prof(vpho::PROF_CONV128, s, flops, bytes);
-            g.tiles_m = (int)((M + 127) / 128); g.tiles_n = (d.Cout + 127) / 128;
-            g.ntiles = g.tiles_m * g.tiles_n;
-            if (d.stats) {
-                if (stats_shape && g.tiles_m <= d.stats_cap) *d.stats_rows = g.tiles_m; else g.d.stats = nullptr;
-            }
-            const int grid = (int)std::min<long long>((g.ntiles + 7) / 8 * 8, std::max(8, slots / groups / 8 * 8));      // the groups share the slots
-            if (g.d.stats) hipLaunchKernelGGL((conv_igemm_pers_bn_kernel<128, 128, 4, 2>), dim3(grid, groups), dim3(512), 0, s, g);
-            else hipLaunchKernelGGL((conv_igemm_pers_kernel<128, 128, 4, 2>), dim3(grid, groups), dim3(512), 0, s, g);
-            return vpho::check_launch("conv_igemm_pers_kernel");
-        }
+        vpho::ProfScope prof(p.prof_class, s, p.flops, p.bytes);
+        hipLaunchKernelGGL(conv_kernels[p.family][p.tile], dim3(p.grid_x, p.grid_y), dim3(p.threads), 0, s, g);
     }
-    switch (variant) {
-        case 128:  launch(conv_igemm_kernel<128, 128, 2, 2, 1>, 128, 128, 256, vpho::PROF_CONV128); break;
-        case 1288:
-            if (glds && pre_on_read) launch(conv_igemm_glds_kernel<128, 128, 4, 2, true>, 128, 128, 512, vpho::PROF_CONV128);
-            else if (glds) launch(conv_igemm_glds_kernel<128, 128, 4, 2>, 128, 128, 512, vpho::PROF_CONV128);
-            else      launch(conv_igemm_kernel<128, 128, 4, 2, 1>, 128, 128, 512, vpho::PROF_CONV128);
-            break;
-        case 12864:
-            if (glds && pre_on_read) launch(conv_igemm_glds_kernel<128, 64, 4, 2, true>, 128, 64, 512, vpho::PROF_CONV128x64);
-            else if (glds) launch(conv_igemm_glds_kernel<128, 64, 4, 2>, 128, 64, 512, vpho::PROF_CONV128x64);
-            else      launch(conv_igemm_kernel<128, 64, 4, 2, 1>, 128, 64, 512, vpho::PROF_CONV128x64);
-            break;
-        default:
-            if (glds && pre_on_read) launch(conv_igemm_glds_kernel<64, 64, 2, 2, true>, 64, 64, 256, vpho::PROF_CONV64);
-            else if (glds) launch(conv_igemm_glds_kernel<64, 64, 2, 2>, 64, 64, 256, vpho::PROF_CONV64);
-            else      launch(conv_igemm_kernel<64, 64, 2, 2, 1>, 64, 64, 256, vpho::PROF_CONV64);
-            break;
-    }
-    if (stats_failed)
-        return vpho::fail("vpho_conv2d_nhwc_f32: bn_x: the launch needs %d partial rows (stats_cap %d) or runs a kernel without the BatchNorm epilogue (tile %d)",
-                          g.tiles_m, d.stats_cap, variant);
-    return vpho::check_launch("conv_igemm_kernel");
+    return vpho::check_launch(p.name);
 }

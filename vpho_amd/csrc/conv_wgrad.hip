@@ -12,14 +12,10 @@
 // narrow inputs (the 4-channel stem: 16 taps per 64-column tile) take the same path.  Slices are summed in a fixed order by a
 // second kernel.  No im2col / transposed copies are materialised.
 #include "common.h"
-#include "../../include/vpho_hip.h"
-#include <algorithm>
-#include <cstdint>
-#include <cstdlib>
+#include "conv_plan.h"                         // BK; tile, slices and the slice sum's order: plan_wgrad
 
 namespace {
 
-constexpr int BK = 32;
 #ifndef WGRAD_RING
 #define WGRAD_RING 2                           // LDS stages of the 64 x 64 tile (A/B builds: 3)
 #endif
@@ -241,11 +237,6 @@ __global__ __launch_bounds__(256) void wgrad_reduce_grouped_kernel(const float* 
     for (int k = 1; k < G; ++k) s += red[k][q];
     reinterpret_cast<f32x4*>(out)[i] = s;
 }
-// threads per quad: 1 (the plain kernel) while it already fills the chip or the slices are few
-inline int wgrad_reduce_groups(int splits, long long n4) {
-    if (splits < 8 || n4 >= 256ll * 1024) return 1;
-    return splits >= 32 && n4 < 64ll * 1024 ? 16 : 4;
-}
 
 // ordered list of the live groups of BK consecutive pixels of an (N, H, W) map: group g is live when one of its pixels lies in the
 // window (y0, x0, w, h) of its image (vpho_roi_windows_i32's table).  One workgroup: every thread counts its run of consecutive
@@ -278,60 +269,11 @@ __global__ __launch_bounds__(1024) void window_groups_kernel(const int* __restri
     if (threadIdx.x == 1023) *count = s_cnt[1023];
 }
 
-struct WgPlan { int bm, bn, tiles_m, tiles_n, splits, m_chunk; };
-
-WgPlan plan_wgrad(long long M, int Cin, int Cout, int taps) {
-    WgPlan p;
-    const int K = Cin * taps;
-    static const int tile_env = getenv("VPHO_WGRAD_TILE") ? atoi(getenv("VPHO_WGRAD_TILE")) : 0;          // tuning aid
-    // 128x128 tiles pay off only for the largest products (measured: 3x3 256->256 on 64x64x64 pixels 100 vs 87 TF/s); everywhere else
-    // the 64x64 tile wins or ties (3x3 128->128: 79 vs 53 TF/s) -- more tiles, hence fewer, longer pixel slices and less partial-sum traffic
-    // (round 5, re-swept per shape with the grouped slice sum, scripts/wgrad_layers.py under VPHO_WGRAD_TILE=64 / 128: the 128 x 128 tile now
-    // wins or ties from M K Cout ~ 4e9 on -- 1x1 1024 -> 256 on 16 x 16 maps 101 -> 92 us, 3x3 128 -> 128 on 32 x 32 217 -> 206 -- and loses below
-    // (3x3 128 -> 128 on 16 x 16: 74 against 88): 19.6 -> 18.7 ms of weight gradients per training step)
-    static const double big_min = getenv("VPHO_WGRAD_BIG_MIN") ? atof(getenv("VPHO_WGRAD_BIG_MIN")) : 4e9;      // tuning aid (round 4's rule: 5e10)
-    const bool big = tile_env ? tile_env == 128 : (K >= 128 && Cout >= 128 && (double)M * K * Cout >= big_min);
-    p.bm = p.bn = big ? 128 : 64;
-    // Three tiles (re-swept per shape, round 5, scripts/wgrad_layers.py under VPHO_WGRAD_TILE = 64 / 128 / 12864: 19.6 / 20.8 / 18.5 ms of weight
-    // gradients per training step, this rule 18.4, the best tile per shape 18.3): 128 output channels x 64 columns of the (tap, ci) axis --
-    // 0.047 bytes of LDS fill per flop against 0.0625 for 64 x 64, three workgroups per CU -- wherever Cout >= 128 and the product is not tiny
-    // (it also serves K = 64: 64 -> 256 on 64 x 64 maps 93 -> 88 us; 3x3 256 -> 256 on 16 x 16 202 -> 190); 128 x 128 for the 1x1 layers with
-    // K a multiple of 128 from M K Cout = 4e9 on (1024 -> 256 on 16 x 16: 101 -> 92) and for the largest products; 64 x 64 for the rest.
-    if (!tile_env) {
-        const double prod = (double)M * K * Cout;
-        const bool big128 = K >= 128 && Cout >= 128 && ((taps == 1 && K % 128 == 0 && prod >= big_min) || prod >= 5e10);
-        if (big128) p.bm = p.bn = 128;
-        else if (Cout >= 128 && K >= 64 && prod >= 1e9) { p.bm = 128; p.bn = 64; }
-        else p.bm = p.bn = 64;
-    } else if (tile_env == 12864 && Cout >= 128) { p.bm = 128; p.bn = 64; }
-    p.tiles_m = (Cout + p.bm - 1) / p.bm;
-    p.tiles_n = (K + p.bn - 1) / p.bn;
-    const long long tiles = (long long)p.tiles_m * p.tiles_n;
-    // Workgroups for 256 CUs (2 x 128x128 or 4 x 64x64 tiles fit a CU's LDS): about two rounds of them, but no slices shorter than
-    // 16 stages of 32 pixels (8 on the smallest maps, where nothing else fills the chip) -- a slice pays its prologue, its 16 KB
-    // (64 KB) of partial sums and their reduction whatever its length.  Swept over the training step's 47 shapes
-    // (scripts/r04_wgrad_want.sh, r04_wgrad_stages.sh): the 3x3 layers want ~2 000 workgroups, the 1x1 layers on 32 x 32 maps ~500
-    // (8 tiles x 64 slices of 1 024 pixels); a fixed target of 1 536 with 8-stage slices cost 1.5 ms per step more.
-    static const int want_env = getenv("VPHO_WGRAD_WANT") ? atoi(getenv("VPHO_WGRAD_WANT")) : 0;      // tuning aid
-    static const int stages_env = getenv("VPHO_WGRAD_STAGES") ? atoi(getenv("VPHO_WGRAD_STAGES")) : 0;
-    const long long want = want_env > 0 ? (big ? want_env : 2 * want_env) : (big ? 1024 : 2048);
-    const long long min_stages = stages_env > 0 ? stages_env : (M < 8192 ? 8 : 16);
-    long long splits = std::max<long long>(1, (want + tiles - 1) / tiles);
-    splits = std::min<long long>(splits, std::max<long long>(1, M / (min_stages * BK)));
-    splits = std::min<long long>(splits, 256);
-    if (splits >= 8) splits = std::max<long long>(8, (splits + 4) / 8 * 8);          // slices go to the 8 XCDs round-robin (see the kernel)
-    long long chunk = (M + splits - 1) / splits;
-    chunk = (chunk + BK - 1) / BK * BK;
-    p.m_chunk = (int)chunk;
-    p.splits = (int)((M + chunk - 1) / chunk);
-    return p;
-}
-
 }  // namespace
 
 extern "C" long long vpho_conv2d_wgrad_workspace_bytes(int N, int OH, int OW, int Cin, int Cout, int KH, int KW) {
     if (N <= 0 || OH <= 0 || OW <= 0 || Cin <= 0 || Cout <= 0 || KH <= 0 || KW <= 0) return -1;
-    const WgPlan p = plan_wgrad((long long)N * OH * OW, Cin, Cout, KH * KW);
+    const WgPlan p = plan_wgrad((long long)N * OH * OW, Cin, Cout, KH * KW, read_wgrad_switches());
     return p.splits > 1 ? (long long)p.splits * Cout * KH * KW * Cin * 4 : 0;
 }
 
@@ -369,7 +311,8 @@ static int wgrad_launch(const float* x, int N, int H, int W, int Cin, int x_ld, 
     VPHO_REQUIRE(M < (1ll << 31) && (long long)N * H * W < (1ll << 31), "vpho_conv2d_wgrad_nhwc_f32: too many pixels");
     VPHO_REQUIRE((double)N * H * W * x_ld * 4.0 < 4.0e9 && (double)M * dy_ld * 4.0 < 4.0e9, "vpho_conv2d_wgrad_nhwc_f32: x and dy must each stay below 4 GB (32-bit buffer offsets)");
     const int taps = KH * KW;
-    const WgPlan p = plan_wgrad(M, Cin, Cout, taps);
+    static_assert(PLAN_PROF_WGRAD64 == vpho::PROF_WGRAD64 && PLAN_PROF_WGRAD128 == vpho::PROF_WGRAD128, "conv_plan.h numbers the profiling classes as common.h does");
+    const WgPlan p = plan_wgrad(M, Cin, Cout, taps, read_wgrad_switches());
     VPHO_REQUIRE(p.splits == 1 || (workspace && ((uintptr_t)workspace & 15) == 0), "vpho_conv2d_wgrad_nhwc_f32: %d pixel slices need the workspace", p.splits);
     WgArgs a;
     a.x = x; a.dy = dy; a.out = p.splits > 1 ? (float*)workspace : dw;
@@ -378,23 +321,18 @@ static int wgrad_launch(const float* x, int N, int H, int W, int Cin, int x_ld, 
     a.M = (int)M; a.K = taps * Cin; a.tiles_n = p.tiles_n; a.ntiles = p.tiles_m * p.tiles_n; a.m_chunk = p.m_chunk;
     a.glist = glist; a.gcount = gcount; a.splits = p.splits;
     hipStream_t s = (hipStream_t)stream;
-    // see the kernel: XCD = blockIdx.x & 7
-    const dim3 grid(p.splits >= 8 ? 8u * (unsigned)a.ntiles * (unsigned)((p.splits + 7) / 8) : (unsigned)((a.ntiles + 7) / 8 * 8) * (unsigned)p.splits);
     // dW[Cout][taps * Cin] = dY^T (M x Cout) . im2col(x) (M x taps * Cin): 2 M Cout K flop; operands read once + dW written once
     // (a launch on a pixel-group list reduces only over the live groups -- device data --: it is timed with its full-size count and
     // reported as an upper bound by its own class id would mislead, so group launches are left out of the classes)
-    vpho::ProfScope prof(glist ? -1 : (p.bm == 128 ? vpho::PROF_WGRAD128 : vpho::PROF_WGRAD64), s, 2.0 * (double)M * Cout * (double)a.K,
+    vpho::ProfScope prof(glist ? -1 : p.prof_class, s, 2.0 * (double)M * Cout * (double)a.K,
                          4.0 * ((double)N * H * W * Cin + (double)M * Cout + (double)Cout * a.K));
-    if (p.bm == 128 && p.bn == 64) hipLaunchKernelGGL((conv_wgrad_tn_kernel<128, 64, 4, 2>), grid, dim3(512), 0, s, a);
-    else if (p.bm == 128) hipLaunchKernelGGL((conv_wgrad_tn_kernel<128, 128, 4, 2>), grid, dim3(512), 0, s, a);
-    else hipLaunchKernelGGL((conv_wgrad_tn_kernel<64, 64, 2, 2>), grid, dim3(256), 0, s, a);
-    if (p.splits > 1) {
+    const auto kernel = p.bn == 128 ? conv_wgrad_tn_kernel<128, 128, 4, 2> : p.bm == 128 ? conv_wgrad_tn_kernel<128, 64, 4, 2> : conv_wgrad_tn_kernel<64, 64, 2, 2>;
+    hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(p.threads), 0, s, a);
+    if (p.reduce_groups) {
         const long long n4 = (long long)Cout * a.K / 4;
-        static const int g_env = getenv("VPHO_WGRAD_REDUCE_GROUPS") ? atoi(getenv("VPHO_WGRAD_REDUCE_GROUPS")) : 0;      // tuning aid: 1 / 4 / 16
-        const int G = g_env == 1 || g_env == 4 || g_env == 16 ? g_env : wgrad_reduce_groups(p.splits, n4);
-        if (G == 16) hipLaunchKernelGGL(wgrad_reduce_grouped_kernel<16>, dim3((unsigned)((n4 + 15) / 16)), dim3(256), 0, s, (const float*)workspace, p.splits, n4, dw);
-        else if (G == 4) hipLaunchKernelGGL(wgrad_reduce_grouped_kernel<4>, dim3((unsigned)((n4 + 63) / 64)), dim3(256), 0, s, (const float*)workspace, p.splits, n4, dw);
-        else hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, (const float*)workspace, p.splits, n4, dw);
+        const int per = 256 / p.reduce_groups;                            // 16-byte columns per workgroup
+        const auto reduce = p.reduce_groups == 16 ? wgrad_reduce_grouped_kernel<16> : p.reduce_groups == 4 ? wgrad_reduce_grouped_kernel<4> : wgrad_reduce_kernel;
+        hipLaunchKernelGGL(reduce, dim3((unsigned)((n4 + per - 1) / per)), dim3(256), 0, s, (const float*)workspace, p.splits, n4, dw);
     }
     return vpho::check_launch("conv_wgrad_tn_kernel");
 }

@@ -14,9 +14,7 @@
 // double buffered (128 KB).
 #include "common.h"
 #include <type_traits>
-#include "../../include/vpho_hip.h"
-#include <cstdlib>
-#include <algorithm>
+#include "conv_plan.h"                         // WK, W_TB, W_CB, W_STAGE, W_IN_PIXELS; staged or not, blocks, kernel: plan_wino
 
 VPHO_STAMP_DECL(wino)
 
@@ -25,20 +23,6 @@ namespace {
 #ifndef WINO_ABLATE
 #define WINO_ABLATE 0                          // timing experiments only (scripts/wino_ablate.sh; 512: no output stores; 32 staged kernel: no input DMA): 1 no patch loads, 2 no U fill, 4 no transform /
 #endif                                         // V stores, 8 no stage barrier, 16 no fragment reads -- wrong results, never in the product build
-constexpr int WK = 8;                          // input channels per stage
-constexpr int W_TB = 64, W_CB = 64;            // tiles / output channels per workgroup
-constexpr int W_STAGE = 2 * 16 * 64 * WK;      // floats per stage: V | U
-constexpr int W_IN_PIXELS = 480;               // STAGED kernel: pixels (64 bytes each) of the input region IN behind the two stages: 128 + 30 KB of the 160
-// STAGED geometry: a 64-tile block = whole tile rows (TW | 64) of one image (NR = 64 / TW <= TH, TH % NR == 0) or all rows of NR / TH
-// images (TH | NR), and the region's pixels fit IN
-inline bool wino_staged_ok(int TH, int TW, int W) {
-    if (TW < 4 || TW > 32 || (W_TB % TW) != 0) return false;
-    const int NR = W_TB / TW;
-    if (NR <= TH ? (TH % NR) != 0 : (NR % TH) != 0) return false;
-    const int rpp = NR < TH ? NR : TH, ipb = NR / rpp;
-    return ipb * (2 * rpp + 2) * (W + 2) <= W_IN_PIXELS;
-}
-
 struct WinoArgs {
     const float* x; const float* u; const float* bias; float* y;
     int N, H, W, Cin, x_ld, Cout, y_ld;
@@ -648,6 +632,13 @@ extern "C" int vpho_winograd_weights_multi_f32(const void* segments, int n_segme
     return vpho::check_launch("wino_weights_multi_kernel");
 }
 
+// (epilogue, mode) -> kernel: plan_wino's two keys; the BatchNorm kernels run on full maps only
+static void (*const wino_kernels[3][3])(const WinoArgs) = {
+    /* WINO_PLAIN  */ {conv_winograd_kernel<0>, conv_winograd_kernel<1>, conv_winograd_kernel<2>},
+    /* WINO_BN_FWD */ {conv_winograd_bn_kernel<0>, conv_winograd_bn_kernel<1>, nullptr},
+    /* WINO_BN_BWD */ {conv_winograd_bnb_kernel<0>, conv_winograd_bnb_kernel<1>, nullptr},
+};
+
 static int wino_launch(const float* x, const float* u, const float* bias, int N, int H, int W, int Cin, int x_ld, int Cout, float out_slope,
                        const int* wins, const int* tile_base, int tiles_hint, float* y, int y_ld, void* stream,
                        const float* gate, float gate_slope, int scatter, int groups, long long x_group, const WinoBn* bn) {
@@ -665,57 +656,36 @@ static int wino_launch(const float* x, const float* u, const float* bias, int N,
     a.x_gs = groups > 1 ? x_group : 0; a.u_gs = groups > 1 ? 16ll * Cout * Cin : 0; a.b_gs = groups > 1 ? Cout : 0;
     a.y_gs = groups > 1 ? (long long)N * H * W * y_ld : 0;
     a.stats = nullptr; a.bn_x = a.bn_mean = a.bn_invstd = a.bn_gamma = a.bn_beta = nullptr;
+    const WinoPlan p = plan_wino(N, H, W, Cout, wins != nullptr, bn != nullptr, bn && bn->x, read_wino_staged());
     const size_t lds = (size_t)2 * W_STAGE * sizeof(float);
     const size_t lds_staged = lds + (size_t)W_IN_PIXELS * 64;
     VPHO_DYN_LDS(conv_winograd_kernel<0>, lds);
     VPHO_DYN_LDS(conv_winograd_kernel<1>, lds_staged);
     VPHO_DYN_LDS(conv_winograd_kernel<2>, lds_staged);
-    const int tbs = (a.T + W_TB - 1) / W_TB;
     // executed flops: 16 GEMMs of T x Cout x Cin (the direct 3x3 would be 2.25 x this)
     // (with windows: the live tiles when the caller knows them -- tiles_hint, profiling passes only --, else all)
     const double tl = (wins && tiles_hint > 0) ? (double)tiles_hint : (double)a.T;
     vpho::ProfScope prof(vpho::PROF_WINOGRAD, (hipStream_t)stream, groups * 2.0 * 16.0 * tl * Cout * (double)Cin,
                          groups * 4.0 * (4.0 * tl * Cin + 16.0 * Cout * Cin + 4.0 * tl * Cout));
-    const int ncb = Cout / W_CB;
-    unsigned blocks = (unsigned)(tbs * ncb);
-    if (ncb <= 8 && (8 % ncb) == 0) { const int G = 8 / ncb; blocks = (unsigned)((tbs + G - 1) / G) * 8u; }
-    // input patches through LDS where the blocks are whole tile rows of full maps (see the kernel); VPHO_WINO_STAGED=0: registers (A/B aid,
-    // bit-identity test; read per call)
-    const char* st = getenv("VPHO_WINO_STAGED");
-    const bool staged = st ? atoi(st) != 0 : true;
     if (bn) {
         // training: BatchNorm reductions in the epilogue, one partial row per tile block (full maps only)
         VPHO_REQUIRE(bn->stats && bn->rows && !wins && !gate && groups == 1 && ((uintptr_t)bn->stats & 15) == 0,
                      "vpho_conv3x3_winograd_stats_nhwc_f32: full maps, one group, no stored gate");
-        VPHO_REQUIRE(tbs <= bn->cap, "vpho_conv3x3_winograd_stats_nhwc_f32: %d partial rows exceed stats_cap %d", tbs, bn->cap);
+        VPHO_REQUIRE(p.tbs <= bn->cap, "vpho_conv3x3_winograd_stats_nhwc_f32: %d partial rows exceed stats_cap %d", p.tbs, bn->cap);
         VPHO_REQUIRE(!bn->x || (bn->mean && bn->invstd && bn->gamma && bn->beta), "vpho_conv3x3_winograd_stats_nhwc_f32: bn_x needs the four BatchNorm vectors");
         VPHO_REQUIRE(!bn->x || (((uintptr_t)bn->x & 15) == 0 && y_ld % 4 == 0 && 4.0 * N * H * W * y_ld < 3.9e9),
                      "vpho_conv3x3_winograd_stats_nhwc_f32: bn_x must be 16-byte aligned, y_ld %% 4 == 0, below 3.9 GB (it is fetched by 16-byte LDS-DMA)");
         a.stats = bn->stats; a.bn_x = bn->x; a.bn_mean = bn->mean; a.bn_invstd = bn->invstd; a.bn_gamma = bn->gamma; a.bn_beta = bn->beta;
-        *bn->rows = tbs;
-        const bool st1 = staged && wino_staged_ok(a.TH, a.TW, W);
+        *bn->rows = p.tbs;
         VPHO_DYN_LDS(conv_winograd_bn_kernel<1>, lds_staged);
         VPHO_DYN_LDS(conv_winograd_bn_kernel<0>, lds);
         VPHO_DYN_LDS(conv_winograd_bnb_kernel<1>, lds_staged);
         VPHO_DYN_LDS(conv_winograd_bnb_kernel<0>, lds);
-        if (bn->x) {
-            if (st1) hipLaunchKernelGGL(conv_winograd_bnb_kernel<1>, dim3(blocks, 1), dim3(256), lds_staged, (hipStream_t)stream, a);
-            else     hipLaunchKernelGGL(conv_winograd_bnb_kernel<0>, dim3(blocks, 1), dim3(256), lds, (hipStream_t)stream, a);
-        } else {
-            if (st1) hipLaunchKernelGGL(conv_winograd_bn_kernel<1>, dim3(blocks, 1), dim3(256), lds_staged, (hipStream_t)stream, a);
-            else     hipLaunchKernelGGL(conv_winograd_bn_kernel<0>, dim3(blocks, 1), dim3(256), lds, (hipStream_t)stream, a);
-        }
-        return vpho::check_launch("conv_winograd_bn_kernel");
     }
     // (Round 6, built and NOT kept: a persistent tile walk like conv_igemm_pers_kernel's -- the last super-stage of a tile prepares pixels, V and U of
     // the next tile's first stage, the epilogue runs with them in LDS -- bit-identical, and 1-6 % SLOWER on seven of nine layers (64 x 64 x 64 images
     // 256 -> 256: 1 233 against 1 220 us; 64 x 32 x 32 128 -> 128: 95.8 against 90.0), +1 % on two; docs/LOG.md round 6.  The one-tile kernel's
     // hand-over costs less than the walk's per-tile bookkeeping and its stage-end wait on the previous tile's stores.)
-    if (staged && wins)
-        hipLaunchKernelGGL(conv_winograd_kernel<2>, dim3(blocks, groups), dim3(256), lds_staged, (hipStream_t)stream, a);
-    else if (staged && wino_staged_ok(a.TH, a.TW, W))
-        hipLaunchKernelGGL(conv_winograd_kernel<1>, dim3(blocks, groups), dim3(256), lds_staged, (hipStream_t)stream, a);
-    else
-        hipLaunchKernelGGL(conv_winograd_kernel<0>, dim3(blocks, groups), dim3(256), lds, (hipStream_t)stream, a);
-    return vpho::check_launch("conv_winograd_kernel");
+    hipLaunchKernelGGL(wino_kernels[p.epilogue][p.mode], dim3(p.blocks, groups), dim3(256), p.lds, (hipStream_t)stream, a);
+    return vpho::check_launch(bn ? "conv_winograd_bn_kernel" : "conv_winograd_kernel");
 }
