@@ -82,7 +82,8 @@ def test_score_head_lds_copy_of_per_image_terms_is_bit_identical_to_global_loads
 
 def test_score_tail_tiles_match_oracle(sd, nets):
     """6 387 rows x 32 heads = 1 600 tiles on 512 workgroup slots: the launch runs 48 ordinary tiles per head and the remaining 243
-    rows as 32-row tail tiles (the last one ragged).  Rows of every kind of tile against the oracle, and BIT-IDENTICAL to a launch of
+    rows as 32-row tail tiles (the last one ragged) -- pinned without a device by tests/_score_plan_cases.py, a_head_tail_tiles_3x2129_hand,
+    with the 500-row launch below as a_head_250x2_ordinary_tiles_only.  Rows of every kind of tile against the oracle, and BIT-IDENTICAL to a launch of
     the same rows that is small enough to take ordinary tiles only: a hypothesis' score does not depend on the batch it is evaluated in
     (both tile kinds sum a row's 256 hidden units as the same eight partial sums of 32 in the same order)."""
     from oracle import nets as N
@@ -100,6 +101,39 @@ def test_score_tail_tiles_match_oracle(sd, nets):
     assert int(rows[0]) // S == int(rows[-1]) // S == 2
     small = nets['hand'].score(feat[[2, 2]].cuda(), torch.cat([x[rows], x[rows]]).cuda(), 0.3, 250).cpu()[:250]
     assert torch.equal(small, got[rows])
+
+
+def test_score_launches_are_the_ones_the_plan_table_names(nets):
+    """tests/_score_plan_cases.py pins, on the CPU, which kernels an evaluation launches and on what grid (tests/test_score_plan_cpu.py); this
+    scores the GPU_CASES of that table under profiling: one pose-encoder and one head launch per evaluation, each with exactly the flops of
+    its plan -- a refused or doubled launch, or a plan for other sizes, moves a counter.  3 x 700 rows on 32 heads are 17 tiles per head, one
+    past a round of 512 slots, so rows 2 048.. run as 32-row tail tiles: every image again in a launch of its own (6 tiles per head, ordinary
+    tiles only) must give the same bits."""
+    from vpho_amd import ops
+    from tests._score_plan_cases import CASES, GPU_CASES
+    classes = ('pose_encoder', 'score_head')
+    kept = {}
+    try:
+        for c in classes:
+            ops.prof_enable(c)
+            ops.prof_collect(c)
+        for net, bs, S, pe, head in GPU_CASES:
+            feat, x = seeded((bs, 1024), 80, 0.3).cuda(), seeded((bs * S, nets[net].D), 81, 1.5).cuda()
+            got = nets[net].score(feat, x, 0.3, S).clone()
+            assert torch.isfinite(got).all() and float(got.abs().max()) > 0
+            for c, case in zip(classes, (pe, head)):
+                plan = dict(t.split('=', 1) for t in CASES[case][1].split())
+                seen = ops.prof_collect(c)
+                assert (seen['launches'], seen['flops']) == (1, float(plan['flops'])), (case, seen)
+            kept[net, bs, S] = feat, x, got
+    finally:
+        for c in classes:
+            ops.prof_enable(c, False)
+    assert 'tail=2 ' in CASES['a_head_3x700_hand_17_tiles_one_past_a_round'][1]
+    feat, x, got = kept['hand', 3, 700]
+    for i in range(3):
+        one = nets['hand'].score(feat[i:i + 1], x[i * 700:(i + 1) * 700], 0.3, 700)
+        assert torch.equal(one, got[i * 700:(i + 1) * 700]), i
 
 
 @pytest.mark.parametrize('name,D', [('hand', 96), ('obj', 9)])

@@ -13,6 +13,7 @@
 // The RK stage algebra (fp64 state, fp32 stage derivatives exactly as numpy stores them), the error norm and the dense
 // output run as elementwise / two-pass-reduction kernels; only the 8-byte error norm crosses PCIe per attempted step.
 #include "common.h"
+#include "score_plan.h"                        // which kernels an evaluation launches: plan_pose_encoder, plan_head; Workspace, the RK45 tableau
 #include <type_traits>
 #include "../../include/vpho_hip.h"
 #include <cmath>
@@ -30,7 +31,6 @@ namespace {
 #ifndef HEAD_ABLATE
 #define HEAD_ABLATE 0                          // timing experiments on head_tile (scripts/kernel_ablate.sh score_ode HEAD_ABLATE ...): 1 no stage fills after the
 #endif                                         // first two, 2 no fragment reads after the first, 4 no stage barrier, 8 no epilogue -- wrong results, never in the product build
-constexpr int HB_K = 16;
 constexpr double SIGMA_MIN = 0.01, SIGMA_MAX = 50.0;
 
 // --------------------------------------------------------------------------------------------- time embedding
@@ -50,6 +50,7 @@ struct RkCtl {
     int n_accepted, n_rejected, nfev, n_log, log_cap, n_attempts;
     float ts[8], inv_std[8], coef[8];
 };
+static_assert(sizeof(RkCtl) == RKCTL_BYTES, "RkCtl is a kernel parameter's target and a slice of the workspace (score_plan.h): its layout does not move with the host code");
 // first-same-as-last: after an accepted step the roles of stage slots 0 and 6 are exchanged
 __device__ __host__ inline int kslot(int j, int kswap) { return (kswap && (j == 0 || j == 6)) ? 6 - j : j; }
 // ctl_mode of a kernel: 0 no controller; 1 part of an attempt (skip once the solve is done, scalars from the controller);
@@ -93,7 +94,6 @@ __global__ __launch_bounds__(256) void time_embed_kernel(const vpho_score_weight
 // --------------------------------------------------------------------------------------------- fused pose encoder
 // P2 = relu(relu(X W0^T + b0) W2^T + b2)   (denoiser.py:60-65,74): both Linear layers of `pose_encoder` in one launch.
 // Block = 32 hypotheses x all 256 hidden units; the 32x256 intermediate stays in LDS.
-struct LinComb { double c[7]; int n; double h; };
 // the seven stage-derivative buffers K_0..K_6 by LOGICAL stage index; first-same-as-last is a pointer swap on the host
 struct KSlots { const float* p[7]; };
 
@@ -106,7 +106,7 @@ struct PoseEncArgs {
     float* out; int R;                 // [R][256]
     const RkCtl* ctl; int ctl_mode, write_ynew; const float* kbase; long long n_el; double *ybuf0, *ybuf1;
 };
-constexpr int PE_ROWS = 32, PE_H_LD = 260;
+static_assert(sizeof(PoseEncArgs) == 272, "PoseEncArgs is the kernels' parameter: its layout does not move with the host code");
 
 // 8 waves; wave w owns hidden columns 32w..32w+31 (one 32x32 MFMA tile) of the workgroup's hypotheses.  Both weight matrices stream as
 // ONE sequence of [256][32] chunks (W0's ceil(Dp/32), then W2's 8) with the weight fragments in REGISTERS: a wave only ever reads its
@@ -327,6 +327,7 @@ struct HeadArgs {
     int nheads, full_tiles, tail_tiles;   // per head: 128-row tiles, then 32-row tail tiles (launch order: all full tiles first)
     const unsigned short* w1p_split;      // [nheads][3][256][256] bf16 planes of w1p (split-bf16 kernel only)
 };
+static_assert(sizeof(HeadArgs) == 160, "HeadArgs is the kernels' parameter: its layout does not move with the host code");
 
 // One tile of the score head: ROWS = 32*RG hypotheses of head n.  TI = MFMA row tiles (32 hidden units each) per wave:
 //   TI = 4: 128 hypotheses, wave = (row group rg = wave & 3) x (hidden half hh = wave >> 2)         -- the ordinary tile
@@ -639,7 +640,6 @@ __global__ __launch_bounds__(512, 4) void score_head_epi0_kernel(const HeadArgs 
 // v_cvt_pk_bf16_f32 + two subtractions per level, issued in the shadow of the MFMAs.  Error study: scripts/split_error_study.py.
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-constexpr int SP_K = 16;                                    // k per LDS stage = one 32x32x16 MFMA step
 
 __device__ __forceinline__ void split3(const f32x4& x0, const f32x4& x1, bf16x8& h, bf16x8& m, bf16x8& l) {
 #pragma unroll
@@ -1109,42 +1109,6 @@ __global__ void dense_ctl_kernel(const RkCtl* __restrict__ c, const double* ybuf
 }
 
 // --------------------------------------------------------------------------------------------- host side
-inline long long align_up(long long v) { return (v + 255) / 256 * 256; }
-
-struct Workspace {
-    float *cimg, *ct, *X, *P1, *P2, *K, *tmp;
-    double *y, *ynew, *partial, *result;
-    int* nan_count;
-    RkCtl* ctl; double *te, *dense_p, *log;
-    long long bytes;
-};
-constexpr int CTL_MAX_STEPS = 1024, CTL_LOG_CAP = 512;
-
-Workspace carve(const vpho_score_weights& w, int bs, int S, char* base) {
-    const long long R = (long long)bs * S, NH = (long long)w.nheads * 256;
-    long long off = 0;
-    Workspace ws;
-    auto take = [&](long long b) { char* p = base ? base + off : nullptr; off += align_up(b); return p; };
-    ws.cimg = (float*)take(bs * NH * 4);
-    ws.ct = (float*)take(8 * NH * 4);
-    ws.X = (float*)take(R * w.Dp * 4);
-    ws.P1 = (float*)take(R * 256 * 4);
-    ws.P2 = (float*)take(R * 256 * 4);
-    ws.K = (float*)take(7 * R * w.D * 4);
-    ws.tmp = (float*)take(R * w.D * 4);
-    ws.y = (double*)take(R * w.D * 8);
-    ws.ynew = (double*)take(R * w.D * 8);
-    ws.partial = (double*)take(1024 * 8);
-    ws.result = (double*)take(64);
-    ws.nan_count = (int*)take(64);
-    ws.ctl = (RkCtl*)take(sizeof(RkCtl));
-    ws.te = (double*)take(CTL_MAX_STEPS * 8);
-    ws.dense_p = (double*)take(CTL_MAX_STEPS * 4 * 8);
-    ws.log = (double*)take(CTL_LOG_CAP * 4 * 8);
-    ws.bytes = off;
-    return ws;
-}
-
 int check_weights(const vpho_score_weights* w) {
     VPHO_REQUIRE(w != nullptr, "score weights: null");
     VPHO_REQUIRE(w->nheads > 0 && w->D == w->nheads * 3 && w->Dp >= w->D && w->Dp % 4 == 0, "score weights: D=%d Dp=%d nheads=%d inconsistent", w->D, w->Dp, w->nheads);
@@ -1172,7 +1136,6 @@ int prepare_cimg(Ctx& c, const float* feat_img) {
     return linear(feat_img, c.bs, 1024, c.w->w1_f, c.w->b1, c.NH, 1.f, c.ws.cimg, c.s);
 }
 
-// X (R x Dp, fp32) -> out (R x D)
 // time embeddings of up to 8 evaluation times in one launch -> ct slots 0..n-1
 int embed_times(Ctx& c, const float* ts, int n, int ctl_mode = 0) {
     TimeList tl;
@@ -1182,119 +1145,107 @@ int embed_times(Ctx& c, const float* ts, int n, int ctl_mode = 0) {
     return vpho::check_launch("time_embed_kernel");
 }
 
-// ct_slot < 0: embed t now into slot 0; otherwise slot ct_slot was filled by embed_times for exactly this t
-// Controller-driven calls (ctl_mode 1: stage `stage` of an attempt, result into logical stage slot `out_slot`; 2: the final
-// denoise evaluation, which runs only once the solve is done) take their run-time scalars from c.ws.ctl.
+// (rows, n1) and (family, cb) -> kernel: the keys of plan_pose_encoder and plan_head.  A pair the plans never produce has no kernel.
+using PeKernel = void (*)(const PoseEncArgs);
+const PeKernel pe_kernels[2][4] = {
+    /* 32 rows */ {pose_encoder_reg_kernel<1>, pose_encoder_reg_kernel<2>, pose_encoder_reg_kernel<3>, pose_encoder_reg_kernel<4>},
+    /* 64 rows */ {pose_encoder_reg64_kernel<1>, pose_encoder_reg64_kernel<2>, pose_encoder_reg64_kernel<3>, pose_encoder_reg64_kernel<4>}};
+using HeadKernel = void (*)(const HeadArgs);
+const HeadKernel head_kernels[HEAD_NFAMILY][2] = {
+    //                 cb = 0: global loads            cb = 1: LDS copy of the per-image terms
+    /* HEAD_PLAIN  */ {score_head_kernel<false>,       score_head_kernel<true>},
+    /* HEAD_EPI0   */ {score_head_epi0_kernel<false>,  score_head_epi0_kernel<true>},
+    /* HEAD_SPLIT6 */ {score_head_split_kernel<6>,     nullptr},
+    /* HEAD_SPLIT9 */ {score_head_split_kernel<9>,     nullptr}};
+
+// Controller-driven calls (mode 1: stage `stage` of an attempt, result into logical stage slot `out_slot`; 2: the final denoise
+// evaluation, which runs only once the solve is done) take their run-time scalars from c.ws.ctl.
 struct CtlCall { int mode = 0, stage = 0, out_slot = 0, write_ynew = 0; };
 
-int eval_net(Ctx& c, const float* X, float t, int rhs_mode, float coef, float* out, int ct_slot = -1,
-             const LinComb* lc = nullptr, const double* y = nullptr, double* ynew = nullptr, const KSlots* ks = nullptr,
-             CtlCall cc = CtlCall()) {
+// One evaluation of the network: input rows (R x Dp, fp32) -> out (R x D)
+struct EvalCall {
+    const float* X = nullptr;           // the input rows, or (comb given) nothing: the pose encoder forms them as (float)(y + h * comb) ...
+    const LinComb* comb = nullptr;
+    const double* y = nullptr;          // ... from y and the stage slots ks (a controller-driven stage takes both from c.ws.ctl instead),
+    const KSlots* ks = nullptr;
+    double* ynew = nullptr;             // and stores them in fp64 here if given
+    float t = 0.f;                      // the time: embedded now into ct slot 0 (ct_slot < 0),
+    int ct_slot = -1;                   // or the slot embed_times filled for exactly this t
+    int rhs_mode = 0; float coef = 0.f; // out = score, or (rhs_mode) 0 - coef * score
+    float* out = nullptr;
+    CtlCall ctl;
+};
+
+// Plans both launches, then launches: a refused call launches nothing and counts nothing under profiling
+int eval_net(Ctx& c, const EvalCall& ev) {
+    const ScoreSwitches sw = read_score_switches();
+    PePlan pp;
+    if (plan_pose_encoder(c.R, c.w->D, c.w->Dp, sw, &pp)) return vpho::fail("%s", pp.error);
+    int slots = 0;                                               // two 57 KB workgroups per CU
+    if (vpho::workgroup_slots(&slots)) slots = -1;               // its error is returned where the plan comes to need the slots
+    HeadPlan hp;
+    if (plan_head(c.R, c.S, c.w->nheads, c.w->split_terms, c.w->w1_p_split != nullptr, slots, sw, &hp)) return hp.need_slots ? 1 : vpho::fail("%s", hp.error);
+    const PeKernel pe_kernel = pe_kernels[pp.rows == 64][pp.n1 - 1];
+    const HeadKernel head_kernel = head_kernels[hp.family][hp.cb];
+    VPHO_DYN_LDS(pe_kernel, pp.lds);
+    VPHO_DYN_LDS(head_kernel, hp.lds);
+
+    const CtlCall& cc = ev.ctl;
+    int ct_slot = ev.ct_slot;
     if (ct_slot < 0) {
-        if (int e = embed_times(c, &t, 1, cc.mode == 2 ? 2 : 0)) return e;
+        if (int e = embed_times(c, &ev.t, 1, cc.mode == 2 ? 2 : 0)) return e;
         ct_slot = 0;
     }
+    PoseEncArgs pa;
+    memset(&pa, 0, sizeof(pa));
+    pa.X = ev.X; pa.Dp = c.w->Dp; pa.w0 = c.w->pe0_w; pa.b0 = c.w->pe0_b; pa.w2 = c.w->pe2_w; pa.b2 = c.w->pe2_b;
+    pa.out = c.ws.P2; pa.R = (int)c.R;
+    if (ev.comb) { pa.use_lc = 1; pa.lc = *ev.comb; pa.y = ev.y; if (ev.ks) pa.ks = *ev.ks; pa.D = c.w->D; pa.ynew = ev.ynew; }
+    pa.ctl = cc.mode ? c.ws.ctl : nullptr; pa.ctl_mode = cc.mode; pa.write_ynew = cc.write_ynew; pa.kbase = c.ws.K; pa.n_el = c.n_el;
+    pa.ybuf0 = c.ws.y; pa.ybuf1 = c.ws.ynew;
     {
-        PoseEncArgs pa;
-        memset(&pa, 0, sizeof(pa));
-        pa.X = X; pa.Dp = c.w->Dp; pa.w0 = c.w->pe0_w; pa.b0 = c.w->pe0_b; pa.w2 = c.w->pe2_w; pa.b2 = c.w->pe2_b;
-        pa.out = c.ws.P2; pa.R = (int)c.R;
-        if (lc) { pa.use_lc = 1; pa.lc = *lc; pa.y = y; if (ks) pa.ks = *ks; pa.D = c.w->D; pa.ynew = ynew; }
-        pa.ctl = cc.mode ? c.ws.ctl : nullptr; pa.ctl_mode = cc.mode; pa.write_ynew = cc.write_ynew; pa.kbase = c.ws.K; pa.n_el = c.n_el;
-        pa.ybuf0 = c.ws.y; pa.ybuf1 = c.ws.ynew;
-        const int K1 = (pa.Dp + 31) / 32 * 32;
-        const dim3 pe_grid((unsigned)((c.R + PE_ROWS - 1) / PE_ROWS));
-        vpho::ProfScope pe_prof(vpho::PROF_POSE_ENC, c.s, 2.0 * (double)c.R * 256.0 * (K1 + 256.0), 0.0);
-        const size_t pe_lds = (size_t)(PE_ROWS * PE_H_LD + 512) * sizeof(float);            // 35 328 B
-        VPHO_REQUIRE(K1 <= 128 && (pa.Dp & 3) == 0, "pose encoder: input dimension %d (padded %d) not supported (<= 128, multiple of 4)", c.w->D, pa.Dp);
-        // 64-row workgroups above 8 192 rows, i.e. as soon as 32-row workgroups would be more than one per CU (measured, isolated launches, hand /
-        // object network: 12 800 rows 35.4 / 33.1 -> 30.4 / 27.9 us, 16 384 rows 35.8 / 32.6 -> 30.7 / 26.8, 32 768 rows -- BASELINE cfg4 -- 67.7 / 58.7 ->
-        // 57.8 / 47.8; at the README config's 6 400 rows the 32-row kernel wins, 18.7 against 28.9: 200 workgroups against 100 on 256 CUs).
-        // VPHO_PE_ROWS=32 / 64 forces either (A/B aid, read per call; the two are bit-identical)
-        const char* rows_env = getenv("VPHO_PE_ROWS");
-        const bool rows64 = rows_env ? atoi(rows_env) == 64 : c.R > 8192;
-        if (rows64) {
-            const size_t lds64 = (size_t)(2 * PE_ROWS * PE_H_LD + 512) * sizeof(float);          // 68 608 B
-            const dim3 grid64((unsigned)((c.R + 2 * PE_ROWS - 1) / (2 * PE_ROWS)));
-            VPHO_DYN_LDS(pose_encoder_reg64_kernel<1>, lds64); VPHO_DYN_LDS(pose_encoder_reg64_kernel<2>, lds64);
-            VPHO_DYN_LDS(pose_encoder_reg64_kernel<3>, lds64); VPHO_DYN_LDS(pose_encoder_reg64_kernel<4>, lds64);
-            switch (K1 / 32) {
-                case 1: hipLaunchKernelGGL(pose_encoder_reg64_kernel<1>, grid64, dim3(512), lds64, c.s, pa); break;
-                case 2: hipLaunchKernelGGL(pose_encoder_reg64_kernel<2>, grid64, dim3(512), lds64, c.s, pa); break;
-                case 3: hipLaunchKernelGGL(pose_encoder_reg64_kernel<3>, grid64, dim3(512), lds64, c.s, pa); break;
-                default: hipLaunchKernelGGL(pose_encoder_reg64_kernel<4>, grid64, dim3(512), lds64, c.s, pa); break;
-            }
-        } else
-        switch (K1 / 32) {
-            case 1: hipLaunchKernelGGL(pose_encoder_reg_kernel<1>, pe_grid, dim3(512), pe_lds, c.s, pa); break;
-            case 2: hipLaunchKernelGGL(pose_encoder_reg_kernel<2>, pe_grid, dim3(512), pe_lds, c.s, pa); break;
-            case 3: hipLaunchKernelGGL(pose_encoder_reg_kernel<3>, pe_grid, dim3(512), pe_lds, c.s, pa); break;
-            default: hipLaunchKernelGGL(pose_encoder_reg_kernel<4>, pe_grid, dim3(512), pe_lds, c.s, pa); break;
-        }
-        if (int e = vpho::check_launch(rows64 ? "pose_encoder_reg64_kernel" : "pose_encoder_reg_kernel")) return e;
+        vpho::ProfScope prof(vpho::PROF_POSE_ENC, c.s, pp.flops, 0.0);
+        hipLaunchKernelGGL(pe_kernel, dim3(pp.grid), dim3(512), pp.lds, c.s, pa);
     }
-    VPHO_REQUIRE((double)c.R * 256.0 * 4.0 < 4.0e9, "score head: %lld hypothesis rows exceed the 32-bit buffer offsets", (long long)c.R);
+    if (int e = vpho::check_launch(pp.name)) return e;
+
     HeadArgs a;
     a.w1p = c.w->w1_p; a.p2 = c.ws.P2; a.cimg = c.ws.cimg; a.ct = c.ws.ct + (long long)ct_slot * c.NH; a.w2 = c.w->w2; a.b2 = c.w->b2;
-    a.out = out; a.nan_count = c.ws.nan_count; a.R = (int)c.R; a.S = c.S; a.NH = c.NH; a.D = c.w->D;
-    a.inv_std_den = sigma_f32(t) + 1e-7f; a.coef = coef; a.rhs_mode = rhs_mode;
+    a.out = ev.out; a.nan_count = c.ws.nan_count; a.R = (int)c.R; a.S = c.S; a.NH = c.NH; a.D = c.w->D;
+    a.inv_std_den = sigma_f32(ev.t) + 1e-7f; a.coef = ev.coef; a.rhs_mode = ev.rhs_mode;
     a.ctl = cc.mode ? c.ws.ctl : nullptr; a.ctl_mode = cc.mode; a.stage = cc.stage; a.out_slot = cc.out_slot; a.kbase = c.ws.K; a.n_el = c.n_el;
-    // [2] stages | [256][4] epilogue table | per-image terms (3 x 257 of 1024 floats)
-    size_t lds = (size_t)(2 * (256 + 128) * HB_K + 256 * 4 + 2 * 128 * 4) * sizeof(float);
-    VPHO_DYN_LDS(score_head_kernel<true>, lds);
-    VPHO_DYN_LDS(score_head_kernel<false>, lds);
-    VPHO_DYN_LDS(score_head_epi0_kernel<true>, lds);
-    VPHO_DYN_LDS(score_head_epi0_kernel<false>, lds);
-    // Tile plan: 128-row tiles; when the last round of the launch would be less than half full, the rows beyond the last full round
-    // become 32-row tail tiles (see head_tile).  VPHO_HEAD_TAIL=0: ordinary tiles only.
-    static const int tail_on = getenv("VPHO_HEAD_TAIL") ? atoi(getenv("VPHO_HEAD_TAIL")) : 1;
-    int slots = 0;                                          // two 57 KB workgroups per CU
-    if (vpho::workgroup_slots(&slots)) return 1;
-    const int tiles = (int)((c.R + 127) / 128), nheads = c.w->nheads;
-    a.nheads = nheads; a.full_tiles = tiles; a.tail_tiles = 0;
-    const long long total = (long long)tiles * nheads;
-    if (tail_on && total > slots && total % slots != 0 && (total % slots) * 2 < slots) {
-        const int fp = (int)(total / slots * slots / nheads);
-        if (fp >= 1 && fp < tiles) { a.full_tiles = fp; a.tail_tiles = (int)((c.R - 128ll * fp + 31) / 32); }
-    }
+    a.nheads = c.w->nheads; a.full_tiles = hp.full_tiles; a.tail_tiles = hp.tail_tiles;
     a.w1p_split = (const unsigned short*)c.w->w1_p_split;
-    if (c.w->w1_p_split && (c.w->split_terms == 6 || c.w->split_terms == 9)) {
-        const size_t slds = (size_t)(2 * (3 * 256 * SP_K / 2 + 128 * SP_K) + 256 * 4 + 2 * 128 * 4) * sizeof(float);
-        VPHO_DYN_LDS(score_head_split_kernel<6>, slds);
-        VPHO_DYN_LDS(score_head_split_kernel<9>, slds);
-        vpho::ProfScope prof(vpho::PROF_SCORE_HEAD, c.s, (double)c.R * c.w->nheads * (2.0 * 256 * 256 + 2.0 * 256 * 3));
-        const dim3 grid((unsigned)(nheads * (a.full_tiles + a.tail_tiles)));
-        if (c.w->split_terms == 6) hipLaunchKernelGGL(score_head_split_kernel<6>, grid, dim3(512), slds, c.s, a);
-        else                       hipLaunchKernelGGL(score_head_split_kernel<9>, grid, dim3(512), slds, c.s, a);
-        return vpho::check_launch("score_head_split_kernel");
-    }
     {
-        vpho::ProfScope prof(vpho::PROF_SCORE_HEAD, c.s, (double)c.R * c.w->nheads * (2.0 * 256 * 256 + 2.0 * 256 * 3));
-        // per-image epilogue terms from an LDS copy when a 128-row tile spans at most 3 images (sample_num >= 64; VPHO_HEAD_CB=0: global loads, A/B aid -- same bits)
-        const char* cb_s = getenv("VPHO_HEAD_CB");
-        const int cb_env = cb_s ? atoi(cb_s) : 1;
-        const dim3 grid((unsigned)(nheads * (a.full_tiles + a.tail_tiles)));
-        const bool cb = c.S >= 64 && cb_env;
-        // VPHO_HEAD_EPI=0: the reference epilogue (read per call; same bits)
-        const char* epi_s = getenv("VPHO_HEAD_EPI");
-        if (epi_s && atoi(epi_s) == 0) {
-            if (cb) hipLaunchKernelGGL(score_head_epi0_kernel<true>, grid, dim3(512), lds, c.s, a);
-            else    hipLaunchKernelGGL(score_head_epi0_kernel<false>, grid, dim3(512), lds, c.s, a);
-        } else if (cb) hipLaunchKernelGGL(score_head_kernel<true>, grid, dim3(512), lds, c.s, a);
-        else           hipLaunchKernelGGL(score_head_kernel<false>, grid, dim3(512), lds, c.s, a);
+        vpho::ProfScope prof(vpho::PROF_SCORE_HEAD, c.s, hp.flops);
+        hipLaunchKernelGGL(head_kernel, dim3(hp.grid), dim3(512), hp.lds, c.s, a);
     }
-    return vpho::check_launch("score_head_kernel");
+    return vpho::check_launch(hp.name);
 }
 
 // rhs(t, .) of the probability-flow ODE: 0 - f32(0.5 g(t)^2) * score     (score_based_model.py:74-83)
 // first_call: fun(t0, y0), the one evaluation whose t is a Python float in scipy (-> float32 sigma); every other t is np.float64 (see ctl_stage_scalars)
-int eval_rhs(Ctx& c, const float* X, double t, float* out, int ct_slot = -1, const LinComb* lc = nullptr,
-             const double* y = nullptr, double* ynew = nullptr, const KSlots* ks = nullptr, bool first_call = false) {
+int eval_rhs(Ctx& c, EvalCall ev, double t, bool first_call = false) {
     const float tf = (float)t;
     const double sigma = first_call ? (double)sigma_f32(tf) : SIGMA_MIN * std::pow(SIGMA_MAX / SIGMA_MIN, t);
     const double g = sigma * std::sqrt(2.0 * (std::log(SIGMA_MAX) - std::log(SIGMA_MIN)));
-    const float coef = (float)(0.5 * g * g);
-    return eval_net(c, X, tf, 1, coef, out, ct_slot, lc, y, ynew, ks);
+    ev.t = tf; ev.rhs_mode = 1; ev.coef = (float)(0.5 * g * g);
+    return eval_net(c, ev);
+}
+
+// What every entry point does first: the NaN counter, the per-image terms, x (R x D, fp32) as the fp64 state y and as the input rows X
+int enqueue_prologue(Ctx& c, const float* feat_img, const float* x) {
+    VPHO_HIP(hipMemsetAsync(c.ws.nan_count, 0, 4, c.s));
+    if (int e = prepare_cimg(c, feat_img)) return e;
+    const int nb = (int)((c.R * c.w->Dp + 255) / 256);
+    hipLaunchKernelGGL(f32_to_state_kernel, dim3(nb), dim3(256), 0, c.s, x, c.n_el, c.w->D, c.w->Dp, c.ws.y, c.ws.X);
+    return 0;
+}
+// the seven stage slots at their home positions
+KSlots home_slots(const Ctx& c) {
+    KSlots ks;
+    for (int j = 0; j < 7; ++j) ks.p[j] = c.ws.K + (long long)j * c.n_el;
+    return ks;
 }
 
 double* pinned_slot() {
@@ -1323,25 +1274,6 @@ int reduce_norm(Ctx& c, NormArgs na, double* value) {
     return 0;
 }
 
-const double RK_C[6] = {0, 1.0 / 5, 3.0 / 10, 4.0 / 5, 8.0 / 9, 1};
-const double RK_A[6][5] = {
-    {0, 0, 0, 0, 0},
-    {1.0 / 5, 0, 0, 0, 0},
-    {3.0 / 40, 9.0 / 40, 0, 0, 0},
-    {44.0 / 45, -56.0 / 15, 32.0 / 9, 0, 0},
-    {19372.0 / 6561, -25360.0 / 2187, 64448.0 / 6561, -212.0 / 729, 0},
-    {9017.0 / 3168, -355.0 / 33, 46732.0 / 5247, 49.0 / 176, -5103.0 / 18656}};
-const double RK_B[6] = {35.0 / 384, 0, 500.0 / 1113, 125.0 / 192, -2187.0 / 6784, 11.0 / 84};
-const double RK_E[7] = {-71.0 / 57600, 0, 71.0 / 16695, -71.0 / 1920, 17253.0 / 339200, -22.0 / 525, 1.0 / 40};
-const double RK_P[7][4] = {
-    {1, -8048581381.0 / 2820520608, 8663915743.0 / 2820520608, -12715105075.0 / 11282082432},
-    {0, 0, 0, 0},
-    {0, 131558114200.0 / 32700410799, -68118460800.0 / 10900136933, 87487479700.0 / 32700410799},
-    {0, -1754552775.0 / 470086768, 14199869525.0 / 1410260304, -10690763975.0 / 1880347072},
-    {0, 127303824393.0 / 49829197408, -318862633887.0 / 49829197408, 701980252875.0 / 199316789632},
-    {0, -282668133.0 / 205662961, 2019193451.0 / 616988883, -1453857185.0 / 822651844},
-    {0, 40617522.0 / 29380423, -110615467.0 / 29380423, 69997945.0 / 29380423}};
-
 }  // namespace
 
 extern "C" long long vpho_score_workspace_bytes(const vpho_score_weights* w, int bs, int S) {
@@ -1357,14 +1289,32 @@ extern "C" int vpho_score_eval(const vpho_score_weights* w, const float* feat_im
     c.w = w; c.bs = bs; c.S = S; c.R = (long long)bs * S; c.n_el = c.R * w->D; c.NH = w->nheads * 256; c.s = (hipStream_t)stream;
     c.ws = carve(*w, bs, S, (char*)workspace);
     VPHO_REQUIRE(workspace_bytes >= c.ws.bytes, "vpho_score_eval: workspace %lld < %lld bytes", workspace_bytes, c.ws.bytes);
-    VPHO_HIP(hipMemsetAsync(c.ws.nan_count, 0, 4, c.s));
-    if (int e = prepare_cimg(c, feat_img)) return e;
-    const int nb = (int)((c.R * w->Dp + 255) / 256);
-    hipLaunchKernelGGL(f32_to_state_kernel, dim3(nb), dim3(256), 0, c.s, x, c.n_el, w->D, w->Dp, c.ws.y, c.ws.X);
-    return eval_net(c, c.ws.X, t, 0, 0.f, out);
+    if (int e = enqueue_prologue(c, feat_img, x)) return e;
+    EvalCall ev;
+    ev.X = c.ws.X; ev.t = t; ev.out = out;
+    return eval_net(c, ev);
 }
 
 namespace {
+
+// Reverse-diffusion predictor "denoise" step at t = eps on the state y.  ctl_mode 0: the host controller's (y and ks are the current
+// ones); 2: the device controller's -- its kernels are no-ops until the controller says done and take the state buffer from it
+int enqueue_denoise(Ctx& c, const double* y, const KSlots& ks, double eps, int num_steps, void* x_out, int x_is_f64, int ctl_mode) {
+    const int D = c.w->D, Dp = c.w->Dp;
+    const int nbX = (int)((c.R * Dp + 255) / 256), nbE = (int)((c.n_el + 255) / 256);
+    const RkCtl* ctl = ctl_mode ? c.ws.ctl : nullptr;
+    const double *ybuf0 = ctl_mode ? c.ws.y : nullptr, *ybuf1 = ctl_mode ? c.ws.ynew : nullptr;
+    const float tfl = (float)eps;
+    hipLaunchKernelGGL(stage_input_kernel, dim3(nbX), dim3(256), 0, c.s, y, ks, c.n_el, D, Dp, LinComb{{0}, 0, 0.0}, c.ws.X, (double*)nullptr,
+                       ctl, ctl_mode, ybuf0, ybuf1);
+    EvalCall ev;
+    ev.X = c.ws.X; ev.t = tfl; ev.out = c.ws.tmp; ev.ctl.mode = ctl_mode;
+    if (int e = eval_net(c, ev)) return e;
+    const float g = sigma_f32(tfl) * (float)std::sqrt(2.0 * (std::log(SIGMA_MAX) - std::log(SIGMA_MIN)));
+    const float stepf = (float)((1.0 - eps) / num_steps);
+    hipLaunchKernelGGL(denoise_kernel, dim3(nbE), dim3(256), 0, c.s, y, c.ws.tmp, c.n_el, g, stepf, x_out, x_is_f64, ctl, ybuf0, ybuf1);
+    return vpho::check_launch("ode tail");
+}
 
 // ---- host-driven solve: the scalar controller runs on the host exactly as scipy's, one 8-byte D2H + sync per attempt ----
 int ode_sample_host(Ctx& c, const float* feat_img, const float* init_x, double T0, double eps, int num_steps, double rtol, double atol,
@@ -1373,24 +1323,15 @@ int ode_sample_host(Ctx& c, const float* feat_img, const float* init_x, double T
     const long long n_el = c.n_el;
     const int D = w->D, Dp = w->Dp;
     const int nbX = (int)((c.R * Dp + 255) / 256), nbE = (int)((n_el + 255) / 256);
-    KSlots ks;
-    for (int j = 0; j < 7; ++j) ks.p[j] = c.ws.K + (long long)j * n_el;
+    KSlots ks = home_slots(c);
     auto Kp = [&](int j) { return const_cast<float*>(ks.p[j]); };
 
-    VPHO_HIP(hipMemsetAsync(c.ws.nan_count, 0, 4, c.s));
-    if (int e = prepare_cimg(c, feat_img)) return e;
+    if (int e = enqueue_prologue(c, feat_img, init_x)) return e;
     double* y = c.ws.y;
     double* ynew = c.ws.ynew;
-    hipLaunchKernelGGL(f32_to_state_kernel, dim3(nbX), dim3(256), 0, c.s, init_x, n_el, D, Dp, y, c.ws.X);
 
-    // t_eval = np.linspace(T0, eps, num_steps)
     std::vector<double> te(num_steps);
-    {
-        const int div = num_steps > 1 ? num_steps - 1 : 1;
-        const double step = (eps - T0) / div;
-        for (int i = 0; i < num_steps; ++i) te[i] = (double)i * step + T0;
-        if (num_steps > 1) te[num_steps - 1] = eps;
-    }
+    t_eval_linspace(T0, eps, num_steps, te.data());
     const double direction = -1.0, tf = eps, max_step = 10.0;
     double t = T0;
     int next_idx = 0;
@@ -1403,7 +1344,10 @@ int ode_sample_host(Ctx& c, const float* feat_img, const float* init_x, double T
     };
 
     // f0 = fun(t0, y0); select_initial_step
-    if (int e = eval_rhs(c, c.ws.X, t, Kp(0), -1, nullptr, nullptr, nullptr, nullptr, true)) return e;
+    EvalCall from_X;
+    from_X.X = c.ws.X;
+    from_X.out = Kp(0);
+    if (int e = eval_rhs(c, from_X, t, true)) return e;
     ++st->nfev;
     double h_abs;
     {
@@ -1423,7 +1367,8 @@ int ode_sample_host(Ctx& c, const float* feat_img, const float* init_x, double T
         lc.n = 1; lc.c[0] = 1.0; lc.h = h0 * direction;
         hipLaunchKernelGGL(stage_input_kernel, dim3(nbX), dim3(256), 0, c.s, y, ks, n_el, D, Dp, lc, c.ws.X, (double*)nullptr,
                            (const RkCtl*)nullptr, 0, (const double*)nullptr, (const double*)nullptr);
-        if (int e = eval_rhs(c, c.ws.X, t + h0 * direction, Kp(1))) return e;
+        from_X.out = Kp(1);
+        if (int e = eval_rhs(c, from_X, t + h0 * direction)) return e;
         ++st->nfev;
         na.mode = 2; na.Ka = Kp(0); na.Kb = Kp(1);
         if (int e = reduce_norm(c, na, &d2)) return e;
@@ -1451,19 +1396,13 @@ int ode_sample_host(Ctx& c, const float* feat_img, const float* init_x, double T
                 ts[5] = (float)(t + h);
                 if (int e = embed_times(c, ts, 6)) return e;
             }
-            for (int s = 1; s < 6; ++s) {
-                LinComb lc;
-                memset(&lc, 0, sizeof(lc));
-                lc.n = s; lc.h = h;
-                for (int j = 0; j < s; ++j) lc.c[j] = RK_A[s][j];
-                if (int e = eval_rhs(c, nullptr, t + RK_C[s] * h, Kp(s), s - 1, &lc, y, nullptr, &ks)) return e;   // stage state formed in the pose encoder
-            }
-            {
-                LinComb lc;
-                memset(&lc, 0, sizeof(lc));
-                lc.n = 6; lc.h = h;
-                for (int j = 0; j < 6; ++j) lc.c[j] = RK_B[j];
-                if (int e = eval_rhs(c, nullptr, t + h, Kp(6), 5, &lc, y, ynew, &ks)) return e;                    // also stores y_new (fp64)
+            for (int s = 1; s <= 6; ++s) {
+                LinComb lc = stage_comb(s);
+                lc.h = h;
+                EvalCall ev;                                       // stage state formed in the pose encoder
+                ev.comb = &lc; ev.y = y; ev.ks = &ks; ev.ct_slot = s - 1; ev.out = Kp(s);
+                if (s == 6) ev.ynew = ynew;                        // the last one also stores y_new (fp64)
+                if (int e = eval_rhs(c, ev, s < 6 ? t + RK_C[s] * h : t + h)) return e;
             }
             st->nfev += 6;
             NormArgs na;
@@ -1505,19 +1444,8 @@ int ode_sample_host(Ctx& c, const float* feat_img, const float* init_x, double T
         std::swap(ks.p[0], ks.p[6]);
         t = t_new;
     }
-    // reverse-diffusion predictor "denoise" step at t = eps
-    {
-        const float tfl = (float)eps;
-        hipLaunchKernelGGL(stage_input_kernel, dim3(nbX), dim3(256), 0, c.s, y, ks, n_el, D, Dp, LinComb{{0}, 0, 0.0}, c.ws.X, (double*)nullptr,
-                           (const RkCtl*)nullptr, 0, (const double*)nullptr, (const double*)nullptr);
-        if (int e = eval_net(c, c.ws.X, tfl, 0, 0.f, c.ws.tmp)) return e;
-        ++st->nfev;
-        const float g = sigma_f32(tfl) * (float)std::sqrt(2.0 * (std::log(SIGMA_MAX) - std::log(SIGMA_MIN)));
-        const float stepf = (float)((1.0 - eps) / num_steps);
-        hipLaunchKernelGGL(denoise_kernel, dim3(nbE), dim3(256), 0, c.s, y, c.ws.tmp, n_el, g, stepf, x_out, x_is_f64,
-                           (const RkCtl*)nullptr, (const double*)nullptr, (const double*)nullptr);
-    }
-    if (int e = vpho::check_launch("ode tail")) return e;
+    if (int e = enqueue_denoise(c, y, ks, eps, num_steps, x_out, x_is_f64, 0)) return e;
+    ++st->nfev;
     int nan_host = 0;
     VPHO_HIP(hipMemcpyAsync(&nan_host, c.ws.nan_count, 4, hipMemcpyDeviceToHost, c.s));
     VPHO_HIP(hipStreamSynchronize(c.s));
@@ -1555,18 +1483,18 @@ int ode_sample_device(Ctx& c, const float* feat_img, const float* init_x, double
     const int D = w->D, Dp = w->Dp;
     const int nbX = (int)((c.R * Dp + 255) / 256), nbE = (int)((n_el + 255) / 256);
     RkCtl* ctl = c.ws.ctl;
-    KSlots ks;
-    for (int j = 0; j < 7; ++j) ks.p[j] = c.ws.K + (long long)j * n_el;
+    const KSlots ks = home_slots(c);
     const double g_scale = std::sqrt(2.0 * (std::log(SIGMA_MAX) - std::log(SIGMA_MIN)));
 
-    VPHO_HIP(hipMemsetAsync(c.ws.nan_count, 0, 4, c.s));
     RkSetup su{T0, eps, rtol, atol, g_scale, num_steps, CTL_LOG_CAP, c.ws.te, c.ws.dense_p, c.ws.log};
     hipLaunchKernelGGL(rk_setup_kernel, dim3(1), dim3(1), 0, c.s, ctl, su);
-    if (int e = prepare_cimg(c, feat_img)) return e;
-    hipLaunchKernelGGL(f32_to_state_kernel, dim3(nbX), dim3(256), 0, c.s, init_x, n_el, D, Dp, c.ws.y, c.ws.X);
+    if (int e = enqueue_prologue(c, feat_img, init_x)) return e;
 
     // select_initial_step: f0 = fun(t0, y0) (t0 is known here), d0, d1 -> h0 on the device -> probe evaluation -> d2 -> h_abs
-    if (int e = eval_rhs(c, c.ws.X, T0, c.ws.K, -1, nullptr, nullptr, nullptr, nullptr, true)) return e;
+    EvalCall from_X;
+    from_X.X = c.ws.X;
+    from_X.out = c.ws.K;
+    if (int e = eval_rhs(c, from_X, T0, true)) return e;
     {
         NormArgs na;
         memset(&na, 0, sizeof(na));
@@ -1582,9 +1510,10 @@ int ode_sample_device(Ctx& c, const float* feat_img, const float* init_x, double
         hipLaunchKernelGGL(stage_input_kernel, dim3(nbX), dim3(256), 0, c.s, c.ws.y, ks, n_el, D, Dp, lc, c.ws.X, (double*)nullptr,
                            (const RkCtl*)ctl, 1, (const double*)c.ws.y, (const double*)c.ws.ynew);
         if (int e = embed_times(c, nullptr, 1, 1)) return e;
-        CtlCall cc;
-        cc.mode = 1; cc.stage = 0; cc.out_slot = 1;
-        if (int e = eval_net(c, c.ws.X, 0.f, 1, 0.f, nullptr, 0, nullptr, nullptr, nullptr, nullptr, cc)) return e;
+        EvalCall probe;                                            // time, sigma and the coefficient come from the controller
+        probe.X = c.ws.X; probe.ct_slot = 0; probe.rhs_mode = 1;
+        probe.ctl.mode = 1; probe.ctl.stage = 0; probe.ctl.out_slot = 1;
+        if (int e = eval_net(c, probe)) return e;
         na.mode = 2; na.Ka = ks.p[0]; na.Kb = ks.p[1];
         if (int e = enqueue_norm(c, na, &ctl->d[2])) return e;
         hipLaunchKernelGGL(rk_init2_kernel, dim3(1), dim3(1), 0, c.s, ctl, n_el);
@@ -1598,13 +1527,11 @@ int ode_sample_device(Ctx& c, const float* feat_img, const float* init_x, double
         hipLaunchKernelGGL(rk_begin_kernel, dim3(1), dim3(1), 0, c.s, ctl, kc);
         if (int e = embed_times(c, nullptr, 6, 1)) return e;
         for (int s = 1; s <= 6; ++s) {
-            LinComb lc;
-            memset(&lc, 0, sizeof(lc));
-            lc.n = s < 6 ? s : 6;
-            for (int j = 0; j < lc.n; ++j) lc.c[j] = s < 6 ? RK_A[s][j] : RK_B[j];
-            CtlCall cc;
-            cc.mode = 1; cc.stage = s - 1; cc.out_slot = s; cc.write_ynew = s == 6;
-            if (int e = eval_net(c, nullptr, 0.f, 1, 0.f, nullptr, s - 1, &lc, nullptr, nullptr, nullptr, cc)) return e;
+            const LinComb lc = stage_comb(s);                      // h, y and the stage slots come from the controller
+            EvalCall ev;
+            ev.comb = &lc; ev.ct_slot = s - 1; ev.rhs_mode = 1;
+            ev.ctl.mode = 1; ev.ctl.stage = s - 1; ev.ctl.out_slot = s; ev.ctl.write_ynew = s == 6;
+            if (int e = eval_net(c, ev)) return e;
         }
         NormArgs na;
         memset(&na, 0, sizeof(na));
@@ -1615,20 +1542,6 @@ int ode_sample_device(Ctx& c, const float* feat_img, const float* init_x, double
         hipLaunchKernelGGL(dense_ctl_kernel, dim3(nbE), dim3(256), 0, c.s, (const RkCtl*)ctl, (const double*)c.ws.y, (const double*)c.ws.ynew,
                            (const float*)c.ws.K, n_el, D, dp, xs_out, xs_is_f64, num_steps);
         return vpho::check_launch("rk attempt");
-    };
-    // reverse-diffusion predictor "denoise" step at t = eps; its kernels are no-ops until the controller says done
-    auto enqueue_final = [&]() -> int {
-        const float tfl = (float)eps;
-        hipLaunchKernelGGL(stage_input_kernel, dim3(nbX), dim3(256), 0, c.s, (const double*)c.ws.y, ks, n_el, D, Dp, LinComb{{0}, 0, 0.0}, c.ws.X,
-                           (double*)nullptr, (const RkCtl*)ctl, 2, (const double*)c.ws.y, (const double*)c.ws.ynew);
-        CtlCall cc;
-        cc.mode = 2;
-        if (int e = eval_net(c, c.ws.X, tfl, 0, 0.f, c.ws.tmp, -1, nullptr, nullptr, nullptr, nullptr, cc)) return e;
-        const float g = sigma_f32(tfl) * (float)g_scale;
-        const float stepf = (float)((1.0 - eps) / num_steps);
-        hipLaunchKernelGGL(denoise_kernel, dim3(nbE), dim3(256), 0, c.s, (const double*)c.ws.y, c.ws.tmp, n_el, g, stepf, x_out, x_is_f64,
-                           (const RkCtl*)ctl, (const double*)c.ws.y, (const double*)c.ws.ynew);
-        return vpho::check_launch("ode tail");
     };
 
     // Enqueue as many attempts as the previous solve on this workspace needed, then the final step, then look ONCE.
@@ -1650,7 +1563,7 @@ int ode_sample_device(Ctx& c, const float* feat_img, const float* init_x, double
         const int n = round == 0 ? std::max(1, n_first) : 2;
         for (int i = 0; i < n; ++i) if (int e = enqueue_attempt()) return e;
         enq += n;
-        if (int e = enqueue_final()) return e;
+        if (int e = enqueue_denoise(c, c.ws.y, ks, eps, num_steps, x_out, x_is_f64, 2)) return e;
         VPHO_HIP(hipMemcpyAsync(hc, ctl, sizeof(RkCtl), hipMemcpyDeviceToHost, c.s));
         VPHO_HIP(hipMemcpyAsync(nan_host, c.ws.nan_count, 4, hipMemcpyDeviceToHost, c.s));
         if (int e = blocking_wait(c.s)) return e;
@@ -1692,7 +1605,7 @@ extern "C" int vpho_ode_sample(const vpho_score_weights* w, const float* feat_im
     VPHO_REQUIRE(workspace_bytes >= c.ws.bytes, "vpho_ode_sample: workspace %lld < %lld bytes", workspace_bytes, c.ws.bytes);
     memset(st, 0, sizeof(*st));
     // VPHO_RK_HOST=1: scipy's controller on the host (one sync per attempted step); default: controller on the device
-    static const bool host_ctl = getenv("VPHO_RK_HOST") && atoi(getenv("VPHO_RK_HOST")) != 0;
+    static const bool host_ctl = env_int("VPHO_RK_HOST", 0) != 0;
     if (host_ctl || num_steps > CTL_MAX_STEPS)
         return ode_sample_host(c, feat_img, init_x, T0, eps, num_steps, rtol, atol, xs_out, xs_is_f64, x_out, x_is_f64, st, step_log, step_log_cap);
     return ode_sample_device(c, feat_img, init_x, T0, eps, num_steps, rtol, atol, xs_out, xs_is_f64, x_out, x_is_f64, st, step_log, step_log_cap);
