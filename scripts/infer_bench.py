@@ -92,9 +92,8 @@ def _kernel_legs(torch, a):
            'agg_obj_6d': torch.randn(n, 9, generator=g, dtype=torch.float64).cuda()}
     batch = {'root_joint': torch.randn(n, 3, generator=g).cuda(), 'is_right': (torch.rand(n, generator=g) < 0.5).cuda()}
     stage, host = packer.stage[0], packer.host[0]
-    args = [ops._f32(out[k]) for k in ('reg_hand_joint', 'reg_hand_vert', 'agg_hand_joint', 'agg_hand_vert')] + \
-           [ops._f64(out['agg_obj_6d']), ops._f32(batch['root_joint']), ops._u8(batch['is_right'].view(torch.uint8)), ops.I(n), ops.I(21), ops.I(778),
-            ops._ptr(stage)]
+    rj, rv, aj, av = (out[k] for k in ('reg_hand_joint', 'reg_hand_vert', 'agg_hand_joint', 'agg_hand_vert'))
+    o9, root, flag = out['agg_obj_6d'], batch['root_joint'], batch['is_right'].view(torch.uint8)
 
     def ms(fn):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -103,7 +102,7 @@ def _kernel_legs(torch, a):
         e1.record()
         e1.synchronize()
         return e0.elapsed_time(e1)
-    kernel = lambda: ops._call('vpho_infer_pack_f32', *args, None)                 # records_host NULL: the kernel alone
+    kernel = lambda: ops._call('vpho_infer_pack_f32', rj, rv, aj, av, o9, root, flag, n, 21, 778, stage, None)                 # records_host NULL: the kernel alone
     copy = lambda: host.copy_(stage, non_blocking=True)
     both = lambda: packer.pack(out, batch)
     for fn in (kernel, copy, both):

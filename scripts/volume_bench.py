@@ -58,12 +58,12 @@ def main():
     hand = torch.from_numpy(np.stack(hands).astype(np.float32)).to(dev)
     out = torch.empty((bs, 2), dtype=torch.float64, device=dev)
     F_ = int(meter.hand_faces.shape[0])
-    ws = torch.empty(ops.lib.vpho_hand_obj_intersection_workspace_bytes(ops.I(bs), ops.I(F_)), dtype=torch.uint8, device=dev)
+    ws = torch.empty(ops.abi.query('vpho_hand_obj_intersection_workspace_bytes', bs, F_), dtype=torch.uint8, device=dev)
     empty = ops.ObjSolids(sol['pts'].data_ptr(), sol['pt_offset'].data_ptr(), len(meter.names), 0)
 
     def run(solids):
-        ops._call('vpho_hand_obj_intersection_f64', C.byref(meter.c), C.byref(solids), ops._i32(meter.hand_faces), ops.I(F_), ops._f32(hand), ops.I(bs),
-                  ops.I(778), ops._f64(rt), ops._i32(oid), C.c_double(a.pitch), ops._f64(out), None, ops._ptr(ws), ops.LL(ws.numel()))
+        ops._call('vpho_hand_obj_intersection_f64', C.byref(meter.c), C.byref(solids), meter.hand_faces, F_, hand, bs,
+                  778, rt, oid, a.pitch, out, None, ws, ws.numel())
     legs = dict(setup=lambda: run(empty), total=lambda: run(sol['c']), wrapper=lambda: meter.volume(hand, rt, oid, a.pitch))
     for fn in legs.values():
         fn()

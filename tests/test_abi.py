@@ -35,7 +35,7 @@ def test_library_exports_every_declared_symbol_at_the_pinned_abi_version():
 
 def test_the_abi_version_is_one_number_in_the_header_the_library_and_the_binding():
     """the header's comment, common.cpp, ops.ABI_VERSION and the library that ops loaded: a stale library is refused when ops is imported
-    (ops.py compares the two), not found out by a missing symbol halfway through a run"""
+    (abi.py, which ops imports, compares the two), not found out by a missing symbol halfway through a run"""
     import __graft_entry__ as g
     g.build()
     hdr = open(os.path.join(ROOT, 'include', 'vpho_hip.h')).read()
@@ -46,7 +46,7 @@ def test_the_abi_version_is_one_number_in_the_header_the_library_and_the_binding
     assert m and int(m.group(2)) == ABI_VERSION
     from vpho_amd import ops
     assert ops.ABI_VERSION == ABI_VERSION and ops.lib.vpho_abi_version() == ABI_VERSION
-    binding = open(os.path.join(ROOT, 'vpho_amd', 'ops.py')).read()
+    binding = open(os.path.join(ROOT, 'vpho_amd', 'abi.py')).read()
     assert re.search(r'if lib\.vpho_abi_version\(\) != ABI_VERSION:\s*raise ImportError', binding)
     for doc in ('README.md', 'INTEGRATION.md'):
         assert re.search(r'version %d\b' % ABI_VERSION, open(os.path.join(ROOT, doc)).read()), doc
@@ -201,90 +201,224 @@ def test_ctypes_structures_mirror_the_header_field_for_field():
         assert f"'{f}'" in doc, f'INTEGRATION.md example lacks vpho_score_weights.{f}'
 
 
-def _header_prototypes():
-    """{function: [kind of every parameter]} with kind in ptr / int / float / double / longlong"""
-    import re
-    txt = open(os.path.join(ROOT, 'include', 'vpho_hip.h')).read()
+_ELEMENTS = {'float': torch.float32, 'double': torch.float64, 'int': torch.int32, 'unsigned int': torch.int32, 'unsigned char': torch.uint8,
+             'long long': torch.int64, 'void': None}
+_SCALARS = {'int': ctypes.c_int, 'long long': ctypes.c_longlong, 'float': ctypes.c_float, 'double': ctypes.c_double}
+
+
+def _header_prototypes(txt=None):
+    """{function: (return type, [parameter])} by this file's own reading of the header; a parameter is ('scalar', C type, name) or
+    ('ptr', element type, name) with the element type one of _ELEMENTS or a struct name"""
+    txt = open(os.path.join(ROOT, 'include', 'vpho_hip.h')).read() if txt is None else txt
     txt = re.sub(r'/\*.*?\*/', ' ', txt, flags=re.S)
     txt = re.sub(r'typedef\s+struct(?:\s+\w+)?\s*\{.*?\}\s*\w+\s*;', ' ', txt, flags=re.S)
     protos = {}
     for ret, name, args in re.findall(r'\b(int|long long|const char\s*\*|void)\s+(vpho_\w+)\s*\(([^)]*)\)\s*;', txt):
-        kinds = []
+        params = []
         for a in args.split(','):
-            a = ' '.join(a.split())
+            a = ' '.join(a.replace('*', ' * ').split())
             if not a or a == 'void':
                 continue
-            if '*' in a:
-                kinds.append('ptr')
-            elif a.startswith('long long'):
-                kinds.append('longlong')
+            *words, pname = [w for w in a.split() if w != 'const']          # the last word is the parameter's name
+            if words[-1] == '*':
+                params.append(('ptr', ' '.join(words[:-1]), pname))
             else:
-                kinds.append({'int': 'int', 'float': 'float', 'double': 'double', 'unsigned': 'int'}[a.replace('const ', '').split()[0]])
-        protos[name] = kinds
+                params.append(('scalar', ' '.join(words), pname))
+        protos[name] = (' '.join(ret.replace('*', ' *').split()), params)
     return protos
 
 
-def test_every_ctypes_call_site_passes_what_the_header_declares():
-    """Static check of vpho_amd/ops.py against include/vpho_hip.h: each `_call('vpho_x', ...)` passes as many arguments as the prototype
-    has before its trailing stream, and every argument built by a typed wrapper (I / F / LL / c_double / tensor pointer / byref) has the
-    declared kind -- a swapped or missing argument would otherwise only show on the GPU, as a wrong result."""
+def _call_sites():
+    """(file, line, 'call' | 'query', entry point, number of arguments) of every `_call('vpho_x', ...)`, `abi.call(...)` and
+    `abi.query(...)` in vpho_amd/, tests/ and scripts/"""
     import ast
-    protos = _header_prototypes()
-    assert len(protos) >= 80
-    src = open(os.path.join(ROOT, 'vpho_amd', 'ops.py')).read()
-    wrap = {'I': 'int', 'F': 'float', 'LL': 'longlong', '_f32': 'ptr', '_f64': 'ptr', '_i32': 'ptr', '_u8': 'ptr', '_ptr': 'ptr', '_at': 'ptr'}
-
-    def kind(node):
-        if isinstance(node, ast.Call):
-            f = node.func
-            if isinstance(f, ast.Name) and f.id in wrap:
-                return wrap[f.id]
-            if isinstance(f, ast.Attribute) and f.attr in ('byref', 'c_void_p'):
-                return 'ptr'
-            if isinstance(f, ast.Attribute) and f.attr == 'c_double':
-                return 'double'
-            if isinstance(f, ast.Attribute) and f.attr == 'c_longlong':
-                return 'longlong'
-        if isinstance(node, ast.Constant) and node.value is None:
-            return 'ptr'
-        return None                      # built elsewhere (a ctypes array, a local): not judged
-
-    seen, judged = set(), 0
-    for node in ast.walk(ast.parse(src)):
-        if isinstance(node, ast.Call) and isinstance(node.func, ast.Name) and node.func.id == '_call':
-            name = node.args[0].value
-            assert name in protos, f'{name} is called but not declared in include/vpho_hip.h'
-            want = protos[name]
-            assert want and want[-1] == 'ptr', f'{name}: the last parameter must be the stream'
-            got = node.args[1:]
-            if any(isinstance(a, ast.Starred) for a in got):
-                continue
-            assert len(got) == len(want) - 1, f'{name}: {len(got)} arguments at line {node.lineno}, header has {len(want) - 1} before the stream'
-            for i, (a, w) in enumerate(zip(got, want)):
-                k = kind(a)
-                if k is not None:
-                    judged += 1
-                    assert k == w, f'{name} argument {i} at line {node.lineno}: passes {k}, header declares {w}'
-            seen.add(name)
-    assert len(seen) >= 60 and judged >= 600, (len(seen), judged)
-    # entry points called directly (not through _call) declare argtypes: those must spell the prototype
-    from vpho_amd import ops
-    kinds = {ctypes.c_void_p: 'ptr', ctypes.c_int: 'int', ctypes.c_float: 'float', ctypes.c_double: 'double', ctypes.c_longlong: 'longlong'}
-    typed = 0
-    for name, want in protos.items():
-        at = getattr(ops.lib, name).argtypes
-        if at is None:
+    import glob
+    out = []
+    for path in sorted(glob.glob(os.path.join(ROOT, 'vpho_amd', '**', '*.py'), recursive=True) + glob.glob(os.path.join(ROOT, 'tests', '*.py'))
+                       + glob.glob(os.path.join(ROOT, 'scripts', '*.py'))):
+        if os.path.abspath(path) == os.path.abspath(__file__):             # miscounts on purpose, to see the refusal
             continue
-        got = [kinds.get(t, 'ptr' if hasattr(t, 'contents') or hasattr(t, '_type_') and isinstance(t._type_, type) else None) for t in at]
-        assert got == want, f'{name}.argtypes {got} vs header {want}'
-        typed += 1
-    assert typed >= 4
-    for node in ast.walk(ast.parse(src)):                 # ... and every direct call has argtypes behind it or typed wrappers only
-        if (isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and isinstance(node.func.value, ast.Name)
-                and node.func.value.id == 'lib' and node.func.attr.startswith('vpho_') and node.func.attr in protos):
-            name = node.func.attr
-            if getattr(ops.lib, name).argtypes is None:
-                assert len(node.args) == len(protos[name]), f'{name}: {len(node.args)} arguments at line {node.lineno}, header has {len(protos[name])}'
-                for i, (a, w) in enumerate(zip(node.args, protos[name])):
-                    k = kind(a) or ('ptr' if isinstance(a, ast.Call) and isinstance(a.func, ast.Name) and a.func.id == '_stream' else None)
-                    assert k == w, f'{name} argument {i} at line {node.lineno}: passes {k} without argtypes, header declares {w}'
+        for node in ast.walk(ast.parse(open(path).read())):
+            if not isinstance(node, ast.Call):
+                continue
+            f = node.func
+            what = f.id if isinstance(f, ast.Name) else f.attr if isinstance(f, ast.Attribute) else None
+            if isinstance(f, ast.Attribute) and what in ('call', 'query'):
+                owner = f.value.id if isinstance(f.value, ast.Name) else f.value.attr if isinstance(f.value, ast.Attribute) else None
+                if owner != 'abi':
+                    continue
+            elif what != '_call':
+                continue
+            if not (node.args and isinstance(node.args[0], ast.Constant) and isinstance(node.args[0].value, str)):
+                assert os.path.basename(path) == 'abi.py', f'{path}:{node.lineno}: the entry point must be a string literal'
+                continue
+            assert not any(isinstance(a, ast.Starred) for a in node.args) and not node.keywords, \
+                f'{path}:{node.lineno}: a starred argument list cannot be counted against the header: spell the arguments out'
+            out.append((os.path.relpath(path, ROOT), node.lineno, 'query' if what == 'query' else 'call', node.args[0].value, len(node.args) - 1))
+    return out
+
+
+def test_every_call_site_names_a_declared_function_and_passes_the_declared_number_of_arguments():
+    """The static half of the binding's check, over vpho_amd/, tests/ and scripts/: each `_call('vpho_x', ...)` / `abi.call` passes as many
+    arguments as the prototype has before its trailing stream, each `abi.query` as many as the prototype has, and none hides its
+    arguments behind a star -- a missing argument would otherwise only show when that line runs."""
+    protos = _header_prototypes()
+    assert len(protos) == ENTRY_POINTS
+    sites = _call_sites()
+    for path, line, how, name, n in sites:
+        assert name in protos, f'{path}:{line}: {name} is called but not declared in include/vpho_hip.h'
+        params = protos[name][1]
+        streamed = bool(params) and params[-1] == ('ptr', 'void', 'stream')
+        if how == 'call':
+            assert streamed, f'{path}:{line}: {name} takes no stream: abi.query'
+            assert n == len(params) - 1, f'{path}:{line}: {name} with {n} arguments, the header has {len(params) - 1} before the stream'
+        else:
+            assert n == len(params), f'{path}:{line}: {name} with {n} arguments, the header has {len(params)}'
+    # ops.py reaches every entry point but the two abi.py calls itself and the two aliases that have no wrapper (tests/test_leaf_coverage_cpu.py)
+    in_ops = {name for path, _, _, name, _ in sites if path == os.path.join('vpho_amd', 'ops.py')}
+    assert in_ops == set(protos) - {'vpho_last_error', 'vpho_abi_version', 'vpho_mha_f32', 'vpho_mha_bwd_f32'}, sorted(in_ops ^ set(protos))
+    assert {'vpho_mha_f32', 'vpho_mha_bwd_f32'} <= {name for path, _, _, name, _ in sites if path.startswith('tests')}
+    # nothing in the binding's one user goes round abi.call / abi.query to the library
+    src = open(os.path.join(ROOT, 'vpho_amd', 'ops.py')).read()
+    assert re.findall(r'\blib\.(vpho_\w+)', src) in ([], ['vpho_last_error']) and 'argtypes' not in src and 'restype' not in src
+
+
+def test_argtypes_and_restype_of_every_entry_point_are_the_header_s():
+    """Every one of the 134 functions is typed, from the header, element types included: what abi.py set on the loaded library against
+    this file's own reading of include/vpho_hip.h.  (Before abi.py four functions had argtypes and a pointer was just 'a pointer'.)"""
+    from vpho_amd import abi
+    protos = _header_prototypes()
+    assert len(protos) == ENTRY_POINTS
+    rets = {'int': ctypes.c_int, 'long long': ctypes.c_longlong, 'const char *': ctypes.c_char_p}
+    structs = set(_header_structs())
+    n_ptr = n_stream = 0
+    for name, (ret, params) in protos.items():
+        fn = getattr(abi.lib, name)
+        assert fn.restype is rets[ret], f'{name}: restype {fn.restype}, header {ret}'
+        assert fn.argtypes is not None and len(fn.argtypes) == len(params), f'{name}: {fn.argtypes} vs {params}'
+        for i, ((kind, what, pname), at) in enumerate(zip(params, fn.argtypes)):
+            where = f'{name} parameter {i} ({what} {pname})'
+            if kind == 'scalar':
+                assert at is _SCALARS[what], f'{where}: {at}'
+            elif (kind, what, pname) == ('ptr', 'void', 'stream'):
+                # the stream is the one pointer no caller passes: abi.call appends torch's integer handle itself
+                assert at is ctypes.c_void_p and i == len(params) - 1, f'{where}: {at}'
+                n_stream += 1
+            elif what in structs:
+                assert at is ctypes.POINTER(abi.struct(what)), f'{where}: {at}'
+            else:
+                assert issubclass(at, abi._Pointer) and at.element == what and at.dtype == _ELEMENTS[what], f'{where}: {at} {at.element} {at.dtype}'
+                n_ptr += 1
+    # every entry point launches on a stream but the version / error / profiling queries and the twelve size queries
+    host_only = [n for n in protos if n in ('vpho_last_error', 'vpho_abi_version') or n.startswith('vpho_prof_') or n.endswith('_bytes')]
+    assert n_stream == ENTRY_POINTS - len(host_only) == 118, (n_stream, host_only)
+    assert n_ptr >= 4 * n_stream, n_ptr                      # a launch reads and writes tensors: the element types judged above are the bulk
+
+
+class _Tensor:
+    """what a converter looks at of a tensor"""
+    def __init__(self, dtype, cuda=True, contiguous=True, address=0x7F0012345000):
+        self.dtype, self.is_cuda, self._c, self._a = dtype, cuda, contiguous, address
+
+    def is_contiguous(self):
+        return self._c
+
+    def data_ptr(self):
+        return self._a
+
+
+def test_the_converters_refuse_what_the_static_check_used_to_judge_and_more():
+    """The run-time refusals that replace the static per-argument judgement of the I / F / LL / _f32 ... wrappers (those are gone):
+      * 'a tensor pointer where the header has a pointer' -> the converter of the declared ELEMENT type: a wrong dtype, a CPU tensor, a
+        non-contiguous tensor and a bare int are refused (the static check knew 'ptr' only, and only for arguments built by a wrapper);
+      * 'I(...) where the header has int, F(...) where it has float' -> c_int refuses a float, c_float / c_double take an int, c_int takes
+        numpy integers and bool (as the wrappers did);
+      * 'byref(...) is a pointer' -> POINTER(mirror) refuses byref of another struct, a data pointer refuses byref / an array of another
+        element type;
+      * 'as many arguments as the header has' (static, kept above) -> abi.call / abi.query count again at run time, since ctypes itself
+        lets surplus arguments through."""
+    import pytest
+    from vpho_amd import abi
+    dtypes = [torch.float32, torch.float64, torch.int32, torch.uint8, torch.int64, torch.float16, torch.bool, torch.int16]
+    elements = {'float': ctypes.c_float, 'double': ctypes.c_double, 'int': ctypes.c_int, 'unsigned int': ctypes.c_uint,
+                'unsigned char': ctypes.c_ubyte, 'long long': ctypes.c_longlong}
+    assert set(elements) | {'void'} == set(abi._POINTERS) == set(_ELEMENTS)
+    for el, ctype in elements.items():
+        conv = abi._POINTERS[el]
+        got = conv.from_param(_Tensor(_ELEMENTS[el]))
+        assert isinstance(got, ctypes.c_void_p) and got.value == 0x7F0012345000
+        assert conv.from_param(None) is None
+        off = ctypes.c_void_p(0x7F0012345010)
+        assert conv.from_param(off) is off
+        for wrong in dtypes:
+            if wrong != _ELEMENTS[el]:
+                with pytest.raises(abi.VphoError, match=f'expected {_ELEMENTS[el]}, got {wrong}'.replace('.', r'\.')):
+                    conv.from_param(_Tensor(wrong))
+        with pytest.raises(abi.VphoError, match='GPU tensors only'):
+            conv.from_param(_Tensor(_ELEMENTS[el], cuda=False))
+        with pytest.raises(abi.VphoError, match='contiguous'):
+            conv.from_param(_Tensor(_ELEMENTS[el], contiguous=False))
+        for bare in (0x7F0012345000, 0, 1.0, 'x'):
+            with pytest.raises(abi.VphoError, match='expected'):
+                conv.from_param(bare)
+        arr, one = (ctype * 3)(), ctype()
+        assert conv.from_param(arr) is arr and conv.from_param(ctypes.byref(one))._obj is one
+        other = ctypes.c_double if ctype is not ctypes.c_double else ctypes.c_float
+        with pytest.raises(abi.VphoError, match='expected'):
+            conv.from_param((other * 3)())
+        with pytest.raises(abi.VphoError, match='expected'):
+            conv.from_param(ctypes.byref(other()))
+    void = abi._POINTERS['void']
+    for any_dtype in dtypes:
+        assert void.from_param(_Tensor(any_dtype)).value == 0x7F0012345000
+    with pytest.raises(abi.VphoError, match='GPU tensors only'):
+        void.from_param(_Tensor(torch.uint8, cuda=False))
+    with pytest.raises(abi.VphoError, match='contiguous'):
+        void.from_param(_Tensor(torch.uint8, contiguous=False))
+    with pytest.raises(abi.VphoError, match='expected'):
+        void.from_param(4096)
+    # scalars, through a host-only function and through the types the header gives float and double parameters
+    eight = abi.query('vpho_bn_workspace_bytes', 8)
+    assert eight > 0 and abi.query('vpho_bn_workspace_bytes', np.int64(8)) == eight == abi.query('vpho_bn_workspace_bytes', np.int32(8))
+    assert abi.query('vpho_bn_workspace_bytes', True) == abi.query('vpho_bn_workspace_bytes', 1)
+    with pytest.raises(abi.VphoError, match=r'vpho_bn_workspace_bytes\(C\)'):
+        abi.query('vpho_bn_workspace_bytes', 8.0)
+    ode = abi.lib.vpho_ode_sample.argtypes
+    assert abi.lib.vpho_score_eval.argtypes[5] is ctypes.c_float and ode[5] is ctypes.c_double
+    assert ode[5].from_param(3) is not None and abi.lib.vpho_score_eval.argtypes[5].from_param(3) is not None      # an int for double / float
+    with pytest.raises(TypeError):
+        ode[7].from_param(50.0)                                                                                     # a float for int
+    # struct pointers
+    from vpho_amd import ops
+    with pytest.raises(abi.VphoError, match=r'vpho_score_workspace_bytes\(w\)'):
+        abi.query('vpho_score_workspace_bytes', ctypes.byref(ops.OdeStats()), 1, 1)
+    with pytest.raises(TypeError):
+        ode[16].from_param(ctypes.byref(ops.ScoreWeights()))
+    assert ode[16].from_param(ctypes.byref(ops.OdeStats())) is not None
+    # the count, with the function's name, before anything is touched (no GPU here: a launch would fail differently)
+    x = _Tensor(torch.float32)
+    with pytest.raises(abi.VphoError, match=r'vpho_maxpool_nhwc_f32: 8 arguments, .* 9 before the stream'):
+        abi.call('vpho_maxpool_nhwc_f32', x, 1, 4, 4, 4, 2, 2, 0)
+    with pytest.raises(abi.VphoError, match=r'vpho_maxpool_nhwc_f32: 10 arguments, .* 9 before the stream'):
+        abi.call('vpho_maxpool_nhwc_f32', x, 1, 4, 4, 4, 2, 2, 0, x, x)
+    with pytest.raises(abi.VphoError, match=r'vpho_bn_workspace_bytes: 2 arguments'):
+        abi.query('vpho_bn_workspace_bytes', 8, 8)
+    with pytest.raises(abi.VphoError, match=r'vpho_bn_workspace_bytes: 0 arguments'):
+        abi.query('vpho_bn_workspace_bytes')
+
+
+def test_the_header_parser_refuses_what_it_does_not_know():
+    """abi.parse_header skips nothing silently: an unknown element type, an unknown scalar, an unknown return type, a prototype without
+    VPHO_API and a stray statement each raise and name the line"""
+    import pytest
+    from vpho_amd import abi
+    good = 'typedef struct { const float* x; int n; } vpho_t;\nVPHO_API int vpho_f(const vpho_t* t, const float* x, long long n, void* stream);\n'
+    structs, protos = abi.parse_header(good)
+    assert structs == {'vpho_t': [('x', ctypes.c_void_p), ('n', ctypes.c_int)]}
+    assert protos['vpho_f'][1] == [('t', 'vpho_t', True), ('x', 'float', True), ('n', 'long long', False), ('stream', 'void', True)]
+    for bad, line in (('VPHO_API int vpho_f(const short* x, void* stream);', 3), ('VPHO_API int vpho_f(unsigned n, void* stream);', 3),
+                      ('VPHO_API int vpho_f(size_t n);', 3), ('VPHO_API float vpho_f(int n);', 3), ('int vpho_f(int n);', 3),
+                      ('VPHO_API int vpho_f(const vpho_other* t);', 3), ('typedef struct { short n; } vpho_u;', 3), ('static int x = 3;', 3),
+                      ('VPHO_API int vpho_f(float** x);', 3)):
+        with pytest.raises(abi.VphoError, match=r'vpho_hip\.h:%d: ' % line):
+            abi.parse_header(good + bad + '\n')

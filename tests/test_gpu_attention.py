@@ -139,7 +139,7 @@ def test_alias_vpho_mha_f32_gives_the_wrappers_bits(case):
     S, B, E, nhead = case[:4]
     qkv = _dev(_reference(case, False)[0])
     out = torch.full((S, B, E), R.SENT, device='cuda')
-    ops._call('vpho_mha_f32', ops._f32(qkv), ops.I(S), ops.I(B), ops.I(E), ops.I(nhead), ops._f32(out))
+    ops._call('vpho_mha_f32', qkv, S, B, E, nhead, out)
     assert R.bits_equal(out, ops.mha(qkv, S, B, E, nhead))
 
 
@@ -150,7 +150,7 @@ def test_alias_vpho_mha_bwd_f32_gives_the_wrappers_bits(case):
     S, B, E, nhead = case[:4]
     qkv, d_out, mask = (_dev(t) for t in _reference(case, True)[:3])
     dqkv = torch.full((S * B, 3 * E), R.SENT, device='cuda')
-    ops._call('vpho_mha_bwd_f32', ops._f32(qkv), ops._f32(d_out), ops.I(S), ops.I(B), ops.I(E), ops.I(nhead), ops._f32(mask), ops._f32(dqkv))
+    ops._call('vpho_mha_bwd_f32', qkv, d_out, S, B, E, nhead, mask, dqkv)
     assert R.bits_equal(dqkv, ops.mha_bwd(qkv, d_out, S, B, E, nhead, drop=mask))
 
 
@@ -166,18 +166,18 @@ def test_refusals_name_their_limit_and_launch_nothing():
     E, nhead = 24, 2
     d65 = sent(65 * 1, 3 * E)
     with pytest.raises(ops.VphoError, match=r'65 exceeds the 64 positions'):
-        ops._call('vpho_mha_bwd_f32', ops._f32(z(65, 3 * E)), ops._f32(z(65, E)), ops.I(65), ops.I(1), ops.I(E), ops.I(nhead), ops._f32(None), ops._f32(d65))
+        ops._call('vpho_mha_bwd_f32', z(65, 3 * E), z(65, E), 65, 1, E, nhead, None, d65)
     with pytest.raises(ops.VphoError, match=r'head_dim 6 is not a multiple of 4'):
         ops.mha_bwd(z(5, 36), z(5, 12), 5, 1, 12, 2)
     d6 = sent(5, 36)
     with pytest.raises(ops.VphoError, match=r'head_dim 6 is not a multiple of 4'):
-        ops._call('vpho_mha_bwd_ws_f32', ops._f32(z(5, 36)), ops._f32(z(5, 12)), ops.I(5), ops.I(1), ops.I(12), ops.I(2), ops._f32(None), ops._f32(d6), ops._ptr(None))
+        ops._call('vpho_mha_bwd_ws_f32', z(5, 36), z(5, 12), 5, 1, 12, 2, None, d6, None)
     with pytest.raises(ops.VphoError, match=r'at most 1024 positions'):
         ops.mha_bwd(z(1025, 3 * 16), z(1025, 16), 1025, 1, 16, 2)
     d1025, ws = sent(1025, 48), torch.zeros(16, dtype=torch.uint8, device='cuda')
     with pytest.raises(ops.VphoError, match=r'1025 exceeds the 1024 positions'):
-        ops._call('vpho_mha_bwd_ws_f32', ops._f32(z(1025, 48)), ops._f32(z(1025, 16)), ops.I(1025), ops.I(1), ops.I(16), ops.I(2), ops._f32(None), ops._f32(d1025),
-                  ops._ptr(ws))
+        ops._call('vpho_mha_bwd_ws_f32', z(1025, 48), z(1025, 16), 1025, 1, 16, 2, None, d1025,
+                  ws)
     with pytest.raises(ops.VphoError, match=r'dropout mask needs head_dim % 4 == 0 and head_dim <= 256 \(got 6\)'):
         ops.mha(z(5, 36), 5, 1, 12, 2, drop=torch.ones(2, 5, 5, device='cuda'))
     with pytest.raises(ops.VphoError, match=r'head_dim 6 is served for sequences .* up to 256 only; got 300'):

@@ -146,7 +146,7 @@ def test_empty_list_launches_nothing():
     assert lst.n == 0 and lst.blocks == 0 and lst.table is None
     lst.update(0.5)
     # the entry point itself: no tensors = success without a launch; a negative count or a missing table = the argument error
-    call = lambda table, n, blocks: ops.lib.vpho_ema_multi_f32(table, ops.I(n), ops.LL(blocks), ops.F(0.5), None)
+    call = lambda table, n, blocks: ops.lib.vpho_ema_multi_f32(table, n, blocks, 0.5, None)
     assert call(None, 0, 0) == 0
     for table, n, blocks in ((None, 1, 1), (None, -1, 0), (None, 0, -1)):
         assert call(table, n, blocks) != 0

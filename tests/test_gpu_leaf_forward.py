@@ -234,8 +234,8 @@ def test_argument_guards_raise_and_launch_nothing():
     tok = sent(1, 65, 512)
     z = torch.zeros(1, 8, 8, 256, device=dev)
     with pytest.raises(ops.VphoError):                               # bs > 5000: by argument, the buffers are never touched
-        ops._call('vpho_cross_tokens_f32', ops._f32(z), ops._f32(z), ops._f32(torch.zeros(1, 512, device=dev)),
-                  ops._f32(torch.zeros(1, 512, device=dev)), ops.I(5001), ops._f32(tok))
+        ops._call('vpho_cross_tokens_f32', z, z, torch.zeros(1, 512, device=dev),
+                  torch.zeros(1, 512, device=dev), 5001, tok)
     hm = sent(2, 1, 1, 3)
     box = torch.tensor([[0.0, 0.0, 10.0, 10.0]] * 2, device=dev)
     with pytest.raises(ops.VphoError):

@@ -196,8 +196,8 @@ def test_far_hand_odd_sizes_and_errors(assets):
     # sd / inside may be NULL in the C ABI: the per-image result is the same
     per_ref = H(near, rt, [1, 2, 3])
     per2 = torch.empty_like(per_ref)
-    ops._call('vpho_hand_obj_penetration_f64', ops.C.byref(H.c), ops._f32(near), ops.I(3), ops.I(near.shape[1]), ops._f64(rt),
-              ops._i32(H.obj_ids(list(H.names[1:4]))), ops.C.c_double(0.005), None, None, ops._f64(per2))
+    ops._call('vpho_hand_obj_penetration_f64', ops.C.byref(H.c), near, 3, near.shape[1], rt,
+              H.obj_ids(list(H.names[1:4])), 0.005, None, None, per2)
     assert torch.equal(per2, per_ref)
 
 

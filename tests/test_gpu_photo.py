@@ -430,11 +430,10 @@ def test_a_refusal_of_the_c_side_is_read_from_the_one_error_slot():
     minv = torch.zeros((1, 6), dtype=torch.float64, device='cuda')
     lev = torch.full((1, 4, 4, 3), 77, dtype=torch.uint8, device='cuda')
     out = torch.full((1, 3, 4, 4), 12345.0, device='cuda')
-    I = ops.I
     with pytest.raises(ops.VphoError, match=r'vpho_photo_levels_u8: bad size \(n 1, H 4, W 4, P 0\)'):
-        ops._call('vpho_photo_levels_u8', ops._u8(frames), I(1), I(4), I(4), ops._f64(minv), I(0), ops._u8(lev))
+        ops._call('vpho_photo_levels_u8', frames, 1, 4, 4, minv, 0, lev)
     with pytest.raises(ops.VphoError, match=r'vpho_frame_patch_f32: bad size \(n 1, H 4, W 4, P 0\)') as e:
-        ops._call('vpho_frame_patch_f32', ops._u8(frames), I(1), I(4), I(4), ops._f64(minv), None, None, None, None, I(0), ops._f32(out))
+        ops._call('vpho_frame_patch_f32', frames, 1, 4, 4, minv, None, None, None, None, 0, out)
     assert 'photo' not in str(e.value)
     torch.cuda.synchronize()
     assert bool((lev == 77).all()) and bool((out == 12345.0).all())

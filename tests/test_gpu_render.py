@@ -217,8 +217,8 @@ def test_refusals_come_before_any_launch(monkeypatch):
     assert calls == []
     # the library refuses the size too, should a caller get past the wrapper
     with pytest.raises(ops.VphoError, match='bad size'):
-        real('vpho_mesh_raster_f32', ops.C.byref(mr.table), ops._f32(_dev(v[None])), ops.I(4), ops._i32(_dev(np.zeros(1, np.int32))), ops._f64(_dev(K[None])),
-             ops.I(1), ops.I(2049), ops.I(8), ops.I(2), ops.C.c_double(0.01), None, None, None, None, None)
+        real('vpho_mesh_raster_f32', ops.C.byref(mr.table), _dev(v[None]), 4, _dev(np.zeros(1, np.int32)), _dev(K[None]),
+             1, 2049, 8, 2, 0.01, None, None, None, None, None)
     mr.raster(_dev(v[None]), [0], _dev(K[None]), 2048, 3)                         # the largest side is served
     torch.cuda.synchronize()
     assert calls == ['vpho_mesh_raster_f32']

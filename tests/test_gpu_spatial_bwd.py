@@ -242,8 +242,8 @@ def test_argument_guards_raise_and_launch_nothing():
     with pytest.raises(ops.VphoError):
         ops.align_heatmap_bwd(torch.zeros(2, 1, 1, 3, device=dev), box, box)     # size <= 1 through the wrapper
     with pytest.raises(ops.VphoError):                                           # and with a destination of our own to look at
-        ops._call('vpho_align_heatmap_bwd_nhwc_f32', ops._f32(torch.zeros(2, 1, 1, 3, device=dev)), ops.I(2), ops.I(1), ops.I(3), ops._f32(box), ops._f32(box),
-                  ops._u8(None), ops._f32(dhm))
+        ops._call('vpho_align_heatmap_bwd_nhwc_f32', torch.zeros(2, 1, 1, 3, device=dev), 2, 1, 3, box, box,
+                  None, dhm)
     df = torch.full((2, 4, 4, 8), SENT, device=dev)
     dy = torch.zeros(2, 2, 2, 8, device=dev)
     with pytest.raises(ops.VphoError):

@@ -210,14 +210,14 @@ def test_edge_cases(meter):
     out = torch.zeros((1, 2), dtype=torch.float64, device='cuda')
     ws = torch.empty(1 << 16, dtype=torch.uint8, device='cuda')
     ids = meter.obj_ids([meter.names[0]])
-    call = lambda F_, pitch: ops._call('vpho_hand_obj_intersection_f64', ops.C.byref(meter.c), ops.C.byref(sol['c']), ops._i32(meter.hand_faces), ops.I(F_),
-                                      ops._f32(verts), ops.I(1), ops.I(verts.shape[1]), ops._f64(rt), ops._i32(ids), ops.C.c_double(pitch), ops._f64(out),
-                                      None, ops._ptr(ws), ops.LL(ws.numel()))
+    call = lambda F_, pitch: ops._call('vpho_hand_obj_intersection_f64', ops.C.byref(meter.c), ops.C.byref(sol['c']), meter.hand_faces, F_,
+                                      verts, 1, verts.shape[1], rt, ids, pitch, out,
+                                      None, ws, ws.numel())
     with pytest.raises(ops.VphoError, match='without faces'):
         call(0, H_PITCH)
     with pytest.raises(ops.VphoError, match='pitch'):
         call(int(meter.hand_faces.shape[0]), 0.0)
-    assert ops.lib.vpho_hand_obj_intersection_workspace_bytes(ops.I(1), ops.I(0)) == -1
+    assert ops.lib.vpho_hand_obj_intersection_workspace_bytes(1, 0) == -1
     # a device id the host cannot check, and a hand vertex that is not a number: NaN rows, the other image untouched
     two_v = torch.from_numpy(np.stack([G['pair0_verts_cam'], G['pair0_verts_cam']])).cuda()
     two_rt = torch.from_numpy(G['rt'][[0, 0]]).cuda()

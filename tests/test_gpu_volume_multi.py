@@ -181,8 +181,8 @@ def test_edge_cases(fix):
     per, table = torch.zeros((3, 5, 2), dtype=torch.float64, device='cuda'), torch.zeros((3, 6), dtype=torch.float64, device='cuda')
     dev_ids = m.obj_ids([m.names[i] for i in fix['ids']])
     call = lambda n, S, F_, pitch: ops._call('vpho_hand_obj_intersection_multi_f64', ops.C.byref(m.c), ops.C.byref(sol['c']), ops.C.byref(cols['c']),
-                                             ops._i32(m.hand_faces), ops.I(F_), ops._f32(verts), ops.I(n), ops.I(S), ops.I(verts.shape[2]), ops._f64(rt),
-                                             ops._i32(dev_ids), ops.C.c_double(pitch), ops._f64(per), ops._f64(table), None, None, ops.LL(0))
+                                             m.hand_faces, F_, verts, n, S, verts.shape[2], rt,
+                                             dev_ids, pitch, per, table, None, None, 0)
     F_ = int(m.hand_faces.shape[0])
     with pytest.raises(ops.VphoError, match='hypotheses'):
         call(3, 0, F_, H_PITCH)
@@ -197,8 +197,8 @@ def test_edge_cases(fix):
     call(3, 5, F_, H_PITCH)                                                     # and the raw call with a NULL workspace is the wrapper's
     assert _bytes_equal(per, fix['per']) and _bytes_equal(table, fix['table'])
     wb = ops.lib.vpho_hand_obj_intersection_multi_workspace_bytes
-    assert wb(ops.I(64), ops.I(100), ops.I(1552)) == 0 and wb(ops.I(1), ops.I(0), ops.I(4)) == -1 and wb(ops.I(1), ops.I(1), ops.I(0)) == -1
-    assert wb(ops.I(70000), ops.I(70000), ops.I(4)) == -1
+    assert wb(64, 100, 1552) == 0 and wb(1, 0, 4) == -1 and wb(1, 1, 0) == -1
+    assert wb(70000, 70000, 4) == -1
     with pytest.raises(ops.VphoError, match='at most'):
         m.volume_multi(verts[:1, :1].expand(50000, 50000, -1, -1), rt[:1, :1].expand(50000, 50000, -1, -1), fix['ids'], H_PITCH)       # views: no memory
 

@@ -182,7 +182,7 @@ def test_header_declares_the_raster_entry_points_at_abi_13():
     from vpho_amd import ops
     for name in ('vpho_mesh_raster_f32', 'vpho_render_overlay_u8', 'vpho_mesh_raster_bytes'):
         assert hasattr(ops.lib, name), name
-    assert ops.lib.vpho_mesh_raster_bytes(ops.I(3), ops.I(10)) == 3 * 10 * 56 and ops.lib.vpho_mesh_raster_bytes(ops.I(-1), ops.I(1)) == -1
+    assert ops.lib.vpho_mesh_raster_bytes(3, 10) == 3 * 10 * 56 and ops.lib.vpho_mesh_raster_bytes(-1, 1) == -1
 
 
 def test_ctypes_structures_of_the_raster_mirror_the_header():

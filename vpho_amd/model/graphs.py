@@ -7,6 +7,7 @@ of the feature path drops from ~3 ms of Python/ctypes per batch to ~0.1 ms, the 
 order (bit-identical outputs).  Inputs are copied into buffers owned by the graph; outputs are the graph's own tensors and are
 overwritten by the next replay of the same entry -- callers clone what must outlive the step.
 """
+import gc
 import threading
 
 import torch
@@ -62,7 +63,18 @@ class GraphedCall:
                 self.fn(static)
             side.synchronize()
             graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph, stream=side, capture_error_mode='thread_local'):
-                out = self.fn(static)
+            # No garbage collection while the stream captures: a dead reference cycle that owns device memory (an earlier GraphedCall's
+            # graph and its pool) would be freed in the middle of the capture, which the runtime refuses -- from a destructor, so the
+            # process aborts.  torch.cuda.graph used to collect on entry; since it stopped, when a collection falls is a matter of
+            # how many objects the launches in between happen to allocate.
+            gc.collect()
+            collecting = gc.isenabled()
+            gc.disable()
+            try:
+                with torch.cuda.graph(graph, stream=side, capture_error_mode='thread_local'):
+                    out = self.fn(static)
+            finally:
+                if collecting:
+                    gc.enable()
             cur.wait_stream(side)
         return static, graph, out

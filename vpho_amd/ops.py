@@ -1,89 +1,27 @@
-"""ctypes binding of the C ABI in ``include/vpho_hip.h`` (``vpho_amd/libvpho_hip.so``).
+"""Tensor-level wrappers of the C ABI in ``include/vpho_hip.h`` (``vpho_amd/libvpho_hip.so``).
 
-Thin by design: tensors in, raw device pointers + the current HIP stream out.  There is NO fallback: importing this
-module without the built extension raises, and every op checks that its tensors live on a GPU.
+Thin by design: tensors in, plain values to ``abi.call`` out.  Every C type -- struct mirrors, argument and return types -- comes from the
+header through ``vpho_amd/abi.py``; no call site here wraps an argument.  There is NO fallback: importing this module without the built
+extension raises, and every op checks that its tensors live on a GPU.
 """
-import ctypes as C
+import ctypes as C                      # host-side values only: byref, host arrays, struct construction
 import os
 
 import torch
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get('VPHO_HIP_LIB') or os.path.join(_HERE, 'libvpho_hip.so')   # override: A/B kernel builds
+from . import abi
+from .abi import ABI_VERSION, LIB_PATH, VphoError, lib  # noqa: F401
 
-if not os.path.exists(LIB_PATH):
-    raise ImportError(f'{LIB_PATH} is missing: build the HIP extension first (python -m vpho_amd.build or '
-                      f'__graft_entry__.build()); vpho_amd has no CPU fallback')
-lib = C.CDLL(LIB_PATH)
-lib.vpho_last_error.restype = C.c_char_p
-lib.vpho_abi_version.restype = C.c_int
-ABI_VERSION = 14                        # include/vpho_hip.h; a stale library must not be found out by a missing symbol halfway through a run
-if lib.vpho_abi_version() != ABI_VERSION:
-    raise ImportError(f'{LIB_PATH} implements ABI version {lib.vpho_abi_version()}, this binding expects {ABI_VERSION}: rebuild the '
-                      f'extension (python -m vpho_amd.build --force)')
-lib.vpho_obj_metrics_workspace_bytes.restype = C.c_longlong
-lib.vpho_obj_metrics_multi_workspace_bytes.restype = C.c_longlong
-lib.vpho_bn_workspace_bytes.restype = C.c_longlong
-lib.vpho_conv2d_wgrad_workspace_bytes.restype = C.c_longlong
-lib.vpho_mha_bwd_workspace_bytes.restype = C.c_longlong
-lib.vpho_grad_sqnorm_workspace_bytes.restype = C.c_longlong
-lib.vpho_infer_record_bytes.restype = C.c_longlong
-lib.vpho_hand_obj_intersection_workspace_bytes.restype = C.c_longlong
-lib.vpho_hand_obj_intersection_multi_workspace_bytes.restype = C.c_longlong
+_call = abi.call                        # a module-level name: tests wrap it to take the census of a step's launches
 
 
-class VphoError(RuntimeError):
-    pass
-
-
-def _check(rc):
-    if rc != 0:
-        raise VphoError(lib.vpho_last_error().decode())
-
-
-def _ptr(t, dtype=None):
-    if t is None:
-        return None
-    if not t.is_cuda:
-        raise VphoError('vpho_amd ops take GPU tensors only (no CPU path)')
-    if dtype is not None and t.dtype != dtype:
-        raise VphoError(f'expected {dtype}, got {t.dtype}')
-    if not t.is_contiguous():
-        raise VphoError('expected a contiguous tensor')
-    return C.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+def _f32p(t):
+    """descriptor fields and table records: the checked address of an fp32 tensor"""
+    return abi.addr(t, torch.float32)
 
 
 # ----------------------------------------------------------------------------------------------- conv / linear
-class ConvDesc(C.Structure):
-    _fields_ = [('x', C.c_void_p), ('w', C.c_void_p), ('bias', C.c_void_p), ('in_scale', C.c_void_p),
-                ('in_shift', C.c_void_p), ('res', C.c_void_p), ('y', C.c_void_p),
-                ('N', C.c_int), ('H', C.c_int), ('W', C.c_int), ('Cin', C.c_int), ('x_ld', C.c_int),
-                ('Cout', C.c_int), ('KH', C.c_int), ('KW', C.c_int), ('stride', C.c_int), ('pad_y', C.c_int),
-                ('pad_x', C.c_int), ('OH', C.c_int), ('OW', C.c_int),
-                ('y_sn', C.c_longlong), ('y_sy', C.c_longlong), ('y_sx', C.c_longlong),
-                ('r_sn', C.c_longlong), ('r_sy', C.c_longlong), ('r_sx', C.c_longlong),
-                ('in_slope', C.c_float), ('out_slope', C.c_float),
-                ('w_ld', C.c_int), ('splits', C.c_int), ('x_split', C.c_longlong), ('w_split', C.c_longlong), ('y_split', C.c_longlong),
-                ('gate', C.c_void_p), ('gate_slope', C.c_float),
-                ('row_map', C.c_void_p), ('row_count', C.c_void_p), ('rows_hint', C.c_int), ('rows_scatter', C.c_int),
-                ('w_planes', C.c_void_p), ('plane_terms', C.c_int),
-                ('res_up', C.c_void_p), ('ru_H', C.c_int), ('ru_W', C.c_int), ('ru_ld', C.c_int),
-                ('x2', C.c_void_p), ('Cin2', C.c_int), ('x2_ld', C.c_int), ('stride2', C.c_int), ('H2', C.c_int), ('W2', C.c_int),
-                ('groups', C.c_int), ('x_group', C.c_longlong), ('w_group', C.c_longlong), ('bias_group', C.c_longlong), ('y_group', C.c_longlong),
-                ('res_group', C.c_longlong), ('x2_group', C.c_longlong), ('pre_group', C.c_longlong), ('ru_group', C.c_longlong),
-                ('stats', C.c_void_p), ('stats_rows', C.c_void_p), ('stats_cap', C.c_int),
-                ('bn_x', C.c_void_p), ('bn_mean', C.c_void_p), ('bn_invstd', C.c_void_p), ('bn_gamma', C.c_void_p), ('bn_beta', C.c_void_p)]
-
-
-lib.vpho_conv2d_nhwc_f32.argtypes = [C.POINTER(ConvDesc), C.c_void_p]
-
-
-def _addr(t):
-    return None if t is None else t.data_ptr()
+ConvDesc = abi.struct('vpho_conv_desc')
 
 
 FUSE_BN = os.environ.get('VPHO_TRAIN_FUSE_BN', '1') != '0'     # A/B aid: 0 = every train-mode BatchNorm runs its own reduction pass
@@ -190,15 +128,13 @@ def conv2d_nhwc(x, w, bias=None, *, kh=1, kw=1, stride=1, pad=0, pad_y=None, pad
     else:
         OH, OW = out_hw
     d = ConvDesc()
-    d.x, d.w, d.bias = _addr(x), _addr(w), _addr(bias)
-    d.in_scale, d.in_shift, d.res = _addr(in_scale), _addr(in_shift), _addr(res)
-    for t in (x, w, bias, in_scale, in_shift, res):
-        _ptr(t, torch.float32)
+    d.x, d.w, d.bias = _f32p(x), _f32p(w), _f32p(bias)
+    d.in_scale, d.in_shift, d.res = _f32p(in_scale), _f32p(in_shift), _f32p(res)
     if rows is not None:
         assert out_view is None and res is None and gate is None and rows.shape == (N, OH, OW) and (res_up is None or rows_scatter)
         if out is None:
             out = torch.empty((N, OH, OW, cout) if rows_scatter else (N * OH * OW, cout), device=x.device, dtype=torch.float32)
-        _ptr(out, torch.float32)
+        _f32p(out)
         ld = out.shape[-1]
         d.y, d.y_sx, d.y_sy, d.y_sn = out.data_ptr(), ld, (ld * OW if rows_scatter else 0), (ld * OW * OH if rows_scatter else 0)
         d.rows_scatter = 1 if rows_scatter else 0
@@ -207,32 +143,32 @@ def conv2d_nhwc(x, w, bias=None, *, kh=1, kw=1, stride=1, pad=0, pad_y=None, pad
         ret = out
     elif out_view is not None:
         yt, d.y_sn, d.y_sy, d.y_sx, off = out_view
-        _ptr(yt, torch.float32)
+        _f32p(yt)
         d.y = yt.data_ptr() + 4 * off
         ret = yt
         if gate is not None:
             assert gate[0].shape == yt.shape and gate[0].is_contiguous() and yt.is_contiguous()
-            d.gate, d.gate_slope = _ptr(gate[0], torch.float32).value + 4 * off, gate[1]
+            d.gate, d.gate_slope = _f32p(gate[0]) + 4 * off, gate[1]
     else:
         if out is None:
             out = torch.empty((G * N, OH, OW, cout), device=x.device, dtype=torch.float32)
-        _ptr(out, torch.float32)
+        _f32p(out)
         assert out.shape[0] == G * N
         ld = out.shape[-1]
         d.y, d.y_sx, d.y_sy, d.y_sn = out.data_ptr(), ld, ld * OW, ld * OW * OH
         ret = out
         if gate is not None:
             assert gate[0].shape == out.shape
-            d.gate, d.gate_slope = _ptr(gate[0], torch.float32).value, gate[1]
+            d.gate, d.gate_slope = _f32p(gate[0]), gate[1]
     if res is not None:
         assert res.shape == (G * N, OH, OW, cout)
         d.r_sx, d.r_sy, d.r_sn = cout, cout * OW, cout * OW * OH
     if x2 is not None:
         assert kh == kw == 1 and rows is None and split is None and in_scale is None and x2.shape[0] == (N if (G == 1 or x2_shared) else G * N) and x2.is_contiguous()
-        d.x2, d.Cin2, d.x2_ld, d.stride2, d.H2, d.W2 = _ptr(x2, torch.float32).value, x2.shape[3], x2.shape[3], stride2, x2.shape[1], x2.shape[2]
+        d.x2, d.Cin2, d.x2_ld, d.stride2, d.H2, d.W2 = _f32p(x2), x2.shape[3], x2.shape[3], stride2, x2.shape[1], x2.shape[2]
     if res_up is not None:
         assert res is None and res_up.shape[0] == G * N and res_up.shape[3] == cout and res_up.is_contiguous()
-        d.res_up, d.ru_H, d.ru_W, d.ru_ld = _ptr(res_up, torch.float32).value, res_up.shape[1], res_up.shape[2], res_up.shape[3]
+        d.res_up, d.ru_H, d.ru_W, d.ru_ld = _f32p(res_up), res_up.shape[1], res_up.shape[2], res_up.shape[3]
     if G > 1:
         assert in_scale is None or (in_scale.shape == (G, cin) and in_shift.shape == (G, cin) and in_scale.is_contiguous() and in_shift.is_contiguous())
         d.groups = G
@@ -260,18 +196,18 @@ def conv2d_nhwc(x, w, bias=None, *, kh=1, kw=1, stride=1, pad=0, pad_y=None, pad
         base = bn.rows                                          # parts > 1: this launch appends behind the rows of the earlier parts
         assert base + cap <= bn.stats.shape[0] and bn.stats.shape[2] == cout
         rows_out = C.c_int(0)
-        d.stats, d.stats_cap, d.stats_rows = bn.stats.data_ptr() + base * BN_STAT_PLANES * cout * 4, cap, C.cast(C.pointer(rows_out), C.c_void_p)
+        d.stats, d.stats_cap, d.stats_rows = bn.stats.data_ptr() + base * BN_STAT_PLANES * cout * 4, cap, C.addressof(rows_out)
         if bn.x is not None:
             assert gate is not None and bn.x.shape == ret.shape and bn.x.is_contiguous() and ret.is_contiguous()
-            bx = _ptr(bn.x, torch.float32).value + (4 * out_view[4] if out_view is not None else 0)      # laid out like y, like the gate
+            bx = _f32p(bn.x) + (4 * out_view[4] if out_view is not None else 0)      # laid out like y, like the gate
             if bn.stored_gate:
-                d.bn_x, d.bn_mean, d.bn_invstd = bx, _ptr(bn.mean, torch.float32).value, _ptr(bn.invstd, torch.float32).value
+                d.bn_x, d.bn_mean, d.bn_invstd = bx, _f32p(bn.mean), _f32p(bn.invstd)
             else:                                               # gate recomputed; the stored gate stays as the kernel's fall-back
                 d.bn_x = bx
-                d.bn_mean, d.bn_invstd, d.bn_gamma, d.bn_beta = (_ptr(t, torch.float32).value for t in (bn.mean, bn.invstd, bn.gamma, bn.beta))
+                d.bn_mean, d.bn_invstd, d.bn_gamma, d.bn_beta = (_f32p(t) for t in (bn.mean, bn.invstd, bn.gamma, bn.beta))
     elif bn is not None:
         bn.failed = True
-    _check(lib.vpho_conv2d_nhwc_f32(C.byref(d), _stream()))
+    _call('vpho_conv2d_nhwc_f32', C.byref(d))
     if rows_out is not None:
         bn.calls += 1
         if rows_out.value == 0:
@@ -311,20 +247,19 @@ def conv3x3_winograd(x, u, bias=None, out_slope=1.0, out=None, rows=None, groups
             N //= groups
         if out is None:
             out = torch.empty((groups * N, H, W, cout), device=x.device, dtype=torch.float32)
-        _call('vpho_conv3x3_winograd_grouped_nhwc_f32', _f32(x), C.c_longlong(0 if x_shared else N * H * W * x_ld), _f32(u), _f32(bias), I(groups), I(N), I(H), I(W),
-              I(cin), I(x_ld), I(cout), F(out_slope), _f32(out), I(out.shape[-1]))
+        _call('vpho_conv3x3_winograd_grouped_nhwc_f32', x, 0 if x_shared else N * H * W * x_ld, u, bias, groups, N, H, W, cin, x_ld, cout, out_slope,
+              out, out.shape[-1])
         return out
     if rows is not None:
         assert rows.shape == (N, H, W)
         if out is None:
             out = torch.empty((N * H * W, cout), device=x.device, dtype=torch.float32)
-        _call('vpho_conv3x3_winograd_rows_nhwc_f32', _f32(x), _f32(u), _f32(bias), I(N), I(H), I(W), I(cin), I(x_ld), I(cout), F(out_slope),
-              _i32(rows.wins), _i32(rows.tiles()), I(int(rows.tiles()[N].item()) if _prof_on else 0), _f32(out), I(out.shape[-1]))
+        _call('vpho_conv3x3_winograd_rows_nhwc_f32', x, u, bias, N, H, W, cin, x_ld, cout, out_slope, rows.wins, rows.tiles(),
+              int(rows.tiles()[N].item()) if _prof_on else 0, out, out.shape[-1])
         return out
     if out is None:
         out = torch.empty((N, H, W, cout), device=x.device, dtype=torch.float32)
-    _call('vpho_conv3x3_winograd_nhwc_f32', _f32(x), _f32(u), _f32(bias), I(N), I(H), I(W), I(cin), I(x_ld), I(cout), F(out_slope), _f32(out),
-          I(out.shape[-1]))
+    _call('vpho_conv3x3_winograd_nhwc_f32', x, u, bias, N, H, W, cin, x_ld, cout, out_slope, out, out.shape[-1])
     return out
 
 
@@ -338,7 +273,7 @@ def winograd_weights_device(w, for_input_gradient=False):
         cin = k9 // 9
         o, i = (cin, cout) if for_input_gradient else (cout, cin)
         u = c[1] if c is not None else torch.empty((i // 8, 16, o, 8), device=w.device, dtype=torch.float32)
-        _call('vpho_winograd_weights_f32', _f32(w), I(cout), I(cin), I(1 if for_input_gradient else 0), _f32(u))
+        _call('vpho_winograd_weights_f32', w, cout, cin, 1 if for_input_gradient else 0, u)
         c = (w._version, u)
         setattr(w, key, c)
         if _WINO_BATCH is not None:
@@ -378,12 +313,12 @@ class WinogradWeightBatch:
             blk = 0
             for n, (w, key, mode, u) in enumerate(self.items.values()):
                 cout, cin = w.shape[0], w.shape[1] // 9
-                _ptr(w, torch.float32), _ptr(u, torch.float32)
+                _f32p(w), _f32p(u)
                 rec[n] = (w.data_ptr(), u.data_ptr(), cout, cin, mode, blk)
                 blk += (cout * cin + 255) // 256
             dev = next(iter(self.items.values()))[0].device
             self.table, self.blocks = torch.from_numpy(rec.view(np.uint8).copy()).to(dev), blk
-        _call('vpho_winograd_weights_multi_f32', _ptr(self.table, torch.uint8), I(len(self.items)), LL(self.blocks))
+        _call('vpho_winograd_weights_multi_f32', abi.at(self.table, torch.uint8), len(self.items), self.blocks)
         for w, key, mode, u in self.items.values():
             setattr(w, key, (w._version, u))
 
@@ -405,11 +340,11 @@ def _winograd_bn(x, u, bias, out_slope, cin, cout, bn, gate_slope=1.0):
     cap = (N * H * W + 255) // 256
     bn.stats = torch.empty((cap, BN_STAT_PLANES, cout), device=x.device, dtype=torch.float32)
     rows_out = C.c_int(0)
-    bx = (bn.x, bn.mean, bn.invstd, bn.gamma, bn.beta) if bn.x is not None else (None,) * 5
+    b_x, b_mean, b_invstd, b_gamma, b_beta = (bn.x, bn.mean, bn.invstd, bn.gamma, bn.beta) if bn.x is not None else (None,) * 5
     if bn.x is not None:
         assert bn.x.shape == out.shape and bn.x.is_contiguous()
-    _call('vpho_conv3x3_winograd_stats_nhwc_f32', _f32(x), _f32(u), _f32(bias), I(N), I(H), I(W), I(cin), I(x_ld), I(cout), F(out_slope), _f32(out), I(cout),
-          _f32(bn.stats), I(cap), C.byref(rows_out), *[_f32(t) for t in bx], F(gate_slope))
+    _call('vpho_conv3x3_winograd_stats_nhwc_f32', x, u, bias, N, H, W, cin, x_ld, cout, out_slope, out, cout, bn.stats, cap, C.byref(rows_out), b_x,
+          b_mean, b_invstd, b_gamma, b_beta, gate_slope)
     bn.rows, bn.calls = rows_out.value, 1
     return out
 
@@ -429,8 +364,7 @@ def conv3x3_train(x, w, bias=None, out_slope=1.0, rows=None, bn=None):
     if rows is not None:
         assert rows.shape == (N, H, W)
         out = torch.zeros((N, H, W, cout), device=x.device, dtype=torch.float32)
-        _call('vpho_conv3x3_winograd_scatter_nhwc_f32', _f32(x), _f32(u), _f32(bias), I(N), I(H), I(W), I(cin), I(x_ld), I(cout), F(out_slope),
-              _i32(rows.wins), _i32(rows.tiles()), _f32(out), I(cout))
+        _call('vpho_conv3x3_winograd_scatter_nhwc_f32', x, u, bias, N, H, W, cin, x_ld, cout, out_slope, rows.wins, rows.tiles(), out, cout)
         return out
     return conv3x3_winograd(x, u, bias, out_slope)
 
@@ -448,8 +382,7 @@ def conv3x3_dgrad_winograd(dy, w, gate=None, rows=None, bn=None):
     if rows is not None and gate is None:
         assert rows.shape == (N, H, W)
         out = torch.zeros((N, H, W, cin), device=dy.device, dtype=torch.float32)
-        _call('vpho_conv3x3_winograd_scatter_nhwc_f32', _f32(dy), _f32(u), None, I(N), I(H), I(W), I(cout), I(ld), I(cin), F(1.0),
-              _i32(rows.wins), _i32(rows.tiles()), _f32(out), I(cin))
+        _call('vpho_conv3x3_winograd_scatter_nhwc_f32', dy, u, None, N, H, W, cout, ld, cin, 1.0, rows.wins, rows.tiles(), out, cin)
         return out
     if gate is None:
         return conv3x3_winograd(dy, u, None, 1.0)
@@ -458,7 +391,7 @@ def conv3x3_dgrad_winograd(dy, w, gate=None, rows=None, bn=None):
         return _winograd_bn(dy, u, None, 1.0, cout, cin, bn, gate_slope=slope)
     assert g.shape == (N, H, W, cin) and g.is_contiguous()
     out = torch.empty((N, H, W, cin), device=dy.device, dtype=torch.float32)
-    _call('vpho_conv3x3_winograd_gate_nhwc_f32', _f32(dy), _f32(u), _f32(g), F(slope), I(N), I(H), I(W), I(cout), I(ld), I(cin), _f32(out), I(cin))
+    _call('vpho_conv3x3_winograd_gate_nhwc_f32', dy, u, g, slope, N, H, W, cout, ld, cin, out, cin)
     return out
 
 
@@ -469,7 +402,7 @@ def linear(x, w, bias=None, out_slope=1.0, out=None, acc64=False):
     if acc64:
         assert x.is_contiguous() and w.is_contiguous() and w.shape[1] == cin
         y = torch.empty((rows, w.shape[0]), device=x.device, dtype=torch.float32) if out is None else out
-        _call('vpho_linear_acc64_f32', _f32(x), I(rows), I(cin), I(cin), _f32(w), _f32(bias), I(w.shape[0]), F(out_slope), _f32(y), I(y.shape[-1]))
+        _call('vpho_linear_acc64_f32', x, rows, cin, cin, w, bias, w.shape[0], out_slope, y, y.shape[-1])
         return y
     y = conv2d_nhwc(x.view(rows, 1, 1, cin), w, bias, out_slope=out_slope,
                     out=None if out is None else out.view(rows, 1, 1, w.shape[0]))
@@ -477,25 +410,8 @@ def linear(x, w, bias=None, out_slope=1.0, out=None, acc64=False):
 
 
 # ----------------------------------------------------------------------------------------------- score net / sampler
-class ScoreWeights(C.Structure):
-    _fields_ = [('D', C.c_int), ('Dp', C.c_int), ('nheads', C.c_int)] + \
-               [(k, C.c_void_p) for k in ('t_W', 't_w', 't_b', 'pe0_w', 'pe0_b', 'pe2_w', 'pe2_b', 'w1_t', 'w1_p',
-                                          'w1_f', 'b1', 'w2', 'b2')] + [('w1_p_split', C.c_void_p), ('split_terms', C.c_int)]
-
-
-class OdeStats(C.Structure):
-    _fields_ = [(k, C.c_int) for k in ('nfev', 'n_accepted', 'n_rejected', 'nan_count', 'status', 'n_log')]
-
-
-lib.vpho_score_workspace_bytes.restype = C.c_longlong
-lib.vpho_maxpool_bwd_workspace_bytes.restype = C.c_longlong
-lib.vpho_maxpool_bwd_workspace_bytes.argtypes = [C.c_int] * 7
-lib.vpho_score_workspace_bytes.argtypes = [C.POINTER(ScoreWeights), C.c_int, C.c_int]
-lib.vpho_score_eval.argtypes = [C.POINTER(ScoreWeights), C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_void_p,
-                                C.c_void_p, C.c_longlong, C.c_void_p]
-lib.vpho_ode_sample.argtypes = [C.POINTER(ScoreWeights), C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_double,
-                                C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong,
-                                C.POINTER(OdeStats), C.c_void_p, C.c_int, C.c_void_p]
+ScoreWeights = abi.struct('vpho_score_weights')
+OdeStats = abi.struct('vpho_ode_stats')
 
 
 class ScoreNet:
@@ -543,7 +459,7 @@ class ScoreNet:
         self.split_mode = mode
 
     def workspace(self, bs, S):
-        need = lib.vpho_score_workspace_bytes(C.byref(self.c), bs, S)
+        need = abi.query('vpho_score_workspace_bytes', C.byref(self.c), bs, S)
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         return self._ws
@@ -553,8 +469,7 @@ class ScoreNet:
         bs = feat_img.shape[0]
         ws = self.workspace(bs, S)
         out = torch.empty((bs * S, self.D), device=self.device, dtype=torch.float32)
-        _check(lib.vpho_score_eval(C.byref(self.c), _ptr(feat_img, torch.float32), bs, S, _ptr(x, torch.float32), float(t),
-                                   _ptr(out), _ptr(ws), ws.numel(), _stream()))
+        _call('vpho_score_eval', C.byref(self.c), feat_img, bs, S, x, float(t), out, ws, ws.numel())
         return out
 
     def sample(self, feat_img, init_x, S, T0, num_steps, xs_f64, x_f64=True, eps=1e-5, rtol=3e-3, atol=3e-4, log_cap=4096):
@@ -567,10 +482,8 @@ class ScoreNet:
         x = torch.empty((R, self.D), device=self.device, dtype=torch.float64 if x_f64 else torch.float32)
         st = OdeStats()
         log = (C.c_double * (4 * log_cap))()
-        _check(lib.vpho_ode_sample(C.byref(self.c), _ptr(feat_img, torch.float32), bs, S, _ptr(init_x, torch.float32),
-                                   float(T0), float(eps), int(num_steps), float(rtol), float(atol), _ptr(xs),
-                                   1 if xs_f64 else 0, _ptr(x), 1 if x_f64 else 0, _ptr(ws), ws.numel(), C.byref(st), log, log_cap,
-                                   _stream()))
+        _call('vpho_ode_sample', C.byref(self.c), feat_img, bs, S, init_x, float(T0), float(eps), int(num_steps), float(rtol), float(atol), xs,
+              1 if xs_f64 else 0, x, 1 if x_f64 else 0, ws, ws.numel(), C.byref(st), log, log_cap)
         n = min(st.n_log, log_cap)
         steps = [(log[4 * i], log[4 * i + 1], log[4 * i + 2], bool(log[4 * i + 3])) for i in range(n)]
         return xs, x, dict(nfev=st.nfev, n_accepted=st.n_accepted, n_rejected=st.n_rejected, nan_count=st.nan_count,
@@ -578,38 +491,15 @@ class ScoreNet:
 
 
 # ----------------------------------------------------------------------------------------------- glue kernels
-def _i32(t):
-    return _ptr(t, torch.int32)
-
-
-def _u8(t):
-    return None if t is None else _ptr(t, torch.uint8)
-
-
-def _f32(t):
-    return None if t is None else _ptr(t, torch.float32)
-
-
-def _f64(t):
-    return None if t is None else _ptr(t, torch.float64)
-
-
-def _call(name, *args):
-    _check(getattr(lib, name)(*args, _stream()))
-
-
 def _new(shape, like, dtype=torch.float32):
     return torch.empty(shape, device=like.device, dtype=dtype)
-
-
-LL, I, F = C.c_longlong, C.c_int, C.c_float
 
 
 def nchw_to_nhwc(x, ld=None):
     N, Cc, H, W = x.shape
     ld = Cc if ld is None else ld
     y = _new((N, H, W, ld), x)
-    _call('vpho_nchw_to_nhwc_f32', _f32(x), I(N), I(Cc), I(H), I(W), _f32(y), I(ld))
+    _call('vpho_nchw_to_nhwc_f32', x, N, Cc, H, W, y, ld)
     return y
 
 
@@ -617,7 +507,7 @@ def nhwc_to_nchw(x, channels=None):
     N, H, W, ld = x.shape
     Cc = ld if channels is None else channels
     y = _new((N, Cc, H, W), x)
-    _call('vpho_nhwc_to_nchw_f32', _f32(x), I(N), I(H), I(W), I(Cc), I(ld), _f32(y))
+    _call('vpho_nhwc_to_nchw_f32', x, N, H, W, Cc, ld, y)
     return y
 
 
@@ -625,7 +515,7 @@ def maxpool_nhwc(x, k, stride, pad):
     N, H, W, Cc = x.shape
     OH, OW = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
     y = _new((N, OH, OW, Cc), x)
-    _call('vpho_maxpool_nhwc_f32', _f32(x), I(N), I(H), I(W), I(Cc), I(k), I(stride), I(pad), _f32(y))
+    _call('vpho_maxpool_nhwc_f32', x, N, H, W, Cc, k, stride, pad, y)
     return y
 
 
@@ -637,12 +527,10 @@ def resize_bilinear_nhwc(x, OH, OW, out=None, c_off=0, accumulate=False, channel
     assert out.shape[:3] == (N, OH, OW)
     if rows is not None:                                     # only the listed output pixels (RoiWindows), in place
         assert rows.shape == (N, OH, OW)
-        _call('vpho_resize_bilinear_rows_nhwc_f32', _f32(x), I(N), I(H), I(W), I(Cc), I(ldx), I(OH), I(OW), _f32(out), I(out.shape[-1]),
-              I(c_off), I(1 if accumulate else 0), _ptr(rows.row_map, torch.int32), _ptr(rows.count, torch.int32),
-              I(int(rows.count.item()) if _prof_on else 0))
+        _call('vpho_resize_bilinear_rows_nhwc_f32', x, N, H, W, Cc, ldx, OH, OW, out, out.shape[-1], c_off, 1 if accumulate else 0, rows.row_map,
+              rows.count, int(rows.count.item()) if _prof_on else 0)
         return out
-    _call('vpho_resize_bilinear_nhwc_f32', _f32(x), I(N), I(H), I(W), I(Cc), I(ldx), I(OH), I(OW), _f32(out), I(out.shape[-1]),
-          I(c_off), I(1 if accumulate else 0))
+    _call('vpho_resize_bilinear_nhwc_f32', x, N, H, W, Cc, ldx, OH, OW, out, out.shape[-1], c_off, 1 if accumulate else 0)
     return out
 
 
@@ -657,7 +545,7 @@ class RoiWindows:
         """(N+1,) int32: first 2 x 2 Winograd tile of every image's window, [N] = their number (vpho_winograd_window_tiles_i32)"""
         if self._tiles is None:
             self._tiles = torch.empty((self.shape[0] + 1,), device=self.wins.device, dtype=torch.int32)
-            _call('vpho_winograd_window_tiles_i32', _i32(self.wins), I(self.shape[0]), _i32(self._tiles))
+            _call('vpho_winograd_window_tiles_i32', self.wins, self.shape[0], self._tiles)
         return self._tiles
 
     def to_map(self, rows):
@@ -678,8 +566,7 @@ def roi_windows(boxes_a, boxes_b, N, H, W, spatial_scale, dilate=0):
     wins = torch.empty((N, 5), device=dev, dtype=torch.int32)
     row_map = torch.empty((N * H * W,), device=dev, dtype=torch.int32)
     count = torch.empty((1,), device=dev, dtype=torch.int32)
-    _call('vpho_roi_windows_i32', _f32(boxes_a), _f32(boxes_b), I(N), I(H), I(W), F(spatial_scale), I(dilate), _ptr(wins, torch.int32),
-          _ptr(row_map, torch.int32), _ptr(count, torch.int32))
+    _call('vpho_roi_windows_i32', boxes_a, boxes_b, N, H, W, spatial_scale, dilate, wins, row_map, count)
     return RoiWindows(wins, row_map, count, (N, H, W))
 
 
@@ -689,14 +576,13 @@ def roi_align_nhwc(feat, boxes, out_size, spatial_scale, flip_w=None, out=None, 
         Cc = feat.shape[-1]
         if out is None:
             out = _new((N, out_size, out_size, Cc), feat)
-        _call('vpho_roi_align_window_nhwc_f32', _f32(feat), _ptr(win.wins, torch.int32), I(N), I(H), I(W), I(Cc), _f32(boxes),
-              F(spatial_scale), I(out_size), _u8(flip_w), _f32(out), I(out.shape[-1]), I(c_off), I(int(win.count.item()) if _prof_on else 0))
+        _call('vpho_roi_align_window_nhwc_f32', feat, win.wins, N, H, W, Cc, boxes, spatial_scale, out_size, flip_w, out, out.shape[-1], c_off,
+              int(win.count.item()) if _prof_on else 0)
         return out
     N, H, W, Cc = feat.shape
     if out is None:
         out = _new((N, out_size, out_size, Cc), feat)
-    _call('vpho_roi_align_nhwc_f32', _f32(feat), I(N), I(H), I(W), I(Cc), _f32(boxes), F(spatial_scale), I(out_size), _u8(flip_w),
-          _f32(out), I(out.shape[-1]), I(c_off))
+    _call('vpho_roi_align_nhwc_f32', feat, N, H, W, Cc, boxes, spatial_scale, out_size, flip_w, out, out.shape[-1], c_off)
     return out
 
 
@@ -708,51 +594,50 @@ def roi_align_dual_nhwc(feat, boxes, out_size, spatial_scale, win, out2, flip_w2
     if out is None:
         out = _new((N, out_size, out_size, Cc), feat)
     assert out.shape == (N, out_size, out_size, Cc) and out.is_contiguous()
-    _call('vpho_roi_align_window_dual_nhwc_f32', _f32(feat), _ptr(win.wins, torch.int32), I(N), I(H), I(W), I(Cc), _f32(boxes),
-          F(spatial_scale), I(out_size), _u8(None), _f32(out), I(Cc), I(0), _u8(flip_w2), _f32(out2), I(out2.shape[-1]), I(c_off2),
-          I(int(win.count.item()) if _prof_on else 0))
+    _call('vpho_roi_align_window_dual_nhwc_f32', feat, win.wins, N, H, W, Cc, boxes, spatial_scale, out_size, None, out, Cc, 0, flip_w2, out2,
+          out2.shape[-1], c_off2, int(win.count.item()) if _prof_on else 0)
     return out
 
 
 def align_heatmap_nhwc(hm, bbox, bbox_rect, flip_w=None):
     N, S, _, Cc = hm.shape
     out = torch.empty_like(hm)
-    _call('vpho_align_heatmap_nhwc_f32', _f32(hm), I(N), I(S), I(Cc), _f32(bbox), _f32(bbox_rect), _u8(flip_w), _f32(out))
+    _call('vpho_align_heatmap_nhwc_f32', hm, N, S, Cc, bbox, bbox_rect, flip_w, out)
     return out
 
 
 def nerf_embed(g, flip_x=None):
     N = g.shape[0]
     out = _new((N, 64), g)
-    _call('vpho_nerf_embed_f32', _f32(g), I(N), _u8(flip_x), _f32(out))
+    _call('vpho_nerf_embed_f32', g, N, flip_x, out)
     return out
 
 
 def cross_tokens(proj_hand, proj_obj, grav_emb, pe):
     bs = proj_hand.shape[0]
     out = _new((bs, 65, 512), proj_hand)
-    _call('vpho_cross_tokens_f32', _f32(proj_hand), _f32(proj_obj), _f32(grav_emb), _f32(pe), I(bs), _f32(out))
+    _call('vpho_cross_tokens_f32', proj_hand, proj_obj, grav_emb, pe, bs, out)
     return out
 
 
 def mha(qkv, S, B, E, nhead, drop=None):
     """drop: optional (B*nhead, S, S) keep-mask / (1 - p) on the attention probabilities (training)"""
     out = _new((S, B, E), qkv)
-    _call('vpho_mha_dropout_f32', _f32(qkv), I(S), I(B), I(E), I(nhead), _f32(drop), _f32(out))
+    _call('vpho_mha_dropout_f32', qkv, S, B, E, nhead, drop, out)
     return out
 
 
 def add_layernorm(x, r, gamma, beta, eps=1e-5):
     E = x.shape[-1]
     out = torch.empty_like(x)
-    _call('vpho_add_layernorm_f32', _f32(x), _f32(r), _f32(gamma), _f32(beta), LL(x.numel() // E), I(E), F(eps), _f32(out))
+    _call('vpho_add_layernorm_f32', x, r, gamma, beta, x.numel() // E, E, eps, out)
     return out
 
 
 def force_local(scale, logits, anchor, rows, group=1, group_stride=1, off_scale=0, off_logits=0, friction=0.8):
     out = _new((rows, 3), scale)
-    _call('vpho_force_local_f32', _f32(scale), I(scale.shape[1]), _f32(logits), I(logits.shape[1]), _f32(anchor), F(friction), LL(rows),
-          I(group), I(group_stride), I(off_scale), I(off_logits), _f32(out))
+    _call('vpho_force_local_f32', scale, scale.shape[1], logits, logits.shape[1], anchor, friction, rows, group, group_stride, off_scale, off_logits,
+          out)
     return out
 
 
@@ -760,19 +645,18 @@ def rot6d_to_axis_angle(x, rot_per_row, out=None, ldo=None):
     rows, ldx = x.shape
     if out is None:
         out = _new((rows, 3 * rot_per_row), x)
-    _call('vpho_rot6d_to_axis_angle_f32', _f32(x), LL(rows), I(rot_per_row), I(ldx), _f32(out), I(out.shape[-1] if ldo is None else ldo))
+    _call('vpho_rot6d_to_axis_angle_f32', x, rows, rot_per_row, ldx, out, out.shape[-1] if ldo is None else ldo)
     return out
 
 
 def append_betas(betas, out, rows_per_image):
     rows = out.numel() // out.shape[-1]
-    _call('vpho_append_betas_f32', _f32(betas), LL(rows), LL(rows_per_image), _f32(out), I(out.shape[-1]))
+    _call('vpho_append_betas_f32', betas, rows, rows_per_image, out, out.shape[-1])
     return out
 
 
 # ----------------------------------------------------------------------------------------------- MANO
-class ManoTables(C.Structure):
-    _fields_ = [(k, C.c_void_p) for k in ('v_template', 'shapedirs', 'posedirs_t', 'J_regressor', 'weights', 'tip_posedirs_t', 'posedirs_mfma')]
+ManoTables = abi.struct('vpho_mano_tables')
 
 
 class Mano:
@@ -796,7 +680,7 @@ class Mano:
     def shape(self, betas):
         n = betas.shape[0]
         vs, J = _new((n, 778, 3), betas), _new((n, 16, 3), betas)
-        _call('vpho_mano_shape_f32', C.byref(self.c), _f32(betas), I(n), _f32(vs), _f32(J))
+        _call('vpho_mano_shape_f32', C.byref(self.c), betas, n, vs, J)
         return vs, J
 
     def train(self, rot6d, shape, gt_vert, gt_joint, gt_rot6d, gt_shape, is_right, weights, want_outputs=False, is_ho3d=None):
@@ -807,9 +691,8 @@ class Mano:
         parts = _new((bs, 4), rot6d, torch.float64)
         verts = _new((bs, 778, 3), rot6d) if want_outputs else None
         joints = _new((bs, 21, 3), rot6d) if want_outputs else None
-        _call('vpho_mano_train_f32', C.byref(self.c), _f32(rot6d), _f32(shape), _f32(gt_vert), _f32(gt_joint), _f32(gt_rot6d), _f32(gt_shape),
-              _u8(is_right), _u8(is_ho3d), I(bs), F(weights[0]), F(weights[1]), F(weights[2]), F(weights[3]), _f32(d6), _f32(ds), _f64(parts),
-              _f32(verts), _f32(joints))
+        _call('vpho_mano_train_f32', C.byref(self.c), rot6d, shape, gt_vert, gt_joint, gt_rot6d, gt_shape, is_right, is_ho3d, bs, weights[0],
+              weights[1], weights[2], weights[3], d6, ds, parts, verts, joints)
         tot = parts.sum(0)
         L = dict(vert_loss=tot[0] * (weights[0] / (bs * 2334.0)), joint_loss=tot[1] * (weights[1] / (bs * 63.0)),
                  mano_pose_loss=tot[2] * (weights[2] / (bs * 96.0)), mano_shape_loss=tot[3] * (weights[3] / (bs * 10.0)))
@@ -821,22 +704,14 @@ class Mano:
         vs, J = shape_ctx
         verts = _new((n, 778, 3), pose) if want_verts else None
         joints = _new((n, 21, 3), pose)
-        _call('vpho_mano_fk_f32', C.byref(self.c), _f32(pose), I(ld), LL(n), I(hands_per_image), _f32(vs), _f32(J), _u8(ho3d),
-              _f32(verts), _f32(joints))
+        _call('vpho_mano_fk_f32', C.byref(self.c), pose, ld, n, hands_per_image, vs, J, ho3d, verts, joints)
         return verts, joints
 
 
 # ----------------------------------------------------------------------------------------------- aggregation
-class ObjTables(C.Structure):
-    _fields_ = [('kpt', C.c_void_p), ('vert', C.c_void_p), ('com', C.c_void_p), ('n_kpt', I), ('n_vert', I), ('n_obj', I)]
-
-
-class AnchorTables(C.Structure):
-    _fields_ = [(k, C.c_void_p) for k in ('face_idx', 'anchor_weight', 'vert2joint', 'skeleton')]
-
-
-class HandSurfaceTable(C.Structure):
-    _fields_ = [(k, C.c_void_p) for k in ('faces', 'csr_offset', 'csr_entry', 'links', 'alpha')] + [('V', I), ('F', I), ('L', I)]
+ObjTables = abi.struct('vpho_obj_tables')
+AnchorTables = abi.struct('vpho_anchor_tables')
+HandSurfaceTable = abi.struct('vpho_hand_surface_table')
 
 
 class HandSurface:
@@ -892,7 +767,7 @@ class HandSurface:
         vf, nf = out if out is not None else (_new((n, self.V + self.L, 3), verts), _new((n, self.V + self.L, 3), verts))
         if any(tuple(t.shape) != (n, self.V + self.L, 3) for t in (vf, nf)):
             raise VphoError(f'HandSurface.fill: outputs of shape {tuple(vf.shape)} and {tuple(nf.shape)}, expected {(n, self.V + self.L, 3)}')
-        _call('vpho_hand_surface_f32', C.byref(self.table), _f32(verts), I(n), _f32(vf), _f32(nf))
+        _call('vpho_hand_surface_f32', C.byref(self.table), verts, n, vf, nf)
         return vf, nf
 
 
@@ -929,7 +804,7 @@ class Aggregation:
 
     def hand_candidates(self, diff_pose, reg_pose, bs, S):
         pose = _new((bs, 2 * S, 48), diff_pose)
-        _call('vpho_hand_candidates_f32', _f32(diff_pose), I(diff_pose.shape[-1]), _f32(reg_pose), I(bs), I(S), _f32(pose))
+        _call('vpho_hand_candidates_f32', diff_pose, diff_pose.shape[-1], reg_pose, bs, S, pose)
         return pose
 
     def hand_heat(self, joints, root, K, bbox, heatmap, observe):
@@ -937,8 +812,7 @@ class Aggregation:
         _, J, H, W = heatmap.shape
         out = _new((bs, Cn, len(observe)), joints)
         obs = (C.c_int * len(observe))(*observe)
-        _call('vpho_hand_heat_f32', _f32(joints), _f32(root), _f32(K), _f32(bbox), _f32(heatmap), I(bs), I(Cn), I(J), I(H), I(W), obs,
-              I(len(observe)), _f32(out))
+        _call('vpho_hand_heat_f32', joints, root, K, bbox, heatmap, bs, Cn, J, H, W, obs, len(observe), out)
         return out
 
     def hand_fuse_level(self, hv, pose, k, level, want_topk_pose=False, want_scores=False):
@@ -947,19 +821,19 @@ class Aggregation:
         val, idx = _new((bs, Fn, k), hv), _new((bs, Fn, k), hv, torch.int32)
         tp = _new((bs, k, Fn, 3), hv) if want_topk_pose else None
         sc = _new((bs, Cn, Fn), hv) if want_scores else None
-        _call('vpho_hand_fuse_level_f32', _f32(hv), I(n_obs), _f32(pose), I(bs), I(Cn), I(k), I(level), _f32(val), _i32(idx), _f32(tp), _f32(sc))
+        _call('vpho_hand_fuse_level_f32', hv, n_obs, pose, bs, Cn, k, level, val, idx, tp, sc)
         return (val, idx, tp, sc) if want_scores else (val, idx, tp)
 
     def topk(self, scores, k, F_=1):
         """scores (rows, n) [F_=1] or (rows, n, F_) -> val, idx (rows, F_, k)"""
         rows, n = scores.shape[:2]
         val, idx = _new((rows, F_, k), scores), _new((rows, F_, k), scores, torch.int32)
-        _call('vpho_topk_f32', _f32(scores), I(rows), I(n), I(F_), I(k), _f32(val), _i32(idx))
+        _call('vpho_topk_f32', scores, rows, n, F_, k, val, idx)
         return val, idx
 
     def topk_weights(self, val):
         w = torch.empty_like(val)
-        _call('vpho_topk_weights_f32', _f32(val), I(val.numel() // val.shape[-1]), I(val.shape[-1]), _f32(w))
+        _call('vpho_topk_weights_f32', val, val.numel() // val.shape[-1], val.shape[-1], w)
         return w
 
     def obj_heat_score(self, pose, root, obj_id, is_right, K, bbox, heatmap, transl_override=None):
@@ -967,42 +841,39 @@ class Aggregation:
         _, J, H, W = heatmap.shape
         assert J == self.obj.n_kpt
         score = _new((bs, n), root)
-        _call('vpho_obj_heat_score', _f64(pose), I(n), _f64(transl_override), _f32(root), C.byref(self.obj), _i32(obj_id), _u8(is_right),
-              _f32(K), _f32(bbox), _f32(heatmap), I(bs), I(H), I(W), _f32(score))
+        _call('vpho_obj_heat_score', pose, n, transl_override, root, C.byref(self.obj), obj_id, is_right, K, bbox, heatmap, bs, H, W, score)
         return score
 
     def obj_cross(self, pose, transl_idx, rot_idx):
         bs, n = pose.shape[:2]
         ko = transl_idx.shape[-1]
         cand = _new((bs, ko * ko, 9), pose, torch.float64)
-        _call('vpho_obj_cross_candidates', _f64(pose), I(n), _i32(transl_idx), _i32(rot_idx), I(bs), I(ko), _f64(cand))
+        _call('vpho_obj_cross_candidates', pose, n, transl_idx, rot_idx, bs, ko, cand)
         return cand
 
     def obj_physics_score(self, cand, root, obj_id, is_right, force_point, force_global):
         bs, n = cand.shape[:2]
         score = _new((bs, n), root)
-        _call('vpho_obj_physics_score', _f64(cand), I(n), _f32(root), C.byref(self.obj), _i32(obj_id), _u8(is_right), _f32(force_point),
-              _f32(force_global), I(bs), _f32(score))
+        _call('vpho_obj_physics_score', cand, n, root, C.byref(self.obj), obj_id, is_right, force_point, force_global, bs, score)
         return score
 
     def obj_fuse(self, pose, idx_a, w_a, idx_b=None, w_b=None, pick_b=None):
         bs, n = pose.shape[:2]
         k = idx_a.shape[-1]
         fused = _new((bs, 9), pose, torch.float64)
-        _call('vpho_obj_fuse_f64', _f64(pose), I(n), _i32(idx_a), _f32(w_a), None if idx_b is None else _i32(idx_b), _f32(w_b), _u8(pick_b),
-              I(bs), I(k), _f64(fused))
+        _call('vpho_obj_fuse_f64', pose, n, idx_a, w_a, idx_b, w_b, pick_b, bs, k, fused)
         return fused
 
     def obj_verts(self, pose, root, obj_id, is_right):
         bs = pose.shape[0]
         out = _new((bs, self.obj.n_vert, 3), root)
-        _call('vpho_obj_verts_f32', _f64(pose), _f32(root), C.byref(self.obj), _i32(obj_id), _u8(is_right), I(bs), _f32(out))
+        _call('vpho_obj_verts_f32', pose, root, C.byref(self.obj), obj_id, is_right, bs, out)
         return out
 
     def force_anchor(self, verts, root, force_local_, hands_per_image):
         n = verts.shape[0]
         fp, fg = _new((n, 32, 3), verts), _new((n, 32, 3), verts)
-        _call('vpho_force_anchor_f32', C.byref(self.anchor), _f32(verts), _f32(root), _f32(force_local_), LL(n), I(hands_per_image), _f32(fp), _f32(fg))
+        _call('vpho_force_anchor_f32', C.byref(self.anchor), verts, root, force_local_, n, hands_per_image, fp, fg)
         return fp, fg
 
     def contact_detect(self, hand_verts, hand_normals, obj_verts, obj_normals, normal_thresh=(-0.015, 0.01), vertical_thresh=0.01,
@@ -1013,9 +884,9 @@ class Aggregation:
         no = obj_verts.shape[1]
         hc, oc = _new((n, nh), hand_verts), _new((n, no), hand_verts)
         o2h = _new((n, no), hand_verts, torch.int32)
-        args = (F(normal_thresh[0]), F(normal_thresh[1]), F(vertical_thresh), F(decay[0]), F(decay[1]))
-        _call('vpho_contact_detect_f32', _f32(hand_verts), _f32(hand_normals), _f32(obj_verts), I(n), I(nh), I(no), *args, _f32(hc), None)
-        _call('vpho_contact_detect_f32', _f32(obj_verts), _f32(obj_normals), _f32(hand_verts), I(n), I(no), I(nh), *args, _f32(oc), _i32(o2h))
+        (n0, n1), v, (d0, d1) = normal_thresh, vertical_thresh, decay
+        _call('vpho_contact_detect_f32', hand_verts, hand_normals, obj_verts, n, nh, no, n0, n1, v, d0, d1, hc, None)
+        _call('vpho_contact_detect_f32', obj_verts, obj_normals, hand_verts, n, no, nh, n0, n1, v, d0, d1, oc, o2h)
         return hc, oc, o2h
 
     def hand_contact(self, hand_verts, hand_normals, obj_verts, normal_thresh=(-0.015, 0.01), vertical_thresh=0.01, decay=(-0.005, 0.005)):
@@ -1023,22 +894,22 @@ class Aggregation:
         (n,No,3) -> hand_contact (n,Nh); one launch, no object normals"""
         n, nh, _ = hand_verts.shape
         hc = _new((n, nh), hand_verts)
-        _call('vpho_contact_detect_f32', _f32(hand_verts), _f32(hand_normals), _f32(obj_verts), I(n), I(nh), I(obj_verts.shape[1]),
-              F(normal_thresh[0]), F(normal_thresh[1]), F(vertical_thresh), F(decay[0]), F(decay[1]), _f32(hc), None)
+        _call('vpho_contact_detect_f32', hand_verts, hand_normals, obj_verts, n, nh, obj_verts.shape[1], normal_thresh[0], normal_thresh[1],
+              vertical_thresh, decay[0], decay[1], hc, None)
         return hc
 
     def force_contact(self, hand_contact, thresh=0.0):
         """ForceAnchor.get_force_contact + check_is_grasped (physics_fn.py:201-221): (n, >=778) -> (n,32), (n,) uint8"""
         n, ld = hand_contact.shape
         fc, gr = _new((n, 32), hand_contact), _new((n,), hand_contact, torch.uint8)
-        _call('vpho_force_contact_f32', C.byref(self.anchor), _f32(hand_contact), I(ld), I(n), F(thresh), _f32(fc), _u8(gr))
+        _call('vpho_force_contact_f32', C.byref(self.anchor), hand_contact, ld, n, thresh, fc, gr)
         return fc, gr
 
     def anchor_frames(self, verts):
         """ForceAnchor.__call__ (physics_fn.py:224-257): verts (n,778,3) -> points (n,32,3), frames (n,32,3,3)"""
         n = verts.shape[0]
         pts, frames = _new((n, 32, 3), verts), _new((n, 32, 3, 3), verts)
-        _call('vpho_anchor_frames_f32', C.byref(self.anchor), _f32(verts), LL(n), _f32(pts), _f32(frames))
+        _call('vpho_anchor_frames_f32', C.byref(self.anchor), verts, n, pts, frames)
         return pts, frames
 
     def force_optimize(self, verts, gravity, com, force_contact, is_grasped, batch_size, iters=3000, phase1=300, lr=1e-3):
@@ -1048,25 +919,25 @@ class Aggregation:
         pts, frames = self.anchor_frames(verts)
         fl, fg = _new((n, 32, 3), verts), _new((n, 32, 3), verts)
         scale, weight, losses = _new((n, 32), verts), _new((n, 32, 8), verts), _new((n // batch_size, 4), verts)
-        _call('vpho_force_optimize_f32', _f32(pts), _f32(frames), _f32(gravity), _f32(com), _f32(force_contact), _u8(is_grasped),
-              I(n // batch_size), I(batch_size), I(iters), I(phase1), F(lr), _f32(fl), _f32(fg), _f32(scale), _f32(weight), _f32(losses))
+        _call('vpho_force_optimize_f32', pts, frames, gravity, com, force_contact, is_grasped, n // batch_size, batch_size, iters, phase1, lr, fl,
+              fg, scale, weight, losses)
         return dict(force_local=fl, force_global=fg, scale=scale, weight=weight, losses=losses, force_point=pts, frames=frames)
 
     def hand_phys_candidates(self, agg_pose, betas, topk_pose):
         bs, k = topk_pose.shape[:2]
         out = _new((bs, k + 1, 58), agg_pose)
-        _call('vpho_hand_phys_candidates_f32', _f32(agg_pose), I(agg_pose.shape[-1]), _f32(betas), _f32(topk_pose), I(bs), I(k), _f32(out))
+        _call('vpho_hand_phys_candidates_f32', agg_pose, agg_pose.shape[-1], betas, topk_pose, bs, k, out)
         return out
 
     def hand_phys_score(self, force_point, force_global, obj_vert, bs, n_cand):
         out = _new((bs, n_cand, 5), force_point)
-        _call('vpho_hand_phys_score_f32', _f32(force_point), _f32(force_global), _f32(obj_vert), I(obj_vert.shape[1]), I(bs), I(n_cand), _f32(out))
+        _call('vpho_hand_phys_score_f32', force_point, force_global, obj_vert, obj_vert.shape[1], bs, n_cand, out)
         return out
 
     def hand_phys_fuse(self, cand, idx):
         bs, n_cand = cand.shape[:2]
         out = _new((bs, 58), cand)
-        _call('vpho_hand_phys_fuse_f32', _f32(cand), I(n_cand), _i32(idx), I(bs), I(idx.shape[-1]), _f32(out))
+        _call('vpho_hand_phys_fuse_f32', cand, n_cand, idx, bs, idx.shape[-1], out)
         return out
 
     # ---- the ablation aggregators (aggregation modes other than heatmap_cascade; csrc/aggregate_modes.hip)
@@ -1074,22 +945,21 @@ class Aggregation:
         """heatmap (bs,J,H,W) -> peak (bs,J,2) in the reference's transposed (-1, 1) grid, flat arg-max index (bs,J) int32"""
         bs, J, H, W = heatmap.shape
         peak, ind = _new((bs, J, 2), heatmap), _new((bs, J), heatmap, torch.int32)
-        _call('vpho_heatmap_peak_f32', _f32(heatmap), LL(bs * J), I(H), I(W), _f32(peak), _i32(ind))
+        _call('vpho_heatmap_peak_f32', heatmap, bs * J, H, W, peak, ind)
         return peak, ind
 
     def hand_pt2d_score(self, joints, root, K, bbox, peak, per_joint=False):
         """joints (bs,C,21,3), peak (bs,21,2) -> (bs,C) or, per_joint, (bs,C,21)"""
         bs, Cn = joints.shape[:2]
         score = _new((bs, Cn, 21) if per_joint else (bs, Cn), joints)
-        _call('vpho_hand_pt2d_score_f32', _f32(joints), _f32(root), _f32(K), _f32(bbox), _f32(peak), I(bs), I(Cn), I(int(per_joint)), _f32(score))
+        _call('vpho_hand_pt2d_score_f32', joints, root, K, bbox, peak, bs, Cn, int(per_joint), score)
         return score
 
     def obj_pt2d_score(self, pose, root, obj_id, is_right, K, bbox, peak):
         bs, n = pose.shape[:2]
         assert peak.shape[1] == self.obj.n_kpt
         score = _new((bs, n), root)
-        _call('vpho_obj_pt2d_score', _f64(pose), I(n), _f32(root), C.byref(self.obj), _i32(obj_id), _u8(is_right), _f32(K), _f32(bbox), _f32(peak),
-              I(bs), _f32(score))
+        _call('vpho_obj_pt2d_score', pose, n, root, C.byref(self.obj), obj_id, is_right, K, bbox, peak, bs, score)
         return score
 
     def hand_pose_fuse(self, pose, idx=None, w=None, n=None):
@@ -1097,14 +967,14 @@ class Aggregation:
         bs, Cn, ld = pose.shape
         n = idx.shape[-1] if idx is not None else (Cn if n is None else n)
         fused = _new((bs, 48), pose)
-        _call('vpho_hand_pose_fuse_f32', _f32(pose), I(ld), I(Cn), None if idx is None else _i32(idx), _f32(w), I(bs), I(n), _f32(fused))
+        _call('vpho_hand_pose_fuse_f32', pose, ld, Cn, idx, w, bs, n, fused)
         return fused
 
     def hand_joint_gather_mean(self, joints, idx):
         """joints (bs,C,21,3), idx (bs,21,k) -> (bs,21,3)"""
         bs, Cn = joints.shape[:2]
         fused = _new((bs, 21, 3), joints)
-        _call('vpho_hand_joint_gather_mean_f32', _f32(joints), _i32(idx), I(bs), I(Cn), I(idx.shape[-1]), _f32(fused))
+        _call('vpho_hand_joint_gather_mean_f32', joints, idx, bs, Cn, idx.shape[-1], fused)
         return fused
 
 
@@ -1116,7 +986,7 @@ def hand_metrics(pd, gt, per_point=False):
     assert gt.shape == pd.shape
     me, pa = _new((n,), pd), _new((n,), pd)
     pp = _new((n, P), pd) if per_point else None
-    _call('vpho_hand_metrics_f32', _f32(pd), _f32(gt), I(n), I(P), _f32(me), _f32(pa), _f32(pp))
+    _call('vpho_hand_metrics_f32', pd, gt, n, P, me, pa, pp)
     return (me, pa, pp) if per_point else (me, pa)
 
 
@@ -1129,7 +999,7 @@ def hand_metrics_multi(pd, gt, root_joint, is_right):
     assert gt.shape == (n, P, 3) and root_joint.shape == (n, 3) and is_right.shape == (n,)
     me, pa = _new((n, S), pd), _new((n, S), pd)
     flag = is_right.to(device=pd.device, dtype=torch.uint8).contiguous()
-    _call('vpho_hand_metrics_multi_f32', _f32(pd), _f32(gt), _f32(root_joint), _u8(flag), I(n), I(S), I(P), _f32(me), _f32(pa))
+    _call('vpho_hand_metrics_multi_f32', pd, gt, root_joint, flag, n, S, P, me, pa)
     return me, pa
 
 
@@ -1174,9 +1044,8 @@ def hand_bench_multi(pd, gt, root_joint, is_right, with_fscore=True, counts=Fals
     if n * S > 0:
         t, g = hand_bench_tables(pd.device)
         flag = is_right.to(device=pd.device, dtype=torch.uint8).contiguous()
-        _call('vpho_hand_bench_multi_f32', _f32(pd), _f32(gt), _f32(root_joint), _u8(flag), I(n), I(S), I(P), C.c_double(HAND_BENCH_F_THRESH[0]),
-              C.c_double(HAND_BENCH_F_THRESH[1]), _f64(t), _f64(g), I(t.shape[0]), I(1 if with_fscore else 0), _f64(values),
-              _i32(cnt) if counts else None)
+        _call('vpho_hand_bench_multi_f32', pd, gt, root_joint, flag, n, S, P, HAND_BENCH_F_THRESH[0], HAND_BENCH_F_THRESH[1], t, g, t.shape[0],
+              1 if with_fscore else 0, values, cnt if counts else None)
     return (values, cnt) if counts else values
 
 
@@ -1187,7 +1056,7 @@ def hand_bench_table(per):
     assert k == 8 and S > 0
     one, best, mean = (_new((n, 8), per, torch.float64) for _ in range(3))
     if n > 0:
-        _call('vpho_hand_bench_table_f64', _f64(per), I(n), I(S), _f64(one), _f64(best), _f64(mean))
+        _call('vpho_hand_bench_table_f64', per, n, S, one, best, mean)
     return one, best, mean
 
 
@@ -1195,14 +1064,14 @@ def obj_9d_to_rt(pose9, root_joint):
     """(n,9) fp64 [rot6d | t], (n,3) fp32 root -> (n,3,4) fp64 [R | t + root]  (transform_fn.py:85-90, train_diff_hand_obj.py:594-597)"""
     n = pose9.shape[0]
     rt = _new((n, 3, 4), pose9, torch.float64)
-    _call('vpho_obj_9d_to_rt_f64', _f64(pose9), _f32(root_joint), I(n), _f64(rt))
+    _call('vpho_obj_9d_to_rt_f64', pose9, root_joint, n, rt)
     return rt
 
 
 def infer_record_dtype(n_joint=21, n_vert=778):
     """numpy structured dtype of one vpho_infer_pack_f32 record (include/vpho_hip.h): blocks A (fp32), B (fp16), C (fp64)"""
     import numpy as np
-    size = lib.vpho_infer_record_bytes(I(n_joint), I(n_vert))
+    size = abi.query('vpho_infer_record_bytes', n_joint, n_vert)
     if size < 0:
         raise VphoError(f'vpho_infer_record_bytes: n_joint = {n_joint}, n_vert = {n_vert} (both positive, n_vert even)')
     a = 24 * (n_joint + n_vert)
@@ -1250,8 +1119,7 @@ class InferPacker:
         if o9.shape != (n, 9) or root.shape != (n, 3) or flag.shape != (n,):
             raise VphoError(f'InferPacker.pack: agg_obj_6d {tuple(o9.shape)}, root_joint {tuple(root.shape)}, is_right {tuple(flag.shape)} for {n} images')
         with torch.cuda.stream(stream):
-            _call('vpho_infer_pack_f32', _f32(rj), _f32(rv), _f32(aj), _f32(av), _f64(o9), _f32(root), _u8(flag), I(n), I(J), I(V),
-                  _ptr(self.stage[slot]), C.c_void_p(self.host[slot].data_ptr()))
+            _call('vpho_infer_pack_f32', rj, rv, aj, av, o9, root, flag, n, J, V, self.stage[slot], C.c_void_p(self.host[slot].data_ptr()))
             ev = torch.cuda.Event(blocking=True)
             ev.record(stream)
         self.events[slot], self.counts[slot] = ev, n
@@ -1265,9 +1133,7 @@ class InferPacker:
         return self.host[slot].numpy()[:self.counts[slot] * self.record_bytes].view(self.dtype)
 
 
-class ObjMetricTables(C.Structure):
-    _fields_ = [('bbox3d', C.c_void_p), ('verts_sampled', C.c_void_p), ('verts', C.c_void_p), ('vert_offset', C.c_void_p),
-                ('diameter', C.c_void_p), ('n_obj', I), ('n_sampled', I)]
+ObjMetricTables = abi.struct('vpho_obj_metric_tables')
 
 
 from .ops_names import OBJ_METRIC_NAMES  # noqa: E402,F401
@@ -1302,15 +1168,14 @@ class ObjectMetrics:
         """pd_rt, gt_rt (n,3,4), cam_intr (n,3,3) fp64, obj_id (n,) int32 -> (n,16) fp64 in the order of OBJ_METRIC_NAMES."""
         n = pd_rt.shape[0]
         assert gt_rt.shape == (n, 3, 4) and pd_rt.shape == (n, 3, 4) and cam_intr.shape == (n, 3, 3) and obj_id.shape == (n,)
-        need = lib.vpho_obj_metrics_workspace_bytes(C.byref(self.c), I(n), I(self.max_verts))
+        need = abi.query('vpho_obj_metrics_workspace_bytes', C.byref(self.c), n, self.max_verts)
         if need < 0:
             raise VphoError('vpho_obj_metrics_workspace_bytes: bad argument')
         # a fresh block from torch's caching allocator per call (stream-ordered reuse): one object serves the evaluator's slots, whose
         # streams run concurrently -- a workspace kept on the object would be shared by kernels of different streams
         ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         out = _new((n, 16), pd_rt, torch.float64)
-        _call('vpho_obj_metrics_f64', C.byref(self.c), _f64(pd_rt), _f64(gt_rt), _f64(cam_intr), _i32(obj_id), I(n), I(self.max_verts),
-              _f64(out), _ptr(ws), LL(ws.numel()))
+        _call('vpho_obj_metrics_f64', C.byref(self.c), pd_rt, gt_rt, cam_intr, obj_id, n, self.max_verts, out, ws, ws.numel())
         return out
 
     def multi(self, pd_rt, gt_rt, cam_intr, obj_id):
@@ -1319,19 +1184,16 @@ class ObjectMetrics:
         per-candidate (n,S,16), best-of-S (n,16) and mean-of-S (n,16) fp64, columns in the order of OBJ_METRIC_NAMES."""
         n, S = pd_rt.shape[:2]
         assert pd_rt.shape == (n, S, 3, 4) and gt_rt.shape == (n, 3, 4) and cam_intr.shape == (n, 3, 3) and obj_id.shape == (n,)
-        need = lib.vpho_obj_metrics_multi_workspace_bytes(C.byref(self.c), I(n), I(S), I(self.max_verts))
+        need = abi.query('vpho_obj_metrics_multi_workspace_bytes', C.byref(self.c), n, S, self.max_verts)
         if need < 0:
             raise VphoError('vpho_obj_metrics_multi_workspace_bytes: bad argument')
         ws = torch.empty(need, dtype=torch.uint8, device=self.device)          # per call, as in __call__
         per, best, mean = _new((n, S, 16), pd_rt, torch.float64), _new((n, 16), pd_rt, torch.float64), _new((n, 16), pd_rt, torch.float64)
-        _call('vpho_obj_metrics_multi_f64', C.byref(self.c), _f64(pd_rt), _f64(gt_rt), _f64(cam_intr), _i32(obj_id), I(n), I(S),
-              I(self.max_verts), _f64(per), _f64(best), _f64(mean), _ptr(ws), LL(ws.numel()))
+        _call('vpho_obj_metrics_multi_f64', C.byref(self.c), pd_rt, gt_rt, cam_intr, obj_id, n, S, self.max_verts, per, best, mean, ws, ws.numel())
         return per, best, mean
 
 
-class ObjSymmetryTables(C.Structure):
-    _fields_ = [('sym_R', C.c_void_p), ('sym_t', C.c_void_p), ('bbox3d', C.c_void_p), ('verts_sampled', C.c_void_p), ('diameter', C.c_void_p),
-                ('K', I), ('n_obj', I), ('n_sampled', I)]
+ObjSymmetryTables = abi.struct('vpho_obj_symmetry_tables')
 
 
 SYMMETRY_MAX_TRANSFORMS = 4096           # vpho_obj_symmetry_multi_f64: symmetry transforms per object
@@ -1391,8 +1253,7 @@ class ObjectSymmetry:
             raise VphoError('vpho_amd ops take GPU tensors only (no CPU path)')
         obj_id = self._check_ids(obj_id, n)
         per = _new((n, S, 3), pd_rt, torch.float64)
-        _call('vpho_obj_symmetry_multi_f64', C.byref(self.c), _f64(pd_rt), _f64(gt_rt), _i32(obj_id), I(n), I(S),
-              I(int(self.prune if prune is None else prune)), _f64(per))
+        _call('vpho_obj_symmetry_multi_f64', C.byref(self.c), pd_rt, gt_rt, obj_id, n, S, int(self.prune if prune is None else prune), per)
         return per
 
     def __call__(self, pd_rt, gt_rt, obj_id, prune=None):
@@ -1406,24 +1267,14 @@ class ObjectSymmetry:
         per = self.per_hypothesis(pd_rt, gt_rt, obj_id, prune)
         n, S = per.shape[:2]
         one, best, mean = (_new((n, 3), per, torch.float64) for _ in range(3))
-        _call('vpho_obj_symmetry_table_f64', _f64(per), I(n), I(S), _f64(one), _f64(best), _f64(mean))
+        _call('vpho_obj_symmetry_table_f64', per, n, S, one, best, mean)
         return per, best, mean
 
 
-class ObjMeshTables(C.Structure):
-    _fields_ = [('tri', C.c_void_p), ('tri_offset', C.c_void_p), ('scale', C.c_void_p), ('translate', C.c_void_p), ('n_obj', I)]
-
-
-class ObjMeshAccel(C.Structure):
-    _fields_ = [('col_offset', C.c_void_p), ('col_tri', C.c_void_p), ('clu_offset', C.c_void_p), ('clu_sphere', C.c_void_p), ('clu_geo', C.c_void_p)]
-
-
-class ObjSolids(C.Structure):
-    _fields_ = [('pts', C.c_void_p), ('pt_offset', C.c_void_p), ('n_obj', I), ('max_pts', I)]
-
-
-class ObjSolidColumns(C.Structure):
-    _fields_ = [('col_start', C.c_void_p), ('col_offset', C.c_void_p), ('n_obj', I), ('max_cols', I)]
+ObjMeshTables = abi.struct('vpho_obj_mesh_tables')
+ObjMeshAccel = abi.struct('vpho_obj_mesh_accel')
+ObjSolids = abi.struct('vpho_obj_solids')
+ObjSolidColumns = abi.struct('vpho_obj_solid_columns')
 
 
 VOLUME_MULTI_MAX_PAIRS = 0x7fffffff      # vpho_hand_obj_intersection_multi_f64: one workgroup per (image, hypothesis) on grid.x
@@ -1540,12 +1391,12 @@ class HandObjectPenetration:
         fl = _new((n, sol['max_pts']), obj_rt, torch.uint8) if flags else None
         if n == 0:
             return (out, fl) if flags else out
-        need = lib.vpho_hand_obj_intersection_workspace_bytes(I(n), I(F_))
+        need = abi.query('vpho_hand_obj_intersection_workspace_bytes', n, F_)
         if need < 0:
             raise VphoError('vpho_hand_obj_intersection_workspace_bytes: bad argument')
         ws = torch.empty(need, dtype=torch.uint8, device=self.device)          # per call: one object serves streams that run concurrently
-        _call('vpho_hand_obj_intersection_f64', C.byref(self.c), C.byref(sol['c']), _i32(self.hand_faces), I(F_), _f32(verts), I(n), I(V),
-              _f64(obj_rt), _i32(obj_id), C.c_double(pitch), _f64(out), _u8(fl), _ptr(ws), LL(ws.numel()))
+        _call('vpho_hand_obj_intersection_f64', C.byref(self.c), C.byref(sol['c']), self.hand_faces, F_, verts, n, V, obj_rt, obj_id, pitch, out, fl,
+              ws, ws.numel())
         return (out, fl) if flags else out
 
     def build_solid_columns(self, pitch):
@@ -1599,12 +1450,12 @@ class HandObjectPenetration:
         fl = _new((n, S, sol['max_pts']), obj_rt, torch.uint8) if flags else None
         if n == 0:
             return (table, per, fl) if flags else (table, per)
-        need = lib.vpho_hand_obj_intersection_multi_workspace_bytes(I(n), I(S), I(F_))
+        need = abi.query('vpho_hand_obj_intersection_multi_workspace_bytes', n, S, F_)
         if need < 0:
             raise VphoError('vpho_hand_obj_intersection_multi_workspace_bytes: bad argument')
         ws = torch.empty(need, dtype=torch.uint8, device=self.device) if need else None       # per call, as in volume
-        _call('vpho_hand_obj_intersection_multi_f64', C.byref(self.c), C.byref(sol['c']), C.byref(cols['c']), _i32(self.hand_faces), I(F_),
-              _f32(verts), I(n), I(S), I(V), _f64(obj_rt), _i32(obj_id), C.c_double(pitch), _f64(per), _f64(table), _u8(fl), _ptr(ws), LL(need))
+        _call('vpho_hand_obj_intersection_multi_f64', C.byref(self.c), C.byref(sol['c']), C.byref(cols['c']), self.hand_faces, F_, verts, n, S, V,
+              obj_rt, obj_id, pitch, per, table, fl, ws, need)
         return (table, per, fl) if flags else (table, per)
 
     def _check_ids(self, obj_id, n):
@@ -1647,8 +1498,7 @@ class HandObjectPenetration:
         per = _new((n, 4), obj_rt, torch.float64)
         sd = _new((n, V), obj_rt, torch.float64)
         inside = _new((n, V), obj_rt, torch.uint8)
-        _call('vpho_hand_obj_penetration_f64', C.byref(self.c), _f32(verts), I(n), I(V), _f64(obj_rt), _i32(obj_id), C.c_double(contact_thresh),
-              _f64(sd), _u8(inside), _f64(per))
+        _call('vpho_hand_obj_penetration_f64', C.byref(self.c), verts, n, V, obj_rt, obj_id, contact_thresh, sd, inside, per)
         return (per, sd, inside) if per_vertex else per
 
     def multi(self, verts, obj_rt, obj_id, per_vertex=False, contact_thresh=0.005):
@@ -1666,13 +1516,12 @@ class HandObjectPenetration:
         per = _new((n, S, 4), obj_rt, torch.float64)
         sd = _new((n, S, V), obj_rt, torch.float64) if per_vertex else None
         inside = _new((n, S, V), obj_rt, torch.uint8) if per_vertex else None
-        _call('vpho_hand_obj_penetration_multi_f64', C.byref(self.c), C.byref(self.acc), _f32(verts), I(n), I(S), I(V), _f64(obj_rt), _i32(obj_id),
-              C.c_double(contact_thresh), _f64(per), _f64(sd) if per_vertex else None, _u8(inside) if per_vertex else None, _f64(table))
+        _call('vpho_hand_obj_penetration_multi_f64', C.byref(self.c), C.byref(self.acc), verts, n, S, V, obj_rt, obj_id, contact_thresh, per,
+              sd if per_vertex else None, inside if per_vertex else None, table)
         return (table, per, sd, inside) if per_vertex else (table, per)
 
 
-class ObjVertexAccel(C.Structure):
-    _fields_ = [(k, C.c_void_p) for k in ('vert', 'index', 'clu_offset', 'clu_start', 'clu_sphere')] + [('n_obj', I)]
+ObjVertexAccel = abi.struct('vpho_obj_vertex_accel')
 
 
 class ContactMulti:
@@ -1708,9 +1557,8 @@ class ContactMulti:
         w = _new((n, S, Nh), hand_verts)
         nn = _new((n, S, Nh), hand_verts, torch.int32) if per_vertex else None
         nd, vd = (_new((n, S, Nh), hand_verts, torch.float64) for _ in range(2)) if per_vertex else (None, None)
-        _call('vpho_contact_multi_f32', C.byref(self.c), _f32(hand_verts), _f32(hand_normals), I(n), I(S), I(Nh), _f64(root), _u8(is_right),
-              _f64(obj_rt), _i32(obj_id), F(normal_thresh[0]), F(normal_thresh[1]), F(vertical_thresh), F(decay[0]), F(decay[1]),
-              _f32(w), None if nn is None else _i32(nn), _f64(nd), _f64(vd))
+        _call('vpho_contact_multi_f32', C.byref(self.c), hand_verts, hand_normals, n, S, Nh, root, is_right, obj_rt, obj_id, normal_thresh[0],
+              normal_thresh[1], vertical_thresh, decay[0], decay[1], w, nn, nd, vd)
         return (w, nn, nd, vd) if per_vertex else w
 
 
@@ -1725,18 +1573,12 @@ def contact_agreement(weight, weight_gt, force_contact, is_grasped, force_contac
                         f'is_grasped {tuple(is_grasped.shape)}, force_contact_gt {tuple(force_contact_gt.shape)}, is_grasped_gt {tuple(is_grasped_gt.shape)}')
     counts = _new((n, S, 3), weight, torch.int32)
     values, table = _new((n, S, 8), weight, torch.float64), _new((n, 24), weight, torch.float64)
-    _call('vpho_contact_agreement_f32', _f32(weight), _f32(weight_gt), _f32(force_contact), _u8(is_grasped), _f32(force_contact_gt),
-          _u8(is_grasped_gt), I(n), I(S), I(Nh), _i32(counts), _f64(values), _f64(table))
+    _call('vpho_contact_agreement_f32', weight, weight_gt, force_contact, is_grasped, force_contact_gt, is_grasped_gt, n, S, Nh, counts, values,
+          table)
     return counts, values, table
 
 
 # ----------------------------------------------------------------------------------------------- score-network training
-def _at(t, off=0):
-    """device address of element `off` of a contiguous fp32 tensor"""
-    _ptr(t, torch.float32)
-    return C.c_void_p(t.data_ptr() + 4 * off)
-
-
 def linear_into(x, w, bias, out, c_off, out_slope=1.0):
     """out[:, c_off : c_off + cout] = act(x @ w.T + bias) for a wider row-major `out` (concatenation buffers)."""
     rows, cin = x.shape
@@ -1750,14 +1592,14 @@ def dsm_prepare(gt_pose, t, z, fourier_W, Dp):
     reps, bs = t.shape
     D = gt_pose.shape[1]
     xt, emb, sd = _new((reps * bs, Dp), gt_pose), _new((reps * bs, 128), gt_pose), _new((reps * bs,), gt_pose)
-    _call('vpho_dsm_prepare_f32', _f32(gt_pose), _f32(t), _f32(z), _f32(fourier_W), I(bs), I(reps), I(D), I(Dp), _f32(xt), _f32(emb), _f32(sd))
+    _call('vpho_dsm_prepare_f32', gt_pose, t, z, fourier_W, bs, reps, D, Dp, xt, emb, sd)
     return xt, emb, sd
 
 
 def plinear2_fwd(h, w2, b2, std_rows, nheads):
     rows = h.shape[0]
     score = _new((rows, 3 * nheads), h)
-    _call('vpho_plinear2_fwd_f32', _f32(h), _f32(w2), _f32(b2), _f32(std_rows), LL(rows), I(nheads), _f32(score))
+    _call('vpho_plinear2_fwd_f32', h, w2, b2, std_rows, rows, nheads, score)
     return score
 
 
@@ -1767,7 +1609,7 @@ def dsm_loss(score, z, std_rows, batch_times_reps):
     dout = torch.empty_like(score)
     loss = _new((), score, torch.float64)
     ws = _new((1024,), score, torch.float64)
-    _call('vpho_dsm_loss_f32', _f32(score), _f32(z), _f32(std_rows), LL(rows), I(D), I(batch_times_reps), _f32(dout), _f64(loss), _f64(ws), I(1024))
+    _call('vpho_dsm_loss_f32', score, z, std_rows, rows, D, batch_times_reps, dout, loss, ws, 1024)
     return loss, dout
 
 
@@ -1777,21 +1619,21 @@ def mse_loss(pd, gt, weight=1.0):
     grad = torch.empty_like(pd)
     loss = _new((), pd, torch.float64)
     ws = _new((1024,), pd, torch.float64)
-    _call('vpho_mse_loss_f32', _f32(pd), _f32(gt), LL(pd.numel()), F(weight), _f32(grad), _f64(loss), _f64(ws), I(1024))
+    _call('vpho_mse_loss_f32', pd, gt, pd.numel(), weight, grad, loss, ws, 1024)
     return loss, grad
 
 
 def plinear2_bwd(h, dout, w2, nheads):
     rows = h.shape[0]
     dpre, dw2, db2 = torch.empty_like(h), torch.empty_like(w2), _new((nheads, 3), h)
-    _call('vpho_plinear2_bwd_f32', _f32(h), _f32(dout), _f32(w2), LL(rows), I(nheads), _f32(dpre), _f32(dw2), _f32(db2))
+    _call('vpho_plinear2_bwd_f32', h, dout, w2, rows, nheads, dpre, dw2, db2)
     return dpre, dw2, db2
 
 
 def relu_bwd(dy, dy_off, ld_dy, y, y_off, ld_y, rows, cols):
     """contiguous (rows, cols) = where(y_slice > 0, dy_slice, 0); slices are given by element offset + leading dimension"""
     dx = _new((rows, cols), dy)
-    _call('vpho_relu_bwd_f32', _at(dy, dy_off), I(ld_dy), _at(y, y_off), I(ld_y), LL(rows), I(cols), _f32(dx), I(cols))
+    _call('vpho_relu_bwd_f32', abi.at(dy, torch.float32, dy_off), ld_dy, abi.at(y, torch.float32, y_off), ld_y, rows, cols, dx, cols)
     return dx
 
 
@@ -1799,13 +1641,13 @@ def colsum(x):
     rows, cols = x.shape
     out = _new((cols,), x)
     ws = _bn_workspace(cols, x.device)
-    _call('vpho_colsum_f32', _f32(x), I(cols), LL(rows), I(cols), _f32(out), _ptr(ws))
+    _call('vpho_colsum_f32', x, cols, rows, cols, out, ws)
     return out
 
 
 def sum_repeats(x, c_off, bs, reps, cols):
     out = _new((bs, cols), x)
-    _call('vpho_sum_repeats_f32', _f32(x), I(x.shape[1]), I(c_off), I(bs), I(reps), I(cols), _f32(out))
+    _call('vpho_sum_repeats_f32', x, x.shape[1], c_off, bs, reps, cols, out)
     return out
 
 
@@ -1815,7 +1657,7 @@ def transpose(x, pad_to=4):
     rows, cols = x.shape
     rp = (rows + pad_to - 1) // pad_to * pad_to
     y = _new((cols, rp), x) if rp == rows else torch.zeros((cols, rp), device=x.device, dtype=x.dtype)
-    _call('vpho_transpose_f32', _f32(x), I(rows), I(cols), I(cols), _f32(y), I(rp))
+    _call('vpho_transpose_f32', x, rows, cols, cols, y, rp)
     return y
 
 
@@ -1826,7 +1668,7 @@ def im2col_t(x, kh, kw, stride, pad_y, pad_x, OH, OW, cin=None):
     P = N * OH * OW
     ldo = (P + 3) // 4 * 4
     out = _new((kh * kw * cin, ldo), x)
-    _call('vpho_im2col_t_f32', _f32(x), I(N), I(H), I(W), I(cin), I(ld), I(kh), I(kw), I(stride), I(pad_y), I(pad_x), I(OH), I(OW), _f32(out), LL(ldo))
+    _call('vpho_im2col_t_f32', x, N, H, W, cin, ld, kh, kw, stride, pad_y, pad_x, OH, OW, out, ldo)
     return out
 
 
@@ -1836,7 +1678,7 @@ def window_groups(win):
     N, H, W = win.shape
     lst = torch.empty((N * H * W // 32,), device=win.wins.device, dtype=torch.int32)
     cnt = torch.empty((1,), device=win.wins.device, dtype=torch.int32)
-    _call('vpho_window_groups_i32', _i32(win.wins), I(N), I(H), I(W), _i32(lst), _i32(cnt))
+    _call('vpho_window_groups_i32', win.wins, N, H, W, lst, cnt)
     return lst, cnt
 
 
@@ -1847,14 +1689,13 @@ def conv2d_wgrad_nhwc(x, dy, kh, kw, stride, pad_y, pad_x, cin=None, groups=None
     _, OH, OW, cout = dy.shape
     cin = ld if cin is None else cin
     dw = _new((cout, kh * kw * cin), x)
-    nbytes = lib.vpho_conv2d_wgrad_workspace_bytes(I(N), I(OH), I(OW), I(cin), I(cout), I(kh), I(kw))
+    nbytes = abi.query('vpho_conv2d_wgrad_workspace_bytes', N, OH, OW, cin, cout, kh, kw)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes > 0 else None
     if groups is not None and OW % 32 == 0:
-        _call('vpho_conv2d_wgrad_groups_nhwc_f32', _f32(x), I(N), I(H), I(W), I(cin), I(ld), _f32(dy), I(OH), I(OW), I(cout), I(cout),
-              I(kh), I(kw), I(stride), I(pad_y), I(pad_x), _i32(groups[0]), _i32(groups[1]), _f32(dw), _ptr(ws))
+        _call('vpho_conv2d_wgrad_groups_nhwc_f32', x, N, H, W, cin, ld, dy, OH, OW, cout, cout, kh, kw, stride, pad_y, pad_x, groups[0], groups[1],
+              dw, ws)
         return dw
-    _call('vpho_conv2d_wgrad_nhwc_f32', _f32(x), I(N), I(H), I(W), I(cin), I(ld), _f32(dy), I(OH), I(OW), I(cout), I(cout),
-          I(kh), I(kw), I(stride), I(pad_y), I(pad_x), _f32(dw), _ptr(ws))
+    _call('vpho_conv2d_wgrad_nhwc_f32', x, N, H, W, cin, ld, dy, OH, OW, cout, cout, kh, kw, stride, pad_y, pad_x, dw, ws)
     return dw
 
 
@@ -1865,7 +1706,7 @@ def _bn_workspace(Cc, device):
     """scratch of the BatchNorm reductions (256 chunks x 2 x C doubles), one per (device, stream): every user is stream-ordered and done with it
     when its call's last kernel has run; allocating it per call cost the training step ~270 allocator round trips"""
     key = (device.index if device.index is not None else torch.cuda.current_device(), torch.cuda.current_stream(device).cuda_stream)
-    need = lib.vpho_bn_workspace_bytes(I(Cc))
+    need = abi.query('vpho_bn_workspace_bytes', Cc)
     ws = _BN_WS.get(key)
     if ws is None or ws.numel() < need:
         ws = _BN_WS[key] = torch.empty(max(need, 256 * 2 * 2048 * 8), dtype=torch.uint8, device=device)
@@ -1881,11 +1722,10 @@ def bn_train_forward(x, gamma, beta, running_mean=None, running_var=None, eps=1e
     ws = _bn_workspace(Cc, x.device)
     if partials is not None and partials.live():
         assert partials.stats.shape[-1] == Cc
-        _call('vpho_bn_train_forward_stats_f32', _f32(x), LL(rows), I(Cc), I(Cc), _f32(partials.stats), I(partials.rows), _f32(gamma), _f32(beta), F(eps), F(momentum),
-              F(slope), _f32(running_mean), _f32(running_var), _f32(mean), _f32(invstd), _f32(res), _f32(y), _ptr(ws))
+        _call('vpho_bn_train_forward_stats_f32', x, rows, Cc, Cc, partials.stats, partials.rows, gamma, beta, eps, momentum, slope, running_mean,
+              running_var, mean, invstd, res, y, ws)
         return y, (mean, invstd)
-    _call('vpho_bn_train_forward_f32', _f32(x), LL(rows), I(Cc), I(Cc), _f32(gamma), _f32(beta), F(eps), F(momentum), F(slope),
-          _f32(running_mean), _f32(running_var), _f32(mean), _f32(invstd), _f32(res), _f32(y), _ptr(ws))
+    _call('vpho_bn_train_forward_f32', x, rows, Cc, Cc, gamma, beta, eps, momentum, slope, running_mean, running_var, mean, invstd, res, y, ws)
     return y, (mean, invstd)
 
 
@@ -1903,16 +1743,16 @@ def bn_train_backward(x, dy, gamma, saved, partials=None, res=None, want_colsum=
         if live:
             assert partials.stats.shape[-1] == Cc
         assert res is None or (res.shape == x.shape and res.is_contiguous())
-        _call('vpho_bn_train_backward_stats_f32', _f32(x), _f32(dy), LL(rows), I(Cc), I(Cc), _f32(gamma), _f32(saved[0]), _f32(saved[1]),
-              _f32(partials.stats) if live else None, I(partials.rows if live else 0), _f32(res), _f32(dx), _f32(dg), _f32(db), _f32(cs), _ptr(ws))
+        _call('vpho_bn_train_backward_stats_f32', x, dy, rows, Cc, Cc, gamma, saved[0], saved[1], partials.stats if live else None,
+              partials.rows if live else 0, res, dx, dg, db, cs, ws)
         return (dx, dg, db, cs) if want_colsum else (dx, dg, db)
-    _call('vpho_bn_train_backward_f32', _f32(x), _f32(dy), LL(rows), I(Cc), I(Cc), _f32(gamma), _f32(saved[0]), _f32(saved[1]), _f32(dx), _f32(dg), _f32(db), _ptr(ws))
+    _call('vpho_bn_train_backward_f32', x, dy, rows, Cc, Cc, gamma, saved[0], saved[1], dx, dg, db, ws)
     return dx, dg, db
 
 
 def lrelu_bwd(dy, y, slope):
     dx = torch.empty_like(dy)
-    _call('vpho_lrelu_bwd_f32', _f32(dy), _f32(y), LL(dy.numel()), F(slope), _f32(dx))
+    _call('vpho_lrelu_bwd_f32', dy, y, dy.numel(), slope, dx)
     return dx
 
 
@@ -1921,18 +1761,18 @@ def maxpool_bwd(x, dy, k, stride, pad, one_pass=False):
     N, H, W, Cc = x.shape
     dx = torch.empty_like(x)
     if one_pass:
-        _call('vpho_maxpool_bwd_nhwc_f32', _f32(x), _f32(dy), I(N), I(H), I(W), I(Cc), I(k), I(stride), I(pad), _f32(dx))
+        _call('vpho_maxpool_bwd_nhwc_f32', x, dy, N, H, W, Cc, k, stride, pad, dx)
         return dx
-    need = lib.vpho_maxpool_bwd_workspace_bytes(N, H, W, Cc, k, stride, pad)
+    need = abi.query('vpho_maxpool_bwd_workspace_bytes', N, H, W, Cc, k, stride, pad)
     ws = torch.empty(need, dtype=torch.uint8, device=x.device) if need > 0 else None
-    _call('vpho_maxpool_bwd_ws_nhwc_f32', _f32(x), _f32(dy), I(N), I(H), I(W), I(Cc), I(k), I(stride), I(pad), _f32(dx), _u8(ws))
+    _call('vpho_maxpool_bwd_ws_nhwc_f32', x, dy, N, H, W, Cc, k, stride, pad, dx, abi.at(ws, torch.uint8))
     return dx
 
 
 def resize_bilinear_bwd(dy, H, W):
     N, OH, OW, Cc = dy.shape
     dx = _new((N, H, W, Cc), dy)
-    _call('vpho_resize_bilinear_bwd_nhwc_f32', _f32(dy), I(N), I(OH), I(OW), I(Cc), I(H), I(W), _f32(dx))
+    _call('vpho_resize_bilinear_bwd_nhwc_f32', dy, N, OH, OW, Cc, H, W, dx)
     return dx
 
 
@@ -1941,27 +1781,26 @@ def roi_align_bwd(dy, boxes, feat_hw, C, scale, flip_w=None, c_off=0, into=None)
     N, P, _, ld = dy.shape
     H, W = feat_hw
     df = torch.zeros((N, H, W, C), device=dy.device, dtype=dy.dtype) if into is None else into
-    _call('vpho_roi_align_bwd_nhwc_f32', _f32(dy), I(ld), I(c_off), I(N), I(H), I(W), I(C), _f32(boxes), F(scale), I(P), _u8(flip_w), _f32(df))
+    _call('vpho_roi_align_bwd_nhwc_f32', dy, ld, c_off, N, H, W, C, boxes, scale, P, flip_w, df)
     return df
 
 
 def align_heatmap_bwd(dout, bbox, bbox_rect, flip_w=None):
     N, S, _, Cc = dout.shape
     dhm = torch.zeros_like(dout)
-    _call('vpho_align_heatmap_bwd_nhwc_f32', _f32(dout), I(N), I(S), I(Cc), _f32(bbox), _f32(bbox_rect), _u8(flip_w), _f32(dhm))
+    _call('vpho_align_heatmap_bwd_nhwc_f32', dout, N, S, Cc, bbox, bbox_rect, flip_w, dhm)
     return dhm
 
 
 def add_lrelu(a, b, slope=1.0):
     y = torch.empty_like(a)
-    _call('vpho_add_lrelu_f32', _f32(a), _f32(b), LL(a.numel()), F(slope), _f32(y))
+    _call('vpho_add_lrelu_f32', a, b, a.numel(), slope, y)
     return y
 
 
 def adamw_(param, grad, m, v, step, lr=2e-4, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.01, grad_scale=1.0):
     """in-place torch.optim.AdamW step on one tensor"""
-    _call('vpho_adamw_f32', _f32(param), _f32(grad), _f32(m), _f32(v), LL(param.numel()), F(lr), F(beta1), F(beta2), F(eps), F(weight_decay),
-          I(step), F(grad_scale))
+    _call('vpho_adamw_f32', param, grad, m, v, param.numel(), lr, beta1, beta2, eps, weight_decay, step, grad_scale)
 
 
 class AdamWList:
@@ -1971,7 +1810,7 @@ class AdamWList:
         rows, blk = [], 0
         for p, g, m, v in quads:
             for t in (p, g, m, v):
-                _ptr(t, torch.float32)
+                _f32p(t)
             assert p.numel() == g.numel() == m.numel() == v.numel()
             rows.append([p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), blk])
             blk += (p.numel() + 1023) // 1024
@@ -1979,8 +1818,7 @@ class AdamWList:
         self.table = torch.tensor(rows, dtype=torch.int64).to(quads[0][0].device)
 
     def step(self, step, lr=2e-4, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.01, grad_scale=1.0):
-        _call('vpho_adamw_multi_f32', _ptr(self.table, torch.int64), I(self.n), LL(self.blocks), F(lr), F(beta1), F(beta2), F(eps), F(weight_decay),
-              I(step), F(grad_scale))
+        _call('vpho_adamw_multi_f32', abi.at(self.table, torch.int64), self.n, self.blocks, lr, beta1, beta2, eps, weight_decay, step, grad_scale)
         # the kernel wrote through raw pointers: tell torch, so that everything cached per weight VERSION (the Winograd transforms of
         # winograd_weights_device, the bf16 planes) is rebuilt -- no launch, a counter per tensor
         torch.autograd.graph.increment_version([q[0] for q in self.keep])
@@ -1990,7 +1828,7 @@ def grad_sqnorm(flat, ws=None, out=None):
     """sum of squares of a contiguous fp32 buffer -> 0-d fp64 tensor that stays on the device (fixed summation order: two runs give the
     same bits).  ``ws``: a uint8 workspace of at least ``grad_sqnorm_workspace_bytes(n)`` bytes to reuse; ``out``: a 0-d fp64 tensor to write"""
     n = flat.numel()
-    need = lib.vpho_grad_sqnorm_workspace_bytes(LL(n))
+    need = abi.query('vpho_grad_sqnorm_workspace_bytes', n)
     if need < 0:
         raise VphoError(f'vpho_grad_sqnorm_workspace_bytes: bad argument (n={n})')
     if ws is None:
@@ -1999,12 +1837,12 @@ def grad_sqnorm(flat, ws=None, out=None):
         raise VphoError(f'grad_sqnorm: a workspace of {ws.numel() * ws.element_size()} bytes, {need} are needed')
     if out is None:
         out = _new((), flat, torch.float64)
-    _call('vpho_grad_sqnorm_f64', _f32(flat), LL(n), _f64(out), _ptr(ws))
+    _call('vpho_grad_sqnorm_f64', flat, n, out, ws)
     return out
 
 
 def grad_sqnorm_workspace_bytes(n):
-    return int(lib.vpho_grad_sqnorm_workspace_bytes(LL(n)))
+    return int(abi.query('vpho_grad_sqnorm_workspace_bytes', n))
 
 
 OPTIM_KINDS = {'adamw': 0, 'adam': 1}
@@ -2019,7 +1857,7 @@ class OptimList:
         rows, blk = [], 0
         for p, g, m, v in quads:
             for t in (p, g, m, v):
-                _ptr(t, torch.float32)
+                _f32p(t)
             assert p.numel() == g.numel() == m.numel() == v.numel()
             rows.append([p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), blk])
             blk += (p.numel() + 1023) // 1024
@@ -2029,8 +1867,8 @@ class OptimList:
     def step(self, step, kind=0, lr=2e-4, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.01, grad_scale=1.0, sqnorm=None, max_norm=0.0):
         if sqnorm is not None and not (sqnorm.numel() == 1 and max_norm > 0):
             raise VphoError(f'OptimList.step: clipping needs one fp64 value and max_norm > 0 (got {tuple(sqnorm.shape)}, {max_norm})')
-        _call('vpho_optim_multi_f32', _ptr(self.table, torch.int64), I(self.n), LL(self.blocks), I(OPTIM_KINDS.get(kind, kind)), F(lr), F(beta1),
-              F(beta2), F(eps), F(weight_decay), I(step), F(grad_scale), _f64(sqnorm), F(max_norm))
+        _call('vpho_optim_multi_f32', abi.at(self.table, torch.int64), self.n, self.blocks, OPTIM_KINDS.get(kind, kind), lr, beta1, beta2, eps, weight_decay, step,
+              grad_scale, sqnorm, max_norm)
         # raw-pointer writes: bump the version counters, as AdamWList.step does (Winograd transforms and bf16 planes are cached per version)
         torch.autograd.graph.increment_version([q[0] for q in self.keep])
 
@@ -2044,7 +1882,7 @@ class EmaList:
         rows, blk = [], 0
         for p, s in pairs:
             for t in (p, s):
-                _ptr(t, torch.float32)
+                _f32p(t)
             if p.device != s.device:
                 raise VphoError(f'EmaList: parameter on {p.device}, shadow on {s.device}')
             if p.numel() != s.numel():
@@ -2057,7 +1895,7 @@ class EmaList:
     def update(self, one_minus_decay):
         if self.n == 0:
             return
-        _call('vpho_ema_multi_f32', _ptr(self.table, torch.int64), I(self.n), LL(self.blocks), F(one_minus_decay))
+        _call('vpho_ema_multi_f32', abi.at(self.table, torch.int64), self.n, self.blocks, one_minus_decay)
         torch.autograd.graph.increment_version([q[1] for q in self.keep])
 
 
@@ -2079,8 +1917,7 @@ def frame_patch(frames, minv, patch, colour=None, flip=None, erase=None, key=Non
         out = _new((n, 3, patch, patch), frames)
     elif tuple(out.shape) != (n, 3, patch, patch):
         raise VphoError(f'frame_patch: out of shape {tuple(out.shape)}, expected {(n, 3, patch, patch)}')
-    _call('vpho_frame_patch_f32', _u8(frames), I(n), I(H), I(W), _f64(minv), _f32(colour), _u8(flip), None if erase is None else _i32(erase),
-          None if key is None else _i32(key), I(patch), _f32(out))
+    _call('vpho_frame_patch_f32', frames, n, H, W, minv, colour, flip, erase, key, patch, out)
     return out
 
 
@@ -2100,8 +1937,7 @@ def heatmap_targets(pts, box, g, sigma, gmin, size, res=None, left=None, out=Non
         out = _new((n, J, size, size), pts)
     elif tuple(out.shape) != (n, J, size, size):
         raise VphoError(f'heatmap_targets: out of shape {tuple(out.shape)}, expected {(n, J, size, size)}')
-    _call('vpho_heatmap_targets_f32', _f64(pts), _f64(box), None if res is None else _i32(res), _u8(left), _f32(g), I(g.shape[0]), C.c_double(sigma),
-          C.c_double(gmin), I(n), I(J), I(size), I(0 if res is None else 1), _f32(out))
+    _call('vpho_heatmap_targets_f32', pts, box, res, left, g, g.shape[0], sigma, gmin, n, J, size, 0 if res is None else 1, out)
     return out
 
 
@@ -2147,7 +1983,7 @@ def photo_levels(frames, minv, patch, out=None):
     if n > 65535 or patch < 1 or patch > 16384:
         raise VphoError(f'photo_levels: n {n} / patch {patch} beyond 65535 images of 16384 pixels a side')
     out = _photo_out('photo_levels', out, (n, patch, patch, 3), frames, torch.uint8)
-    _call('vpho_photo_levels_u8', _u8(frames), I(n), I(H), I(W), _f64(minv), I(patch), _u8(out))
+    _call('vpho_photo_levels_u8', frames, n, H, W, minv, patch, out)
     return out
 
 
@@ -2158,7 +1994,7 @@ def photo_clahe_lut(levels, clip):
     n, P = _photo_levels('photo_clahe_lut', levels, clahe=True)
     clip = _photo_host_ints('photo_clahe_lut', 'clip', clip, n, lambda k: 0 <= k <= P * P, 'a clip count in 0 .. P * P').to(levels.device)
     l8, lut = _new((n, P, P), levels, torch.uint8), _new((n, 64, 256), levels, torch.uint8)
-    _call('vpho_photo_clahe_lut_u8', _u8(levels), _i32(clip), I(n), I(P), _u8(l8), _u8(lut))
+    _call('vpho_photo_clahe_lut_u8', levels, clip, n, P, l8, lut)
     return l8, lut, clip
 
 
@@ -2171,7 +2007,7 @@ def photo_clahe_apply(levels, clip, l8, lut, out=None, want_l8=False):
             raise VphoError(f'photo_clahe_apply: {name} must be {shape} {dt}')
     out = _photo_out('photo_clahe_apply', out, (n, P, P, 3), levels, torch.uint8)
     l8o = _new((n, P, P), levels, torch.uint8) if want_l8 else None
-    _call('vpho_photo_clahe_apply_u8', _u8(levels), _i32(clip), _u8(l8), _u8(lut), I(n), I(P), _u8(out), _u8(l8o))
+    _call('vpho_photo_clahe_apply_u8', levels, clip, l8, lut, n, P, out, l8o)
     return (out, l8o) if want_l8 else out
 
 
@@ -2186,7 +2022,7 @@ def photo_grey_sum(levels, colour=None):
     n, P = _photo_levels('photo_grey_sum', levels)
     _photo_rows('photo_grey_sum', 'colour', colour, (n, 5))
     sums = torch.zeros(n, dtype=torch.int64, device=levels.device)
-    _call('vpho_photo_grey_sum_u8', _u8(levels), _f32(colour), I(n), I(P), _ptr(sums, torch.int64))
+    _call('vpho_photo_grey_sum_u8', levels, colour, n, P, sums)
     return sums
 
 
@@ -2200,8 +2036,7 @@ def photo_colour(levels, colour=None, contrast=None, hue=None, sums=None, out=No
     if contrast is not None and (sums is None or tuple(sums.shape) != (n,) or sums.dtype != torch.int64):
         raise VphoError('photo_colour: contrast factors need the (n) int64 grey sums of photo_grey_sum')
     out = _photo_out('photo_colour', out, (n, P, P, 3), levels, torch.uint8)
-    _call('vpho_photo_colour_u8', _u8(levels), _f32(colour), _f32(contrast), _f32(hue), None if sums is None else _ptr(sums, torch.int64), I(n), I(P),
-          _u8(out))
+    _call('vpho_photo_colour_u8', levels, colour, contrast, hue, sums, n, P, out)
     return out
 
 
@@ -2223,22 +2058,13 @@ def photo_filter(levels, k1, K1, k2, K2, flip=None, erase=None, key=None, out=No
     if erase is not None and key is None:
         raise VphoError('photo_filter: erase rectangles need a Philox key')
     out = _photo_out('photo_filter', out, (n, 3, P, P), levels, torch.float32)
-    _call('vpho_photo_filter_f32', _u8(levels), _f32(k1), _i32(K1), _f32(k2), _i32(K2), _u8(flip), None if erase is None else _i32(erase),
-          None if key is None else _i32(key), I(n), I(P), _f32(out))
+    _call('vpho_photo_filter_f32', levels, k1, K1, k2, K2, flip, erase, key, n, P, out)
     return out
 
 
 # ----------------------------------------------------------------------------------------------- predictions to pixels (raster.hip)
-class MeshTable(C.Structure):
-    _fields_ = [(k, C.c_void_p) for k in ('faces', 'face_offset', 'vert_count')] + [('M', I)]
-
-
-class RenderLayer(C.Structure):
-    _fields_ = [(k, C.c_void_p) for k in ('depth_front', 'face_front', 'verts', 'mesh_id', 'faces', 'face_offset')] + [('Vmax', I), ('M', I)] + \
-               [(k, F) for k in ('red', 'green', 'blue', 'opacity')]
-
-
-lib.vpho_mesh_raster_bytes.restype = C.c_longlong
+MeshTable = abi.struct('vpho_mesh_table')
+RenderLayer = abi.struct('vpho_render_layer')
 
 
 class MeshRaster:
@@ -2313,14 +2139,13 @@ class MeshRaster:
                 raise VphoError(f'MeshRaster.raster: mesh {i} has {self.vert_counts[i]} vertices, verts holds {Vmax} per image')
         verts, K = verts.float().contiguous(), K.double().contiguous()
         stride = max([self.face_counts[i] for i in host], default=0)
-        size = lib.vpho_mesh_raster_bytes(I(n), I(stride))
+        size = abi.query('vpho_mesh_raster_bytes', n, stride)
         if size < 0:
             raise VphoError(f'vpho_mesh_raster_bytes: n = {n}, face_stride = {stride}')
         ws = torch.empty(max(size, 16), dtype=torch.uint8, device=verts.device)
         df, ff = _new((n, H, W), verts), _new((n, H, W), verts, torch.int32)
         db, fb = (_new((n, H, W), verts), _new((n, H, W), verts, torch.int32)) if back else (None, None)
-        _call('vpho_mesh_raster_f32', C.byref(self.table), _f32(verts), I(Vmax), _i32(ids), _f64(K), I(n), I(H), I(W), I(stride), C.c_double(z_near),
-              _f32(df), _f32(db), _i32(ff), _i32(fb), _ptr(ws))
+        _call('vpho_mesh_raster_f32', C.byref(self.table), verts, Vmax, ids, K, n, H, W, stride, z_near, df, db, ff, fb, ws)
         out = dict(depth_front=df, face_front=ff, verts=verts, mesh_id=ids, mesh_id_host=host, K=K)
         if back:
             out.update(depth_back=db, face_back=fb)
@@ -2343,7 +2168,7 @@ class MeshRaster:
         if not 0.0 <= op <= 1.0:
             raise VphoError(f'MeshRaster.overlay: the {who} layer has opacity {op}, expected 0 .. 1')
         keep = (df, ff, verts, ids)
-        return RenderLayer(_f32(df).value, _i32(ff).value, _f32(verts).value, _i32(ids).value, self.faces.data_ptr(), self.face_offset.data_ptr(), verts.shape[1], self.M,
+        return RenderLayer(_f32p(df), abi.addr(ff, torch.int32), _f32p(verts), abi.addr(ids, torch.int32), self.faces.data_ptr(), self.face_offset.data_ptr(), verts.shape[1], self.M,
                            r, g, b, op), keep
 
     def overlay(self, image, K, hand=None, obj=None, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), ambient=0.3, out=None):
@@ -2365,8 +2190,8 @@ class MeshRaster:
         elif tuple(out.shape) != (n, H, W, 3) or out.dtype != torch.uint8:
             raise VphoError(f'MeshRaster.overlay: out of shape {tuple(out.shape)} / {out.dtype}, expected {(n, H, W, 3)} uint8')
         mean3, std3 = (C.c_float * 3)(*[float(v) for v in mean]), (C.c_float * 3)(*[float(v) for v in std])
-        _call('vpho_render_overlay_u8', _f32(image), mean3, std3, _f64(K), None if lh is None else C.byref(lh), None if lo is None else C.byref(lo),
-              F(ambient), I(n), I(H), I(W), _u8(out))
+        _call('vpho_render_overlay_u8', image, mean3, std3, K, None if lh is None else C.byref(lh), None if lo is None else C.byref(lo), ambient, n,
+              H, W, out)
         del keep_h, keep_o
         return out
 
@@ -2377,24 +2202,24 @@ def cross_tokens_bwd(dtok, want_hand=True, want_obj=True):
     dph = torch.zeros((bs, 8, 8, 256), device=dtok.device) if want_hand else None
     dpo = torch.zeros((bs, 8, 8, 256), device=dtok.device) if want_obj else None
     dge = _new((bs, 512), dtok)
-    _call('vpho_cross_tokens_bwd_f32', _f32(dtok), I(bs), _f32(dph), _f32(dpo), _f32(dge))
+    _call('vpho_cross_tokens_bwd_f32', dtok, bs, dph, dpo, dge)
     return dph, dpo, dge
 
 
 def layernorm_bwd(x, r, gamma, dy, eps=1e-5):
     E = x.shape[-1]
     dx, gx = torch.empty_like(x), torch.empty_like(x)
-    _call('vpho_layernorm_bwd_f32', _f32(x), _f32(r), _f32(gamma), _f32(dy), LL(x.numel() // E), I(E), F(eps), _f32(dx), _f32(gx))
+    _call('vpho_layernorm_bwd_f32', x, r, gamma, dy, x.numel() // E, E, eps, dx, gx)
     return dx, gx
 
 
 def mha_bwd(qkv, d_out, S, B, E, nhead, drop=None):
     dqkv = torch.empty_like(qkv)
-    need = lib.vpho_mha_bwd_workspace_bytes(I(S), I(B), I(nhead))
+    need = abi.query('vpho_mha_bwd_workspace_bytes', S, B, nhead)
     if need < 0:
         raise VphoError(f'vpho_mha_bwd_workspace_bytes: bad argument (S={S}, B={B}, nhead={nhead}; at most 1024 positions)')
     ws = torch.empty(need, dtype=torch.uint8, device=qkv.device) if need > 0 else None
-    _call('vpho_mha_bwd_ws_f32', _f32(qkv), _f32(d_out), I(S), I(B), I(E), I(nhead), _f32(drop), _f32(dqkv), _ptr(ws))
+    _call('vpho_mha_bwd_ws_f32', qkv, d_out, S, B, E, nhead, drop, dqkv, ws)
     return dqkv
 
 
@@ -2404,9 +2229,8 @@ def physics_loss(scale_raw, logits, com, anchor, frame, point, gt_force_local, g
     fl, dsc, dlg, dcm = _new((bs * 32, 3), com), _new((bs * 32, 1), com), _new((bs * 32, 8), com), _new((bs * 32, 3), com)
     losses, ws = _new((5,), com, torch.float64), _new((bs * 5,), com, torch.float64)
     w5 = (C.c_float * 5)(*[float(w) for w in weights])
-    _call('vpho_physics_loss_f32', _f32(scale_raw), _f32(logits), _f32(com), _f32(anchor), F(friction), _f32(frame), _f32(point),
-          _f32(gt_force_local), _f32(gravity), _f32(gt_com), _u8(is_grasped), w5, I(bs), _f32(fl), _f32(dsc), _f32(dlg), _f32(dcm),
-          _f64(losses), _f64(ws))
+    _call('vpho_physics_loss_f32', scale_raw, logits, com, anchor, friction, frame, point, gt_force_local, gravity, gt_com, is_grasped, w5, bs, fl,
+          dsc, dlg, dcm, losses, ws)
     return fl, losses, dsc, dlg, dcm
 
 
@@ -2422,10 +2246,10 @@ _prof_on = False
 def prof_enable(name, on=True):
     global _prof_on
     _prof_on = bool(on)
-    _check(lib.vpho_prof_enable(I(PROF_CLASSES[name]), I(1 if on else 0)))
+    abi.check(abi.query('vpho_prof_enable', PROF_CLASSES[name], 1 if on else 0))
 
 
 def prof_collect(name):
     ms, n, fl, by = C.c_double(), C.c_longlong(), C.c_double(), C.c_double()
-    _check(lib.vpho_prof_collect(I(PROF_CLASSES[name]), C.byref(ms), C.byref(n), C.byref(fl), C.byref(by)))
+    abi.check(abi.query('vpho_prof_collect', PROF_CLASSES[name], C.byref(ms), C.byref(n), C.byref(fl), C.byref(by)))
     return dict(total_ms=ms.value, launches=n.value, flops=fl.value, bytes=by.value)
