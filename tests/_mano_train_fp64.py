@@ -45,15 +45,21 @@ def manopth_round_trip(Rm, eps):
     return torch.eye(3, dtype=Rm.dtype) + torch.sin(phi) * K + (1 - torch.cos(phi)) * (K @ K)
 
 
-def forward(mano, rot6d, shape, is_ho3d=None, rodrigues_eps=None):
-    """rot6d (bs, 96), shape (bs, 10) -> root-centred verts (bs, 778, 3), joints (bs, 21, 3) in metres, Gram-Schmidt matrices (bs, 16, 3, 3)"""
-    t = lambda k: torch.as_tensor(mano[k], dtype=rot6d.dtype)
-    bs = rot6d.shape[0]
-    gs = gram_schmidt(rot6d.reshape(bs, 16, 6))                       # what the pose loss reads
-    Rm = gs if rodrigues_eps is None else manopth_round_trip(gs, rodrigues_eps)
+def shape_blend(mano, shape):
+    """shape (bs, 10) -> v_shaped (bs, 778, 3), J (bs, 16, 3) in the dtype of `shape`"""
+    t = lambda k: torch.as_tensor(mano[k], dtype=shape.dtype)
     v_shaped = torch.einsum('vck,bk->bvc', t('shapedirs'), shape) + t('v_template')
-    J = torch.einsum('jv,bvc->bjc', t('J_regressor'), v_shaped)
-    pf = (Rm[:, 1:] - torch.eye(3, dtype=rot6d.dtype)).reshape(bs, 135)
+    return v_shaped, torch.einsum('jv,bvc->bjc', t('J_regressor'), v_shaped)
+
+
+def chain(mano, Rm, shape, is_ho3d=None):
+    """joint rotations Rm (bs, 16, 3, 3), shape (bs, 10) -> root-centred verts (bs, 778, 3), joints (bs, 21, 3) in metres: shape blend, J,
+    pose blend, parent-table chain, skinning with the rest joint removed, tips, root centring, manopth or HO3D joint order.  Shared by the
+    training front end (``forward``: Gram-Schmidt matrices) and the forward-kinematics one (tests/_mano_fk_fp64.py: Rodrigues)."""
+    t = lambda k: torch.as_tensor(mano[k], dtype=Rm.dtype)
+    bs = Rm.shape[0]
+    v_shaped, J = shape_blend(mano, shape)
+    pf = (Rm[:, 1:] - torch.eye(3, dtype=Rm.dtype)).reshape(bs, 135)
     v_posed = v_shaped + torch.einsum('vck,bk->bvc', t('posedirs'), pf)
     Gr, Gt = [None] * 16, [None] * 16
     for j, p in enumerate(PARENT):
@@ -72,7 +78,14 @@ def forward(mano, rot6d, shape, is_ho3d=None, rodrigues_eps=None):
     if is_ho3d is not None:
         ho = torch.cat([j21[:, TO_MANOLAYER][:, :16], x[:, TIPS_HO3D]], 1)
         j21 = torch.where(is_ho3d.bool()[:, None, None], ho, j21)
-    return x - cen, j21 - cen, gs
+    return x - cen, j21 - cen
+
+
+def forward(mano, rot6d, shape, is_ho3d=None, rodrigues_eps=None):
+    """rot6d (bs, 96), shape (bs, 10) -> root-centred verts (bs, 778, 3), joints (bs, 21, 3) in metres, Gram-Schmidt matrices (bs, 16, 3, 3)"""
+    gs = gram_schmidt(rot6d.reshape(rot6d.shape[0], 16, 6))           # what the pose loss reads
+    Rm = gs if rodrigues_eps is None else manopth_round_trip(gs, rodrigues_eps)
+    return chain(mano, Rm, shape, is_ho3d) + (gs,)
 
 
 def losses(mano, rot6d, shape, gt_vert, gt_joint, gt_rot6d, gt_shape, is_right, weights, is_ho3d=None, rodrigues_eps=None):

@@ -11,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # entry points with no wrapper named in a GPU test file, each with the reason it is acceptable.  The test fails on an entry that is no
 # longer needed, and none of the kernels of the leaf-test issues may ever be listed here (LEAF_KERNELS, CASCADE_KERNELS,
-# SPATIAL_BWD_KERNELS below).
+# SPATIAL_BWD_KERNELS, MANO_FK_KERNELS below).
 EXCEPTIONS = {
     'vpho_conv3x3_winograd_gate_nhwc_f32': 'gated Winograd input gradient of the training blocks: compared through the bottleneck / FPN / encoder training goldens only',
     'vpho_mha_f32': 'alias of vpho_mha_dropout_f32 without a mask (no wrapper): called through ops._call in test_gpu_attention.py, every forward form, the bits of ops.mha',
@@ -49,6 +49,10 @@ CASCADE_CALLED_ELSEWHERE = {'vpho_obj_fuse_f64', 'vpho_hand_phys_score_f32', 'vp
 SPATIAL_BWD_KERNELS = {'vpho_maxpool_bwd_nhwc_f32', 'vpho_maxpool_bwd_ws_nhwc_f32', 'vpho_resize_bilinear_bwd_nhwc_f32',
                        'vpho_roi_align_bwd_nhwc_f32', 'vpho_align_heatmap_bwd_nhwc_f32'}
 SPATIAL_BWD_WRAPPERS = {'maxpool_bwd', 'resize_bilinear_bwd', 'roi_align_bwd', 'align_heatmap_bwd'}
+
+# the MANO shape blend and forward kinematics, whose every launch form tests/test_gpu_mano_fk.py covers
+MANO_FK_KERNELS = {'vpho_mano_shape_f32', 'vpho_mano_fk_f32'}
+MANO_FK_WRAPPERS = {'Mano.shape', 'Mano.fk'}
 
 
 def _declared():
@@ -310,6 +314,22 @@ def test_the_spatial_backward_kernels_are_never_an_exception_and_each_wrapper_is
     tree = ast.parse(src)                                            # and the one-pass pool form is asked for by its keyword there
     assert any(isinstance(n, ast.Call) and isinstance(n.func, ast.Attribute) and n.func.attr == 'maxpool_bwd'
                and any(k.arg == 'one_pass' for k in n.keywords) for n in ast.walk(tree))
+
+
+def test_the_mano_fk_kernels_are_never_an_exception_and_each_wrapper_is_called_directly():
+    assert not (set(EXCEPTIONS) & MANO_FK_KERNELS)
+    declared = set(_declared())
+    assert MANO_FK_KERNELS <= declared, sorted(MANO_FK_KERNELS - declared)
+    W = wrappers()
+    assert MANO_FK_WRAPPERS <= set(W), sorted(MANO_FK_WRAPPERS - set(W))
+    assert W['Mano.shape'] == {'vpho_mano_shape_f32'} and W['Mano.fk'] == {'vpho_mano_fk_f32'}
+    src = open(os.path.join(ROOT, 'tests', 'test_gpu_mano_fk.py')).read()
+    calls = ops_calls_in(src, ops_classes(), ops_factories(), package_attributes())
+    assert MANO_FK_WRAPPERS <= calls, sorted(MANO_FK_WRAPPERS - calls)
+    tree = ast.parse(src)                                            # and the joints-only launch and the HO3D flags are asked for there
+    fk = [n for n in ast.walk(tree) if isinstance(n, ast.Call) and isinstance(n.func, ast.Attribute) and n.func.attr == 'fk']
+    assert any(any(k.arg == 'ho3d' for k in n.keywords) for n in fk)
+    assert any(len(n.args) >= 4 and isinstance(n.args[3], ast.Constant) and n.args[3].value is False for n in fk)
 
 
 _SAMPLE = '''
